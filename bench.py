@@ -10,8 +10,11 @@ backward + Adam) on synthetic 512x512 LArTPC crops, data-parallel over N MI355X.
 BASELINE.json configs[1]: ub_uresnet 3-class, bf16 storage / fp32 accumulate, batch 16 per GPU,
 512x512x1 -> 3 classes.  Weak scaling: per-GPU batch fixed, global batch = 16*N; the only
 exchange is the RCCL gradient all-reduce, overlapped with backward (ubresnet_amd/dist.py).
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel, timed
-live with HIP events on the launch stream) and `cpu_baseline` (the CPU oracle, N=1 only).
+Prints ONE JSON line (rank 0) with the contract fields.  A plain run does only what that line needs:
+set up, warm up, time the steps.  `--full` adds the measurements that take runs of their own:
+`roofline` (dominant kernel, one more step timed with HIP events on the launch streams), the ASPP_ResNet
+and inplanes=32 legs, the whole-view inference leg and `cpu_baseline` (the CPU oracle), N=1 only.
+`--dump-outputs DIR` writes what the last timed step computed as .npy files (see dump_outputs).
 """
 import argparse
 import json
@@ -43,16 +46,24 @@ def parse():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "f16"])
     ap.add_argument("--model", default="uresnet", choices=["uresnet", "aspp"],
                     help="aspp = BASELINE configs[3]: ASPP_ResNet on 3-plane 512x832 input")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-launch breakdown / roofline, the extra model legs, the inference leg and the CPU baseline (the --no-* switches drop single ones)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--optimizer", choices=["flat", "torch"], default="flat", help="flat: ubresnet_amd.optim.FlatAdam (one launch); torch: torch.optim.Adam(fused=True)")
     ap.add_argument("--no-breakdown", action="store_true")
     ap.add_argument("--no-infer", action="store_true", help="skip the whole-view inference leg (BASELINE configs[4])")
-    ap.add_argument("--breakdown-file", default="")
+    ap.add_argument("--breakdown-file", default="", help="per-launch breakdown table of the headline leg (needs --full)")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the ASPP_ResNet (configs[3]) and inplanes=32 (wlarcv2 variant) legs of the N=1 line")
     ap.add_argument("--extra-steps", type=int, default=5, help="timed steps of each extra leg")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the launch path (gloo, no kernels): ranks, gradient exchange and the JSON line; `value` is not a measurement")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.breakdown_file and not (a.full and not a.no_breakdown):
+        ap.error("--breakdown-file needs --full (and no --no-breakdown)")
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def _free_port():
@@ -393,7 +404,41 @@ def _rooflines(prof, dtype, pmc=None):
     return roof, tops, tot, bysym
 
 
-def train_leg(kind, inplanes, batch, size, dtype, steps, warmup, optimizer, world, rank, dev, breakdown, breakdown_file=""):
+DUMP_SAMPLE = 1 << 20     # entries kept of each large output (4 MB in fp32)
+
+
+def dump_outputs(d, model, out, loss):
+    """What a caller of the timed train step holds after its last step, as DIR/<name>.npy (float32 / float64, ~13 MB in all):
+    the loss, the log-probabilities, the gradients and the updated parameters (both in named_parameters order, flattened),
+    per-tensor gradient L2 norms and the BatchNorm running statistics.  The three large arrays are a fixed seeded sample
+    (DUMP_SAMPLE entries, same positions for the same arguments), the rest is whole."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    params = [p for _, p in model.named_parameters()]
+
+    def sample(t, seed):
+        t = t.detach().reshape(-1)
+        if t.numel() <= DUMP_SAMPLE:
+            return t.float().cpu().numpy()
+        idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).sort().values
+        return t[idx.to(t.device)].float().cpu().numpy()
+
+    with torch.no_grad():
+        grads = torch.cat([p.grad.reshape(-1) for p in params])
+        arrays = {
+            "loss": np.array([float(loss.detach().item())], np.float64),
+            "logp_sample": sample(out, 1),
+            "grad_sample": sample(grads, 2),
+            "grad_norms": torch.stack([p.grad.double().norm() for p in params]).cpu().numpy(),
+            "param_sample": sample(torch.cat([p.reshape(-1) for p in params]), 3),
+            "bn_running_stats": torch.cat([v.reshape(-1).float() for k, v in model.state_dict().items()
+                                           if k.endswith(("running_mean", "running_var"))]).cpu().numpy(),
+        }
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), v)
+
+
+def train_leg(kind, inplanes, batch, size, dtype, steps, warmup, optimizer, world, rank, dev, breakdown, breakdown_file="", dump_dir=""):
     """K timed train steps (forward + PixelWiseNLLLoss + zero_grad + backward + [gradient all-reduce] + Adam) of one model
     configuration, inputs resident in HBM; returns the fields of a bench line for it (rank 0; other ranks get the timing)."""
     from ubresnet_amd import ops, synthetic
@@ -427,7 +472,7 @@ def train_leg(kind, inplanes, batch, size, dtype, steps, warmup, optimizer, worl
     x, lab, wgt = synthetic.make_batch(batch, H, W, seed0=1000 + lo * planes, planes=planes)
     x, lab, wgt = torch.from_numpy(x).to(dev), torch.from_numpy(lab).to(dev), torch.from_numpy(wgt).to(dev)
 
-    def step():
+    def step(keep=False):
         out = model.forward(x)
         loss = crit.forward(out, lab, wgt)
         opt.zero_grad()
@@ -435,7 +480,7 @@ def train_leg(kind, inplanes, batch, size, dtype, steps, warmup, optimizer, worl
         if reducer is not None:
             reducer.finish()
         opt.step()
-        return loss
+        return (out if keep else None), loss
 
     for _ in range(warmup):
         step()
@@ -443,8 +488,8 @@ def train_leg(kind, inplanes, batch, size, dtype, steps, warmup, optimizer, worl
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        loss = step()
+    for i in range(steps):
+        out, loss = step(keep=bool(dump_dir) and i == steps - 1)      # only the last step's output outlives its step
     torch.cuda.synchronize()
     if dist.is_initialized():
         dist.barrier()
@@ -454,6 +499,9 @@ def train_leg(kind, inplanes, batch, size, dtype, steps, warmup, optimizer, worl
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     lossv = float(loss.detach().item())
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, model, out, loss)
+    del out
 
     name = "ASPP_ResNet" if kind == "aspp" else "ub_uresnet"
     res = {
@@ -551,8 +599,8 @@ def main():
     torch.cuda.set_device(dev)
 
     res = train_leg(a.model, a.inplanes, a.batch, a.size, a.dtype, a.steps, a.warmup, a.optimizer, world, rank, dev,
-                    not a.no_breakdown, a.breakdown_file)
-    solo = rank == 0 and world == 1
+                    a.full and not a.no_breakdown, a.breakdown_file, a.dump_outputs)
+    solo = rank == 0 and world == 1 and a.full
     if solo and not a.no_extra_legs and a.model == "uresnet" and a.inplanes == 16:
         # BASELINE configs[3] (ASPP_ResNet, 3 x 512 x 832; models/ASPP_ResNet.py:291) and the inplanes=32 network that
         # training/train_ubresnet2018_wlarcv2.py:88 builds ("also report ip=32"), on this one GPU, a few steps each

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 mkdir -p $O
 cd $R
-python bench.py --steps 20 --warmup 5 --breakdown-file $O/${TAG}_bench_launch_breakdown.txt > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || echo "bench failed"
+python bench.py --steps 20 --warmup 5 --full --breakdown-file $O/${TAG}_bench_launch_breakdown.txt > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || echo "bench failed"
 echo "bench done"; tail -c 300 $O/${TAG}_bench.json
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$TAG -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-breakdown --no-infer --no-extra-legs > $O/${TAG}_rocprof.log 2>&1
