@@ -1,0 +1,374 @@
+"""Float64 restatements of the two MFMA entry points of include/ubresnet_hip.h -- one ubr_conv launch (ops.conv /
+ops.conv_phases) and one weight gradient (ops.wgrad) -- written from the descriptor, not from F.conv2d, plus the checks
+the kernel tests compare with.  A helper module for the tests (imported by name; not a conftest).
+
+Exact operands.  exact_operands() draws sparse small dyadic values m * 2^e, m in {-2,-1,0,1,2}, with whole all-zero
+16x16 tiles as on LArTPC crops.  With per-channel transforms picked from scale in {0.5,1,2}, shift in {-1,0,1} and an
+integer `sub`, every operand a kernel feeds its MFMAs is a small dyadic number, exact in bf16, f16 and fp32, every
+product is exact, and every partial sum is an integer multiple of one power of two `unit`.  If, for an output, the
+sum of the absolute values of its terms (the same op on |operands|, returned alongside every reference as `absref`)
+stays below 2^24 * unit, then EVERY fp32 summation order -- any split-K, slab order, MFMA shape or tile walk -- gives
+the exact value, and the stored output must equal the fp64 reference after one round-to-nearest-even to the output
+type (ET<bf16_t> converts with v_cvt_pk_bf16_f32, RNE; torch's .to() is RNE too).  The check is then bit for bit: a
+dropped, doubled or shifted tap, tile, channel slice or pixel is off by whole units.  assert_exact() asserts the
+budget before it compares; it never assumes it.
+
+Where the budget cannot hold (outputs with huge fan-in, the fp32 statistics over a whole 512x512 batch, the
+log-softmax epilogue) assert_bounded() / assert_stats() check a stated error bound instead (constants below).
+"""
+import math
+
+import torch
+
+U32 = 2.0 ** -24          # unit roundoff of fp32 (round to nearest)
+UNIT_ROUNDOFF = {torch.float32: 2.0 ** -24, torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}
+CPU = {torch.float32: 4, torch.bfloat16: 8, torch.float16: 8}          # channels per 16-byte unit
+NEG_BIG = -3.0e38
+STAT_SLOTS, RED_SLOTS = 32, 8
+
+# assert_bounded(): |got - ref| <= C_OUT * u_out * |ref| + C_ACC * K * 2^-24 * absref.
+#   The kernel's fp32 value v^ of an output with K terms carries |v^ - ref| <= gamma_K * absref (any summation order,
+#   gamma_K = K u / (1 - K u) <= 1.01 K u for K u < 0.01); the store rounds once more: |round(v^) - v^| <= u_out |v^|
+#   <= u_out (|ref| + gamma_K absref).  With u_out <= 2^-8 the sum is below C_OUT u_out |ref| + C_ACC K u absref.
+C_OUT = 1.0
+C_ACC = 1.03
+
+# Conv statistics (ubr_conv_desc.stats).  Finding, from the epilogues of conv_igemm_kernel / conv_pc_kernel /
+# conv_thin_kernel (csrc/ubr_conv.hip, `finish` and the fast epilogue): the forward statistics sum the fp32 value
+# v = act(conv + bias (+ addend)) BEFORE it is rounded to the stored type (s1 += v; s2 += v*v); only the
+# BatchNorm-backward form (bnb_c) rounds first (round4<T> -> g, then bnb_accumulate).  The sums are fp32 per lane:
+# one lane adds one pixel of every 16-pixel row fragment it owns (a chain, in pixel order, of at most
+# N*OH*ceil(OW/16) terms, however the workgroups are laid out -- the persistent conv_pc_kernel flushes only when its
+# cout tile changes), then wave_quadrow_sum16 adds the 16 lanes of a row in 4 butterfly levels (csrc/ubr_common.h),
+# and from there on everything is fp64 (per-workgroup fp64 adds, fp64 atomics into the slots).  So each fp32 partial
+# is a sum of at most L = N*OH*ceil(OW/16) + 4 rounding steps deep, and per channel
+#     |s1 - sum v|   <= gamma_L * sum |v|          (+ fp64: 2^-50 * sum |v|)
+#     |s2 - sum v^2| <= gamma_{L+1} * sum v^2      (one more rounding: v*v in fp32)
+# The same L bounds the BatchNorm-backward sums (same lane chain, sum g_y and sum g_y*xhat; xhat = d*invstd is one
+# more rounding, covered by the +1).  stats_eps() returns these epsilons.
+
+
+# Log-softmax epilogue (ubr_conv_desc.epilogue = 1; the head's 7x7 conv, thin or generic kernel): over the n = Cout <= 16 exact fp32 logits v of a
+# pixel the kernel forms m = max v (exact), e = sum_r expf(v_r - m), lse = m + logf(e), out = v - lse, all in fp32.  With
+# expf / logf within 2 ulp (<= 4u relative; u = 2^-24):
+#   d_r = fl(v_r - m) = (v_r - m)(1 + d), |d| <= u: exp(d_r) = exp(v_r - m)(1 + u|v_r - m|); as x e^-x <= 1/e, these add
+#     at most (n/e) u e to e;  expf: 4u per term;  the sum of n terms in [0, 1]: (n - 1) u e.   So e^ = e (1 + t),
+#     |t| <= (1.4 n + 4) u  (first order; e >= 1 since the max term is 1).
+#   logf(e^) = log e + log(1 + t) + 4u |log e|, log e <= ln n:  |error| <= (1.4 n + 4 + 4 ln n) u.
+#   lse = fl(m + logf(e^)): + u |lse|;  out = fl(v - lse): + u |out|.
+# Hence |got - ref| <= u (|ref| + |lse| + 1.4 n + 4 + 4 ln n), times C_ACC for the second-order terms: logsoftmax_ref().
+
+
+def logsoftmax_ref(v):
+    """v: fp64 exact logits, channels last -> (log-softmax fp64, per-element bound of the fused epilogue; see above)"""
+    n = v.shape[-1]
+    m = v.amax(-1, keepdim=True)
+    lse = m + torch.log(torch.exp(v - m).sum(-1, keepdim=True))
+    ref = v - lse
+    return ref, C_ACC * U32 * (ref.abs() + lse.abs() + 1.4 * n + 4 + 4 * math.log(n))
+
+
+def stats_chain(N, OH, OW):
+    return N * OH * ((OW + 15) // 16) + 4
+
+
+def gamma(k):
+    ku = k * U32
+    return ku / (1.0 - ku) if ku < 0.5 else float("inf")
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# operands
+# ------------------------------------------------------------------------------------------------------------------
+def exact_operands(shape, dtype, density=0.25, seed=0, exp=0, zero_tiles=0.5, tile=16, device="cpu", maxmag=2):
+    """values m * 2^exp, m uniform in {-maxmag..-1, 1..maxmag} where nonzero; `density` of the entries nonzero; for a 4-D NHWC
+    shape, a fraction `zero_tiles` of the tile x tile pixel blocks is all zero (every channel)."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    m = torch.randint(1, maxmag + 1, shape, generator=g, device=device, dtype=torch.int32)
+    sgn = torch.randint(0, 2, shape, generator=g, device=device, dtype=torch.int32) * 2 - 1
+    keep = torch.rand(shape, generator=g, device=device) < density
+    v = torch.where(keep, (m * sgn).float(), torch.zeros((), device=device))
+    if len(shape) == 4 and zero_tiles > 0:
+        N, H, W, _ = shape
+        th, tw = (H + tile - 1) // tile, (W + tile - 1) // tile
+        z = torch.rand((N, th, tw), generator=g, device=device) < zero_tiles
+        z = z.repeat_interleave(tile, 1).repeat_interleave(tile, 2)[:, :H, :W]
+        v = v.masked_fill(z.unsqueeze(-1), 0.0)
+    return (v * 2.0 ** exp).to(dtype)
+
+
+def exact_affine(C, seed, device="cpu", relu=True, sub_exp=0):
+    """(sub, scale, shift, lo) fp32 vectors for which max((v - sub)*scale + shift, lo) is exact on exact operands:
+    sub in {-1,0,1}*2^sub_exp, scale in {0.5,1,2}, shift in {-1,0,1}; lo = 0 (ReLU) or NEG_BIG (none), or a vector"""
+    g = torch.Generator().manual_seed(seed)
+    sub = (torch.randint(-1, 2, (C,), generator=g).float() * 2.0 ** sub_exp)
+    scale = torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (C,), generator=g)]
+    shift = torch.randint(-1, 2, (C,), generator=g).float()
+    if isinstance(relu, torch.Tensor):
+        lo = relu.float().cpu()
+    else:
+        lo = torch.full((C,), 0.0 if relu else NEG_BIG)
+    return tuple(t.to(device) for t in (sub, scale, shift, lo))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# geometry
+# ------------------------------------------------------------------------------------------------------------------
+def unpack_weights(wp, Cin, Cout):
+    """packed image [ntaps][Kpad/CPU][Mpad][CPU] (ubr_pack_weights) -> fp64 [ntaps][Cin][Cout]"""
+    T, KU, Mp, cpu = wp.shape
+    return wp.double().permute(0, 1, 3, 2).reshape(T, KU * cpu, Mp)[:, :Cin, :Cout]
+
+
+def pack_dense(W, taps_idx, fwd=True):
+    """PyTorch weight [Cout][Cin][kh][kw] (fwd) or [Cin][Cout][kh][kw] (dgrad / ConvTranspose2d orientation, fwd=False)
+    -> dense fp64 [ntaps][K][M] with K the summed channel, tap image index i = tap index i of the window"""
+    Wd = W.double()
+    if fwd:
+        Wd = Wd.permute(1, 0, 2, 3)          # [Cin][Cout][kh][kw]
+    K, M = Wd.shape[0], Wd.shape[1]
+    flat = Wd.reshape(K, M, -1)
+    return flat[:, :, list(taps_idx)].permute(2, 0, 1).contiguous()
+
+
+def _xform(x, xf):
+    v = x.double()
+    if xf is not None:
+        sub, scale, shift, lo = (t.double().to(v.device) for t in xf)
+        C = v.shape[-1]
+        v = torch.maximum((v - sub[:C]) * scale[:C] + shift[:C], lo[:C])
+    return v
+
+
+def _gather(xt, taps, S, iy0, ix0, OH, OW):
+    """yield (tap number, view [N,OH,OW,C] of the zero-padded input at oy*S+iy0+dy, ox*S+ix0+dx)"""
+    N, H, W, C = xt.shape
+    dys = [t[0] for t in taps]
+    dxs = [t[1] for t in taps]
+    pt = max(0, -(iy0 + min(dys)))
+    pb = max(0, (OH - 1) * S + iy0 + max(dys) - (H - 1))
+    pl = max(0, -(ix0 + min(dxs)))
+    pr = max(0, (OW - 1) * S + ix0 + max(dxs) - (W - 1))
+    xp = torch.nn.functional.pad(xt, (0, 0, pl, pr, pt, pb))
+    for i, (dy, dx) in enumerate(zip(dys, dxs)):
+        y0, x0 = iy0 + dy + pt, ix0 + dx + pl
+        yield i, xp[:, y0:y0 + (OH - 1) * S + 1:S, x0:x0 + (OW - 1) * S + 1:S, :]
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# ubr_conv
+# ------------------------------------------------------------------------------------------------------------------
+def conv_ref(x, W, taps, Cout, OH, OW, S=1, iy0=0, ix0=0, xf=None, bias=None, addend=None, addend_mask=None, act=0,
+             want_abs=True):
+    """fp64 value of what ONE ubr_conv launch computes, and the same op on |operands| (the budget):
+        out(oy,ox,co) = act( bias[co] + addend*bit + sum_t sum_ci xform(x)(oy*S+iy0+dy[t], ox*S+ix0+dx[t], ci) * W[wt[t]][ci][co] )
+    x: NHWC [N,H,W,Cin]; W: fp64 [ntaps_img][Cin][Cout] (unpack_weights of the packed image); taps [(dy,dx,wt)];
+    xf: (sub, scale, shift, lo) or None (zero padding AFTER the transform); addend: NHWC [N,OH,OW,Cout];
+    addend_mask: uint8 [N*OH*OW*Cout/CPU] bits (channel e of unit u = bit e of byte u); act: bit 0 ReLU before the addend,
+    bit 1 ReLU after it.  Returns (ref, absref), fp64 [N,OH,OW,Cout]."""
+    xt = _xform(x, xf)
+    N = xt.shape[0]
+    Cin = xt.shape[3]
+    Wd = W.double().to(xt.device)
+    acc = torch.zeros((N, OH, OW, Cout), dtype=torch.float64, device=xt.device)
+    accabs = torch.zeros_like(acc) if want_abs else None
+    for i, v in _gather(xt, taps, S, iy0, ix0, OH, OW):
+        wt = Wd[taps[i][2], :Cin, :Cout]
+        acc += torch.matmul(v, wt)
+        if want_abs:
+            accabs += torch.matmul(v.abs(), wt.abs())
+    if bias is not None:
+        b = bias.double().to(acc.device)[:Cout]
+        acc += b
+        if want_abs:
+            accabs += b.abs()
+    if act & 1:
+        acc = acc.clamp_min(0)
+    if addend is not None:
+        a = addend.double().to(acc.device)
+        if addend_mask is not None:
+            a = a * mask_bits(addend_mask, a.shape, CPU[addend.dtype]).to(acc.device)
+        acc = acc + a
+        if want_abs:
+            accabs = accabs + a.abs()
+    if act & 2:
+        acc = acc.clamp_min(0)
+    return acc, accabs
+
+
+def mask_bits(mask, shape, cpu):
+    N, OH, OW, C = shape
+    m = mask[:N * OH * OW * (C // cpu)].view(N, OH, OW, C // cpu, 1).to(torch.int32)
+    bits = (m >> torch.arange(cpu, device=mask.device, dtype=torch.int32)) & 1
+    return bits.reshape(N, OH, OW, C).double()
+
+
+def conv_phases_ref(x, W, phases, Cout, OH, OW, xf=None, bias=None, addend_full=None):
+    """fp64 value of a phased launch (ops.conv_phases): phase (ry, rx, taps) writes y_full[:, ry::2, rx::2] (OH x OW each);
+    addend_full (optional) has y_full's shape.  Returns (ref, absref) of y_full's shape; positions no phase writes are NaN."""
+    N = x.shape[0]
+    ref = torch.full((N, 2 * OH, 2 * OW, Cout), float("nan"), dtype=torch.float64, device=x.device)
+    ab = ref.clone()
+    for ry, rx, tp in phases:
+        ad = addend_full[:, ry::2, rx::2, :] if addend_full is not None else None
+        r, a = conv_ref(x, W, tp, Cout, OH, OW, xf=xf, bias=bias, addend=ad)
+        ref[:, ry::2, rx::2, :] = r
+        ab[:, ry::2, rx::2, :] = a
+    return ref, ab
+
+
+def round_to(ref, dtype):
+    """one RNE rounding of an fp64 value that is exact in fp32 (the budget) to the stored type"""
+    return ref.float().to(dtype)
+
+
+def conv_stats_ref(v, bnb=None, dtype=None):
+    """per-channel reference sums of ubr_conv_desc.stats over the output grid: (s1, s2, a1, a2) fp64 [C] with a = sum of |terms|.
+    Forward statistics: s1 = sum v, s2 = sum v^2 of the fp32 value BEFORE it is stored (see the note at the top).
+    bnb = (c, mean, scale, shift, invstd): BatchNorm-backward sums of the STORED output g = round(v):
+    s1 = sum g*[bn(c) > 0], s2 = sum g*[bn(c) > 0] * (c - mean)*invstd, bn(c) = (c - mean)*scale + shift."""
+    C = v.shape[-1]
+    if bnb is None:
+        f = v.reshape(-1, C)
+        return f.sum(0), (f * f).sum(0), f.abs().sum(0), (f * f).sum(0)
+    c, mean, scale, shift, invstd = bnb
+    g = round_to(v, dtype).double().reshape(-1, C)
+    cd = c.double().reshape(-1, C).to(g.device)
+    d = cd - mean.double().to(g.device)
+    bn = d * scale.double().to(g.device) + shift.double().to(g.device)
+    gy = torch.where(bn > 0, g, torch.zeros((), dtype=g.dtype, device=g.device))
+    t2 = gy * (d * invstd.double().to(g.device))
+    return gy.sum(0), t2.sum(0), gy.abs().sum(0), t2.abs().sum(0)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# ubr_wgrad (+ ubr_wgrad_reduce)
+# ------------------------------------------------------------------------------------------------------------------
+def wgrad_ref(x, g, taps, S=1, iy0=0, ix0=0, xf=None, want_abs=True):
+    """dW[t][co][ci] = sum_{n,oy,ox} g(n,oy,ox,co) * xform(x)(n, oy*S+iy0+dy[t], ox*S+ix0+dx[t], ci), fp64 [ntaps][Cout][Cin],
+    and the same op on |operands|.  taps: [(dy, dx, anything)]."""
+    xt = _xform(x, xf)
+    gd = g.double().to(xt.device)
+    N, GH, GW, Cout = gd.shape
+    Cin = xt.shape[3]
+    g2 = gd.reshape(-1, Cout).t()
+    ga = g2.abs() if want_abs else None
+    out = torch.empty((len(taps), Cout, Cin), dtype=torch.float64, device=xt.device)
+    ab = torch.empty_like(out) if want_abs else None
+    for i, v in _gather(xt, taps, S, iy0, ix0, GH, GW):
+        v2 = v.reshape(-1, Cin)
+        out[i] = _mm_long(g2, v2)
+        if want_abs:
+            ab[i] = _mm_long(ga, v2.abs())
+    return out, ab
+
+
+def _mm_long(a, b, chunk=1 << 14):
+    """a [M, P] @ b [P, K] for a long P (every pixel of a batch) as a batch of P/chunk products summed in fp64: a GEMM library
+    runs a 16 x 4M x 16 product on a handful of workgroups (values are exact either way)"""
+    P = a.shape[1]
+    if P <= 4 * chunk:
+        return a @ b
+    nb = (P + chunk - 1) // chunk
+    pad = nb * chunk - P
+    a = torch.nn.functional.pad(a, (0, pad)).view(a.shape[0], nb, chunk).transpose(0, 1)
+    b = torch.nn.functional.pad(b, (0, 0, 0, pad)).view(nb, chunk, b.shape[1])
+    return torch.bmm(a, b).sum(0)
+
+
+def wgrad_scatter(dW, dst_numel, taps, sm, sk, Cout_valid, Cin_valid, dst_offset=0, init=None):
+    """ubr_wgrad_reduce's scatter: dst[dst_offset + co*sm + ci*sk + tapidx[t]] (+)= dW[t][co][ci] for co < Cout_valid,
+    ci < Cin_valid.  init: the destination before the launch (fp64, accumulate); returns (value, touched-mask) flat fp64 / bool"""
+    dev = dW.device
+    out = torch.zeros(dst_numel, dtype=torch.float64, device=dev) if init is None else init.double().to(dev).clone()
+    touched = torch.zeros(dst_numel, dtype=torch.bool, device=dev)
+    co = torch.arange(Cout_valid, device=dev).view(-1, 1)
+    ci = torch.arange(Cin_valid, device=dev).view(1, -1)
+    for t, tp in enumerate(taps):
+        idx = (dst_offset + co * sm + ci * sk + tp[2]).reshape(-1)
+        out.index_add_(0, idx, dW[t, :Cout_valid, :Cin_valid].reshape(-1))
+        touched[idx] = True
+    return out, touched
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# checks
+# ------------------------------------------------------------------------------------------------------------------
+def budget_ok(absref, unit):
+    return float(absref.max()) < 2.0 ** 24 * unit if absref.numel() else True
+
+
+def assert_exact(got, ref, dtype, absref=None, unit=None, what=""):
+    """got (stored, `dtype`) must equal round_to(ref, dtype) element for element (+0 == -0).  With absref / unit, first
+    asserts the budget max(absref) < 2^24 * unit that makes every fp32 summation order exact, and that ref is on the grid."""
+    if absref is not None:
+        assert unit is not None
+        amax = float(absref.max()) if absref.numel() else 0.0
+        assert amax < 2.0 ** 24 * unit, "%s: budget %.6g units >= 2^24: not an exact case" % (what, amax / unit)
+        q = ref / unit
+        fin = torch.isfinite(q)
+        assert torch.equal(q[fin], q[fin].round()), "%s: reference not on the 2^%d grid" % (what, round(math.log2(unit)))
+    exp = round_to(ref, dtype).to(got.device)
+    g = got.float()
+    e = exp.float()
+    bad = ~((g == e) | (torch.isnan(g) & torch.isnan(e)))
+    if bool(bad.any()):
+        idx = bad.nonzero()[0].tolist()
+        nb = int(bad.sum())
+        bud = (" budget %.6g units" % (float(absref[tuple(idx)]) / unit)) if absref is not None else ""
+        raise AssertionError("%s: %d of %d elements differ; first at %s: got %r, expected %r (fp64 %r)%s"
+                             % (what, nb, bad.numel(), tuple(idx), float(g[tuple(idx)]), float(e[tuple(idx)]),
+                                float(ref[tuple(idx)]), bud))
+
+
+def bound(ref, absref, dtype, K):
+    return C_OUT * UNIT_ROUNDOFF[dtype] * ref.abs() + C_ACC * K * U32 * absref
+
+
+def assert_bounded(got, ref, absref, dtype, K, what=""):
+    """|got - ref| <= C_OUT * u_out * |ref| + C_ACC * K * 2^-24 * absref per element (K: terms per output)"""
+    ref = ref.to(got.device)
+    assert_within(got, ref, bound(ref, absref.to(got.device), dtype, K), what)
+
+
+def assert_within(got, ref, lim, what=""):
+    """|got - ref| <= lim per element"""
+    ref, lim = ref.to(got.device), lim.to(got.device)
+    err = (got.double() - ref).abs()
+    bad = ~(err <= lim)
+    if bool(bad.any()):
+        idx = bad.nonzero()[0].tolist()
+        raise AssertionError("%s: %d elements outside the bound; first at %s: got %r, fp64 %r, |err| %.3e > %.3e"
+                             % (what, int(bad.sum()), tuple(idx), float(got[tuple(idx)]), float(ref[tuple(idx)]),
+                                float(err[tuple(idx)]), float(lim[tuple(idx)])))
+
+
+def stats_eps(L):
+    """(eps1, eps2) of the per-channel statistics bound for an fp32 partial chain of L (see the note at the top)"""
+    return gamma(L) + 2.0 ** -50, gamma(L + 1) + 2.0 ** -50
+
+
+def assert_stats(s, refs, L, unit=None, unit2=None, what=""):
+    """s: fp64 [2C] = the slots summed; refs = conv_stats_ref(...).  Exact when both budgets hold (sum |terms| < 2^24 units
+    of the term grid, v^2 exact in fp32), else |s - ref| <= eps * sum |terms| per channel.  Returns 'exact' / 'bounded'."""
+    s1r, s2r, a1, a2 = (t.to(s.device) for t in refs)
+    C = s1r.numel()
+    s1, s2 = s[:C], s[C:2 * C]
+    if unit2 is None and unit is not None:
+        unit2 = unit * unit
+    exact = unit is not None and float(a1.max()) < 2.0 ** 24 * unit and float(a2.max()) < 2.0 ** 24 * unit2
+    if exact:
+        for nm, a, b in (("sum", s1, s1r), ("sum of squares", s2, s2r)):
+            if not torch.equal(a, b):
+                c = int((a != b).nonzero()[0])
+                raise AssertionError("%s: stats %s of channel %d: got %r, exact %r" % (what, nm, c, float(a[c]), float(b[c])))
+        return "exact"
+    e1, e2 = stats_eps(L)
+    for nm, a, b, ab, e in (("sum", s1, s1r, a1, e1), ("sum of squares", s2, s2r, a2, e2)):
+        err = (a - b).abs()
+        bad = ~(err <= e * ab)
+        if bool(bad.any()):
+            c = int(bad.nonzero()[0])
+            raise AssertionError("%s: stats %s of channel %d: got %r, fp64 %r, |err| %.3e > %.2e * %.3e"
+                                 % (what, nm, c, float(a[c]), float(b[c]), float(err[c]), e, float(ab[c])))
+    return "bounded"

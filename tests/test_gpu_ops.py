@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import kref
+
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
@@ -144,7 +146,46 @@ def test_conv_forward(case, dt):
         n = N * OH * OW
         rs, rss = ref.sum(dim=(0, 2, 3)).double(), (ref.double() ** 2).sum(dim=(0, 2, 3))
         assert (s[:Cout] - rs).abs().max().item() <= tol(dt) * n * max(ref.abs().max().item(), 1e-6)
+        # per channel: the statistics sum the kernel's fp32 outputs, each within 1.03*K*2^-24*absref of the exact value (as is
+        # the fp32 reference), plus the fp32 partial-sum error of kref.stats_eps over the lane chain (tests/kref.py)
+        K = Cin * k * k + 2
+        absref = F.conv2d(xin.abs(), rnd(dt, w).abs(), b.abs() if bias else None, stride, pad, dil)
+        if addend:
+            absref = absref + ad.abs()
+        e1, _ = kref.stats_eps(kref.stats_chain(N, OH, OW))
+        lim = 2 * kref.C_ACC * K * kref.U32 * absref.double().sum(dim=(0, 2, 3)) + e1 * ref.abs().double().sum(dim=(0, 2, 3)) + 1e-9
+        assert bool(((s[:Cout] - rs).abs() <= lim).all()), "stats sum: %.3e > %.3e" % ((s[:Cout] - rs).abs().max(), lim.min())
+        # (both lines hold: the per-channel bound is the tight one in 16-bit types, the line above can be in fp32)
         assert (s[Cout:] - rss).abs().max().item() <= 2 * tol(dt) * rss.max().item() + 1e-6
+    _conv_forward_exact(case, dt)
+
+
+def _conv_forward_exact(case, dt):
+    """the same launch on exact operands (tests/kref.py): output bit for bit, statistics exact or within the derived bound,
+    the rest of the output buffer untouched"""
+    N, H, W, Cin, Cout, k, stride, dil, xf, bias, stats, addend, hint = case
+    pad = dil * (k // 2)
+    taps = ops.conv_taps(k, dil, pad)
+    x = kref.exact_operands((N, H, W, Cin), dt, seed=101, device=DEV)
+    wd = kref.exact_operands((Cout, Cin, k, k), torch.float32, seed=102, density=0.5, exp=-1)
+    b = kref.exact_operands((Cout,), torch.float32, seed=103, density=0.8, exp=-2, device=DEV) if bias else None
+    xfr = kref.exact_affine(Cin, 104, device=DEV) if xf else None
+    OH, OW = (H + 2 * pad - dil * (k - 1) - 1) // stride + 1, (W + 2 * pad - dil * (k - 1) - 1) // stride + 1
+    ad = kref.exact_operands((N, OH, OW, Cout), dt, seed=105, exp=-2, device=DEV) if addend else None
+    xbuf = torch.full((N, H, W, Cin + 16), float("nan"), dtype=dt, device=DEV)
+    xbuf[..., 16:] = x
+    ybuf = torch.full((N, OH, OW, Cout + 32), 7.0, dtype=dt, device=DEV)
+    st = statbuf(2 * Cout) if stats else None
+    wp = ops.pack_weights(wd.to(DEV), dt, Cout, Cin, Cin * k * k, k * k, k * k)
+    ops.conv(xbuf[..., 16:], wp, ybuf[..., 32:], taps, Cout, S=stride, xf=Affine(*xfr) if xf else None, bias=b, addend=ad, stats=st,
+             tile_hint=hint)
+    torch.cuda.synchronize()
+    ref, ab = kref.conv_ref(x, kref.pack_dense(wd, range(k * k)), taps, Cout, OH, OW, S=stride, xf=xfr, bias=b, addend=ad)
+    what = "exact operands, %s" % ops.last_conv_kernel()
+    kref.assert_exact(ybuf[..., 32:], ref, dt, ab, 0.25, what)
+    assert (ybuf[..., :32].float() == 7.0).all(), "conv wrote outside its channel slice"
+    if stats:
+        kref.assert_stats(slotsum(st, 2 * Cout), kref.conv_stats_ref(ref), kref.stats_chain(N, OH, OW), 0.25, what=what)
 
 
 @pytest.mark.parametrize("dt", DTS + [torch.float16])
@@ -212,6 +253,42 @@ def test_conv_training_epilogues(dt, shape):
         ops.conv(x, wp, y3, taps, Cout, addend=ad, addend_mask=mask)
         torch.cuda.synchronize()
         assert torch.equal(y3, y2)
+    _training_epilogues_exact(dt, shape)
+
+
+def _training_epilogues_exact(dt, shape):
+    """the same two epilogues on exact operands (tests/kref.py): the output bit for bit, the BatchNorm-backward sums of the
+    stored output exact or within kref's bound, only the UBR_RED_SLOTS stripes used; the masked addend bit for bit"""
+    N, H, W, Cin, Cout, ksz = shape
+    taps = ops.conv_taps(ksz, 1, ksz // 2)
+    x = kref.exact_operands((N, H, W, Cin), dt, seed=121, device=DEV)
+    wd = kref.exact_operands((Cout, Cin, ksz, ksz), torch.float32, seed=122, density=0.5, exp=-1)
+    wp = ops.pack_weights(wd.to(DEV), dt, Cout, Cin, Cin * ksz * ksz, ksz * ksz, ksz * ksz)
+    Wd = kref.pack_dense(wd, range(ksz * ksz))
+    c = kref.exact_operands((N, H, W, Cout), dt, seed=123, density=0.6, device=DEV)
+    g_ = torch.Generator().manual_seed(124)
+    pick = lambda vals: torch.tensor(vals)[torch.randint(0, len(vals), (Cout,), generator=g_)].to(DEV)
+    mean, scale, shift, invstd = pick([-1., 0., 1.]), pick([0.5, 1., 2.]), pick([-1., 0., 1.]), pick([0.5, 1., 2.])
+    y = torch.full((N, H, W, Cout), float("nan"), dtype=dt, device=DEV)
+    red = statbuf(2 * Cout)
+    ops.conv(x, wp, y, taps, Cout, bnb=(c, mean, scale, shift, invstd), stats=red)
+    torch.cuda.synchronize()
+    ref, ab = kref.conv_ref(x, Wd, taps, Cout, H, W)
+    what = "exact operands, %s" % ops.last_conv_kernel()
+    kref.assert_exact(y, ref, dt, ab, 0.25, what)
+    assert float(red.view(SLOTS, -1)[8:].abs().max()) == 0.0
+    kref.assert_stats(slotsum(red, 2 * Cout), kref.conv_stats_ref(ref, (c, mean, scale, shift, invstd), dt), kref.stats_chain(N, H, W),
+                      0.25, 0.125, what)
+    cpu_ = kref.CPU[dt]
+    if Cout % cpu_ == 0:
+        ad = kref.exact_operands((N, H, W, Cout), dt, seed=125, exp=-2, device=DEV)
+        mask = torch.randint(0, 256, (N * H * W * (Cout // cpu_),), dtype=torch.uint8, device=DEV,
+                             generator=torch.Generator(device=DEV).manual_seed(126))
+        y3 = torch.full_like(y, float("nan"))
+        ops.conv(x, wp, y3, taps, Cout, addend=ad, addend_mask=mask)
+        torch.cuda.synchronize()
+        ref, ab = kref.conv_ref(x, Wd, taps, Cout, H, W, addend=ad, addend_mask=mask)
+        kref.assert_exact(y3, ref, dt, ab, 0.25, "masked addend, " + what)
 
 
 @pytest.mark.parametrize("dt", DTS)
@@ -316,6 +393,44 @@ def test_deconv_forward_and_grads(dt, chans):
             ops.wgrad(xd, gup[:, ry::2, rx::2, :], ops.transposed_phase_taps(4, 1, 1, 2, ry, rx), dW, 16, Cd * 16, Cd, Cin, ws)
     torch.cuda.synchronize()
     close(dW.cpu(), wr.grad, 2 * tol(dt), "deconv wgrad")
+    _deconv_exact(dt, N, H, W, Cin, Cd)
+
+
+def _deconv_exact(dt, N, H, W, Cin, Cd):
+    """ConvTranspose2d(k4, s2, p1) phases, its data gradient (stride-2 4x4 conv) and its weight gradient (four tap subsets into
+    one [Cin][Cd][4][4] tensor) on exact operands, bit for bit against tests/kref.py; the concat slice's neighbours untouched"""
+    x = kref.exact_operands((N, H, W, Cin), dt, seed=131, device=DEV)
+    w = kref.exact_operands((Cin, Cd, 4, 4), torch.float32, seed=132, density=0.5, exp=-1)
+    Wd = kref.pack_dense(w, range(16), fwd=False)
+    wp = ops.pack_weights(w.to(DEV), dt, Cd, Cin, 16, Cd * 16, 16)
+    cat = torch.full((N, 2 * H, 2 * W, Cd + 16), 5.0, dtype=dt, device=DEV)
+    phases = [(ry, rx, ops.transposed_phase_taps(4, 1, 1, 2, ry, rx)) for ry in range(2) for rx in range(2)]
+    for ry, rx, tp in phases:
+        ops.conv(x, wp, cat[:, ry::2, rx::2, :Cd], tp, Cd)
+    torch.cuda.synchronize()
+    ref, ab = kref.conv_phases_ref(x, Wd, phases, Cd, H, W)
+    kref.assert_exact(cat[..., :Cd], ref, dt, ab, 0.25, "deconv fwd, exact operands, %s" % ops.last_conv_kernel())
+    assert (cat[..., Cd:].float() == 5.0).all()
+    g = kref.exact_operands((N, 2 * H, 2 * W, Cd), dt, seed=133, exp=-1, device=DEV)
+    gx = torch.full((N, H, W, Cin), float("nan"), dtype=dt, device=DEV)
+    wpd = ops.pack_weights(w.to(DEV), dt, Cin, Cd, Cd * 16, 16, 16)
+    ops.conv(g, wpd, gx, ops.conv_taps(4, 1, 1), Cin, S=2)
+    torch.cuda.synchronize()
+    ref, ab = kref.conv_ref(g, kref.pack_dense(w, range(16)), ops.conv_taps(4, 1, 1), Cin, H, W, S=2)
+    kref.assert_exact(gx, ref, dt, ab, 0.25, "deconv dgrad, exact operands, %s" % ops.last_conv_kernel())
+    n = Cin * Cd * 16
+    dW = torch.full((n + 16,), float("nan"), device=DEV)
+    exp, ab, touched = None, None, torch.zeros(n + 16, dtype=torch.bool, device=DEV)
+    ws = ops.WgradWorkspace()
+    for ry, rx, tp in phases:
+        ops.wgrad(x, g[:, ry::2, rx::2, :], tp, dW, 16, Cd * 16, Cd, Cin, ws)
+        r, a = kref.wgrad_ref(x, g[:, ry::2, rx::2, :], tp)
+        exp, t = kref.wgrad_scatter(r, n + 16, tp, 16, Cd * 16, Cd, Cin, init=exp)
+        ab, _ = kref.wgrad_scatter(a, n + 16, tp, 16, Cd * 16, Cd, Cin, init=ab)
+        touched |= t
+    torch.cuda.synchronize()
+    assert int(touched.sum()) == n and bool(torch.isnan(dW[n:]).all())
+    kref.assert_exact(dW[:n], exp[:n], torch.float32, ab[:n], 0.25, "deconv wgrad, exact operands")
 
 
 GRAD_CASES = [
@@ -339,14 +454,21 @@ GRAD_CASES = [
     (1, 16, 16, 128, 64, 1, 1, False),
     (1, 8, 8, 128, 64, 1, 2, False),
     (2, 12, 20, 64, 64, 3, 1, False),
+    # N, H, W, Cin, Cout, k, stride, xf, dilation: the ASPP branches' halos of 3 and 5 (wgrad_plan's halo-fit fallbacks)
+    (1, 32, 48, 64, 16, 3, 1, False, 3),
+    (1, 32, 52, 128, 16, 3, 1, True, 5),
+    (2, 24, 40, 32, 32, 3, 1, False, 5),
+    (2, 64, 64, 32, 64, 3, 2, True),
+    (1, 64, 96, 16, 32, 1, 2, False),
 ]
 
 
 @pytest.mark.parametrize("dt", DTS)
 @pytest.mark.parametrize("case", GRAD_CASES)
 def test_conv_dgrad_wgrad(case, dt):
-    N, H, W, Cin, Cout, k, stride, xf = case
-    pad = k // 2
+    N, H, W, Cin, Cout, k, stride, xf, *rest = case
+    dil = rest[0] if rest else 1
+    pad = dil * (k // 2)
     x = rnd(dt, gen(N, Cin, H, W, seed=1))
     w = gen(Cout, Cin, k, k, seed=2, scale=(2.0 / (k * k * Cin)) ** 0.5)
     aff, xin = None, x
@@ -356,17 +478,17 @@ def test_conv_dgrad_wgrad(case, dt):
         aff = Affine(lo_zero(Cin), sc.to(DEV), sh.to(DEV), lo_zero(Cin))
     xr = xin.clone().requires_grad_(True)
     wr = rnd(dt, w).clone().requires_grad_(True)
-    y = F.conv2d(xr, wr, None, stride, pad)
+    y = F.conv2d(xr, wr, None, stride, pad, dil)
     g = rnd(dt, gen(*y.shape, seed=3))
     y.backward(g)
     gd = nhwc(g, dt)
     # ---- weight gradient ----
     dW = torch.full((Cout, Cin, k, k), 3.0, device=DEV)
-    ops.wgrad(nhwc(x, dt), gd, ops.conv_taps(k, 1, pad), dW, Cin * k * k, k * k, Cout, Cin, ops.WgradWorkspace(), S=stride, xf=aff)
+    ops.wgrad(nhwc(x, dt), gd, ops.conv_taps(k, dil, pad), dW, Cin * k * k, k * k, Cout, Cin, ops.WgradWorkspace(), S=stride, xf=aff)
     torch.cuda.synchronize()
     close(dW.cpu(), wr.grad, 2 * tol(dt), "wgrad")
     # accumulate flag
-    ops.wgrad(nhwc(x, dt), gd, ops.conv_taps(k, 1, pad), dW, Cin * k * k, k * k, Cout, Cin, ops.WgradWorkspace(), S=stride, xf=aff, accumulate=True)
+    ops.wgrad(nhwc(x, dt), gd, ops.conv_taps(k, dil, pad), dW, Cin * k * k, k * k, Cout, Cin, ops.WgradWorkspace(), S=stride, xf=aff, accumulate=True)
     close(dW.cpu(), 2 * wr.grad, 2 * tol(dt), "wgrad accumulate")
     # ---- data gradient (w.r.t. the conv input as the conv saw it) ----
     wpd = ops.pack_weights(w.to(DEV), dt, Cin, Cout, k * k, Cin * k * k, k * k)
@@ -374,16 +496,61 @@ def test_conv_dgrad_wgrad(case, dt):
     ad = rnd(dt, gen(N, Cin, H, W, seed=9))
     add = nhwc(ad, dt)
     if stride == 1:
-        ops.conv(gd, wpd, gx, ops.conv_dgrad_taps_s1(k, 1, pad), Cin, addend=add)
+        ops.conv(gd, wpd, gx, ops.conv_dgrad_taps_s1(k, dil, pad), Cin, addend=add)
     else:
         gx.copy_(add)
         for ry in range(2):
             for rx in range(2):
-                taps = ops.transposed_phase_taps(k, 1, pad, 2, ry, rx)
+                taps = ops.transposed_phase_taps(k, dil, pad, 2, ry, rx)
                 if taps:
                     ops.conv(gd, wpd, gx[:, ry::2, rx::2, :], taps, Cin, addend=gx[:, ry::2, rx::2, :])
     torch.cuda.synchronize()
     close(nchw(gx), xr.grad + ad, tol(dt), "dgrad")
+    _dgrad_wgrad_exact(N, H, W, Cin, Cout, k, stride, dil, xf, dt)
+
+
+def _dgrad_wgrad_exact(N, H, W, Cin, Cout, k, stride, dil, xf, dt):
+    """the same launches on exact operands (tests/kref.py): weight gradient (one launch and accumulating) and data gradient
+    bit for bit against the fp64 reference, entries outside the weight layout / output untouched"""
+    pad = dil * (k // 2)
+    OH, OW = (H + 2 * pad - dil * (k - 1) - 1) // stride + 1, (W + 2 * pad - dil * (k - 1) - 1) // stride + 1
+    x = kref.exact_operands((N, H, W, Cin), dt, seed=111, device=DEV)
+    g = kref.exact_operands((N, OH, OW, Cout), dt, seed=112, exp=-1, device=DEV)
+    xfr = kref.exact_affine(Cin, 113, device=DEV) if xf else None
+    taps = ops.conv_taps(k, dil, pad)
+    n = Cout * Cin * k * k
+    dW = torch.full((n + 16,), float("nan"), device=DEV)
+    ops.wgrad(x, g, taps, dW, Cin * k * k, k * k, Cout, Cin, ops.WgradWorkspace(), S=stride, xf=Affine(*xfr) if xf else None)
+    torch.cuda.synchronize()
+    ref, ab = kref.wgrad_ref(x, g, taps, S=stride, xf=xfr)
+    exp, touched = kref.wgrad_scatter(ref, n + 16, taps, Cin * k * k, k * k, Cout, Cin)
+    abs_, _ = kref.wgrad_scatter(ab, n + 16, taps, Cin * k * k, k * k, Cout, Cin)
+    assert int(touched.sum()) == n and bool(torch.isnan(dW[n:]).all())
+    kref.assert_exact(dW[:n], exp[:n], torch.float32, abs_[:n], 0.25, "wgrad, exact operands")
+    ops.wgrad(x, g, taps, dW, Cin * k * k, k * k, Cout, Cin, ops.WgradWorkspace(), S=stride, xf=Affine(*xfr) if xf else None, accumulate=True)
+    torch.cuda.synchronize()
+    kref.assert_exact(dW[:n], 2 * exp[:n], torch.float32, 2 * abs_[:n], 0.25, "wgrad accumulate, exact operands")
+    # data gradient (stride 1: one launch; stride 2: one launch per phase into the strided views, over an addend in place)
+    wd = kref.exact_operands((Cout, Cin, k, k), torch.float32, seed=114, density=0.5, exp=-1)
+    wpd = ops.pack_weights(wd.to(DEV), dt, Cin, Cout, k * k, Cin * k * k, k * k)
+    Wd = kref.pack_dense(wd, range(k * k), fwd=False)
+    ad = kref.exact_operands((N, H, W, Cin), dt, seed=115, exp=-2, device=DEV)
+    gx = ad.clone()
+    if stride == 1:
+        gtaps = ops.conv_dgrad_taps_s1(k, dil, pad)
+        ops.conv(g, wpd, gx, gtaps, Cin, addend=gx)
+        ref, ab = kref.conv_ref(g, Wd, gtaps, Cin, H, W, addend=ad)
+    else:
+        phases = [(ry, rx, ops.transposed_phase_taps(k, dil, pad, 2, ry, rx)) for ry in range(2) for rx in range(2)]
+        phases = [p for p in phases if p[2]]
+        for ry, rx, tp in phases:
+            ops.conv(g, wpd, gx[:, ry::2, rx::2, :], tp, Cin, addend=gx[:, ry::2, rx::2, :])
+        ref, ab = ad.double(), ad.double().abs()
+        for ry, rx, tp in phases:
+            r, a = kref.conv_ref(g, Wd, tp, Cin, H // 2, W // 2, addend=ad[:, ry::2, rx::2, :])
+            ref[:, ry::2, rx::2, :], ab[:, ry::2, rx::2, :] = r, a
+    torch.cuda.synchronize()
+    kref.assert_exact(gx, ref, dt, ab, 0.25, "dgrad, exact operands, %s" % ops.last_conv_kernel())
 
 
 @pytest.mark.parametrize("dt", DTS)
@@ -414,6 +581,38 @@ def test_stem(cfg, dt):
     torch.cuda.synchronize()
     close(dW.cpu(), wr.grad, 1e-4, "stem wgrad")
     close(dB.cpu(), br.grad, 1e-4, "stem bgrad")
+    _stem_exact(dt, N, Cin, H, W, Cout)
+
+
+def _stem_exact(dt, N, Cin, H, W, Cout):
+    """ubr_stem_forward / ubr_stem_wgrad on exact operands (tests/kref.py): output, weight and bias gradients bit for bit,
+    statistics exact or within kref's bound for a chain as long as the whole channel (any summation order)"""
+    x = kref.exact_operands((N, H, W, Cin), torch.float32, seed=141, zero_tiles=0.3)
+    x[0, :16, :16, :] = 0.0
+    w = kref.exact_operands((Cout, Cin, 7, 7), torch.float32, seed=142, density=0.5, exp=-1)
+    b = kref.exact_operands((Cout,), torch.float32, seed=143, density=0.8, exp=-2)
+    taps = ops.conv_taps(7, 1, 3)
+    xd = x.permute(0, 3, 1, 2).contiguous().to(DEV)
+    y = torch.full((N, H, W, Cout), float("nan"), dtype=dt, device=DEV)
+    st = statbuf(2 * Cout)
+    ops.stem_forward(xd, w.to(DEV), b.to(DEV), y, st)
+    torch.cuda.synchronize()
+    ref, ab = kref.conv_ref(x.to(DEV), kref.pack_dense(w, range(49)), taps, Cout, H, W, bias=b)
+    kref.assert_exact(y, ref, dt, ab, 0.25, "stem fwd, exact operands")
+    kref.assert_stats(slotsum(st, 2 * Cout), kref.conv_stats_ref(ref), N * H * W + 4, 0.25, what="stem stats, exact operands")
+    g = kref.exact_operands((N, H, W, Cout), dt, seed=144, exp=-1, device=DEV)
+    dW = torch.full((Cout, Cin, 7, 7), float("nan"), device=DEV)
+    dB = torch.full((Cout,), float("nan"), device=DEV)
+    ops.stem_wgrad(xd, g, dW, dB, ops.WgradWorkspace())
+    torch.cuda.synchronize()
+    r, a = kref.wgrad_ref(x.to(DEV), g, taps)
+    n = Cout * Cin * 49
+    exp, touched = kref.wgrad_scatter(r, n, taps, Cin * 49, 49, Cout, Cin)
+    abs_, _ = kref.wgrad_scatter(a, n, taps, Cin * 49, 49, Cout, Cin)
+    assert bool(touched.all())
+    kref.assert_exact(dW.reshape(-1), exp, torch.float32, abs_, 0.5, "stem wgrad, exact operands")
+    gs = g.double().reshape(-1, Cout)
+    kref.assert_exact(dB, gs.sum(0), torch.float32, gs.abs().sum(0), 0.5, "stem bgrad, exact operands")
 
 
 def _bn_vectors(C, seed):

@@ -97,6 +97,7 @@ def _timed(name):
             return r
         wrapper.__name__ = fn.__name__
         wrapper.__doc__ = fn.__doc__
+        wrapper.__wrapped__ = fn          # inspect.signature() reports the operator's own parameters
         return wrapper
     return deco
 
