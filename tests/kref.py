@@ -1,6 +1,7 @@
 """Float64 restatements of the two MFMA entry points of include/ubresnet_hip.h -- one ubr_conv launch (ops.conv /
-ops.conv_phases) and one weight gradient (ops.wgrad) -- written from the descriptor, not from F.conv2d, plus the checks
-the kernel tests compare with.  A helper module for the tests (imported by name; not a conftest).
+ops.conv_phases) and one weight gradient (ops.wgrad) -- written from the descriptor, not from F.conv2d, of the elementwise
+formulas of its streaming kernels (block tail, BatchNorm backward, max-pool, head and loss), plus the checks the kernel tests
+compare with and the sentinel-guarded replay buffers they share.  A helper module for the tests (imported by name; not a conftest).
 
 Exact operands.  exact_operands() draws sparse small dyadic values m * 2^e, m in {-2,-1,0,1,2}, with whole all-zero
 16x16 tiles as on LArTPC crops.  With per-channel transforms picked from scale in {0.5,1,2}, shift in {-1,0,1} and an
@@ -46,6 +47,19 @@ C_ACC = 1.03
 #     |s2 - sum v^2| <= gamma_{L+1} * sum v^2      (one more rounding: v*v in fp32)
 # The same L bounds the BatchNorm-backward sums (same lane chain, sum g_y and sum g_y*xhat; xhat = d*invstd is one
 # more rounding, covered by the +1).  stats_eps() returns these epsilons.
+
+
+# Reduce passes of the streaming kernels (csrc/ubr_elem.hip: bn_bwd_kernel / tail_bwd_kernel with APPLY = false, channel_sum_kernel).
+# Finding: a thread keeps ONE 16-byte channel unit and adds its pixels' terms (g_y, and g_y*xhat = g_y * fl((c - mean)*invstd)) into
+# fp32 registers, a chain of ceil(npix * CU / (256 * workgroups)) terms -- 8 to 64 at the network's shapes, since pick_blocks() gives
+# a thread 8 pixels and caps the grid at 512 workgroups (channel_sum: one pixel per thread, capped at 1024).  With a power-of-two
+# unit count below 64 (every U-ResNet layer), flush_sums_pow2 then adds the 64/CU lanes of a wave that hold the same unit in
+# log2(64/CU) fp32 butterfly levels; from the per-wave LDS rows on everything is fp64 (four rows added per workgroup, one fp64 atomic
+# per channel into stripe blockIdx % UBR_RED_SLOTS).  With CU >= 64 there is no butterfly, and for other unit counts (C = 80, 96) and
+# in channel_sum the per-thread fp32 partial goes straight into fp64 LDS atomics.  So an fp32 partial is at most
+# L = ceil(npix*CU/(256*workgroups)) + log2(64/CU) roundings deep; a bounded check would use gamma(L + 1) * sum |terms| per channel (the
+# +1: xhat is rounded once).  On exact operands no bound is needed: assert_sums_exact() asserts that the sum of |terms| of a whole
+# channel stays below 2^24 units of the term grid, so every fp32 partial of any grid is exact, and compares for equality.
 
 
 # Log-softmax epilogue (ubr_conv_desc.epilogue = 1; the head's 7x7 conv, thin or generic kernel): over the n = Cout <= 16 exact fp32 logits v of a
@@ -343,6 +357,78 @@ def assert_within(got, ref, lim, what=""):
                                 float(err[tuple(idx)]), float(lim[tuple(idx)])))
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# replay buffers (shared by test_gpu_kernels_exact.py and test_gpu_stream_exact.py)
+# ------------------------------------------------------------------------------------------------------------------
+ESZ = {torch.float32: 4, torch.bfloat16: 2, torch.float16: 2}
+_ITY = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+class TV:
+    """an NHWC tensor view as a recorded call saw it: shape, strides, dtype, storage group and byte address"""
+
+    def __init__(self, t, gid=None):
+        self.shape, self.stride, self.dtype = tuple(t.shape), tuple(t.stride()), t.dtype
+        self.ptr = t.data_ptr()
+        self.gid = gid if gid is not None else t.untyped_storage().data_ptr()
+
+    @classmethod
+    def make(cls, shape, stride, dtype, gid, ptr):
+        t = cls.__new__(cls)
+        t.shape, t.stride, t.dtype, t.gid, t.ptr = tuple(shape), tuple(stride), dtype, gid, ptr
+        return t
+
+    def extent(self):
+        return 1 + sum((n - 1) * s for n, s in zip(self.shape, self.stride))
+
+    def key(self, base):
+        return (self.shape, self.stride, str(self.dtype), self.ptr - base)
+
+
+class Buffers:
+    """one sentinel-filled buffer per storage group, big enough for the group's views, same 256-byte alignment"""
+
+    def __init__(self, views, device="cuda"):
+        self.groups = {}
+        for v in views:
+            g = self.groups.setdefault(v.gid, {"dtype": v.dtype, "lo": v.ptr, "hi": v.ptr})
+            assert g["dtype"] == v.dtype, "views of one storage with different element types"
+            g["lo"] = min(g["lo"], v.ptr)
+            g["hi"] = max(g["hi"], v.ptr + v.extent() * ESZ[v.dtype])
+        for g in self.groups.values():
+            esz = ESZ[g["dtype"]]
+            g["m"] = (256 + g["lo"] % 256) // esz
+            n = g["m"] + (g["hi"] - g["lo"]) // esz + 256 // esz
+            g["buf"] = torch.full((n,), float("nan"), dtype=g["dtype"], device=device)
+            g["written"] = torch.zeros(n, dtype=torch.bool, device=device)
+
+    def _strided(self, what, v):
+        g = self.groups[v.gid]
+        return g[what].as_strided(v.shape, v.stride, g["m"] + (v.ptr - g["lo"]) // ESZ[v.dtype])
+
+    def view(self, v):
+        return self._strided("buf", v)
+
+    def mark_written(self, v):
+        self._strided("written", v).fill_(True)
+
+    def snapshot(self):
+        return {k: g["buf"].clone() for k, g in self.groups.items()}
+
+    def check_sentinel(self, snap, what):
+        for k, g in self.groups.items():
+            assert_untouched(g["buf"], snap[k], g["written"], what)
+
+
+def assert_untouched(buf, before, written, what=""):
+    """every element of `buf` outside the boolean map `written` (None: nothing may change) still holds `before`'s bits"""
+    ity = _ITY[buf.element_size()]
+    bad = buf.reshape(-1).view(ity) != before.reshape(-1).view(ity)
+    if written is not None:
+        bad &= ~written.reshape(-1)
+    assert not bool(bad.any()), "%s: wrote %d elements outside its output view(s)" % (what, int(bad.sum()))
+
+
 def stats_eps(L):
     """(eps1, eps2) of the per-channel statistics bound for an fp32 partial chain of L (see the note at the top)"""
     return gamma(L) + 2.0 ** -50, gamma(L + 1) + 2.0 ** -50
@@ -372,3 +458,211 @@ def assert_stats(s, refs, L, unit=None, unit2=None, what=""):
             raise AssertionError("%s: stats %s of channel %d: got %r, fp64 %r, |err| %.3e > %.2e * %.3e"
                                  % (what, nm, c, float(a[c]), float(b[c]), float(err[c]), e, float(ab[c])))
     return "bounded"
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# streaming kernels (csrc/ubr_elem.hip, csrc/ubr_head.hip): the elementwise formulas of include/ubresnet_hip.h in fp64
+# ------------------------------------------------------------------------------------------------------------------
+def _vec(v, ref):
+    return v.double().to(ref.device)
+
+
+def _bn(c, mean, scale, shift):
+    return (c.double() - _vec(mean, c)) * _vec(scale, c) + _vec(shift, c)
+
+
+def tail_fwd_ref(c2, mean2, scale2, shift2, sc, mean_b=None, scale_b=None, shift_b=None):
+    """out = relu( relu(bn2(c2)) + shortcut ), shortcut = bnpass(sc) (mean_b given) or sc; fp64 NHWC"""
+    r2 = _bn(c2, mean2, scale2, shift2).clamp_min(0)
+    sh = sc.double() if mean_b is None else _bn(sc, mean_b, scale_b, shift_b)
+    return (r2 + sh).clamp_min(0)
+
+
+def mask_pack(positive, cpu):
+    """bool [..., C] -> uint8 [npix * C/cpu]: bit e of byte (pixel, unit) = channel e of the unit (the block tail's ReLU mask)"""
+    C = positive.shape[-1]
+    b = positive.reshape(-1, C // cpu, cpu).to(torch.int32)
+    w = (1 << torch.arange(cpu, device=positive.device, dtype=torch.int32))
+    return (b * w).sum(-1).to(torch.uint8).reshape(-1)
+
+
+def mask_unpack(mask, shape, cpu):
+    """uint8 [>= npix * C/cpu] -> bool of `shape` (NHWC)"""
+    return mask_bits(mask, shape, cpu) > 0
+
+
+def bn_finalize_ref(s1, s2, count, gamma, beta, eps, rmean=None, rvar=None, momentum=0.1):
+    """ubr_bn_finalize's arithmetic in fp64 from the summed statistics: (scale, shift, mean, invstd, running_mean, running_var),
+    every vector rounded to fp32 once as the kernel stores it.  momentum: the factor in fp64 (the kernel widens its fp32 argument;
+    for cumulative averaging the caller passes float32(1 / (batches tracked + 1)))."""
+    s1, s2 = s1.double(), s2.double()
+    m = s1 / count
+    var = (s2 / count - m * m).clamp_min(0)
+    inv = 1.0 / torch.sqrt(var + float(torch.tensor(eps, dtype=torch.float32)))
+    scale = (_vec(gamma, s1) * inv).float()
+    out = [scale, beta.float().to(s1.device), m.float(), inv.float(), None, None]
+    if rmean is not None:
+        unb = var * count / (count - 1.0) if count > 1.0 else var
+        out[4] = ((1.0 - momentum) * _vec(rmean, s1) + momentum * m).float()
+        out[5] = ((1.0 - momentum) * _vec(rvar, s1) + momentum * unb).float()
+    return tuple(out)
+
+
+def bn_bwd_ref(ga, ga2, c, scale, shift, mean, invstd, relu):
+    """-> (g_y, xhat) fp64: g_y = (ga + ga2) * [bn(c) > 0] (relu) and xhat = (c - mean) * invstd"""
+    g = ga.double() if ga2 is None else ga.double() + ga2.double()
+    d = c.double() - _vec(mean, c)
+    if relu:
+        g = torch.where(d * _vec(scale, c) + _vec(shift, c) > 0, g, torch.zeros((), dtype=g.dtype, device=g.device))
+    return g, d * _vec(invstd, c)
+
+
+def tail_bwd_ref(go, go2, positive, c2, scale2, shift2, mean2, invstd2, cb=None, mean_b=None, invstd_b=None):
+    """backward operands of a block tail: positive = [out > 0] (bool NHWC, from `out` or from the mask bits).
+    -> (g_z, g_y2, xhat2, xhat_b): g_z = (go + go2)*positive (gradient into the shortcut branch), g_y2 = g_z*[bn2(c2) > 0]"""
+    g = go.double() if go2 is None else go.double() + go2.double()
+    zero = torch.zeros((), dtype=g.dtype, device=g.device)
+    gz = torch.where(positive, g, zero)
+    d2 = c2.double() - _vec(mean2, c2)
+    gy2 = torch.where(d2 * _vec(scale2, c2) + _vec(shift2, c2) > 0, gz, zero)
+    xhb = None if cb is None else (cb.double() - _vec(mean_b, cb)) * _vec(invstd_b, cb)
+    return gz, gy2, d2 * _vec(invstd2, c2), xhb
+
+
+def reduce_ref(gy, xhat=None):
+    """per-channel sums of a reduce pass and the sums of |terms| (the budget): (sum g_y, sum g_y*xhat, a1, a2), fp64 [C]"""
+    C = gy.shape[-1]
+    g = gy.reshape(-1, C)
+    if xhat is None:
+        return g.sum(0), None, g.abs().sum(0), None
+    t = g * xhat.reshape(-1, C)
+    return g.sum(0), t.sum(0), g.abs().sum(0), t.abs().sum(0)
+
+
+def apply_ref(gy, xhat, scale, k1, k2):
+    """pass 2: g_c = scale * (g_y - k1 - xhat*k2)"""
+    return _vec(scale, gy) * (gy - _vec(k1, gy) - xhat * _vec(k2, gy))
+
+
+def assert_sums_exact(got, ref, absref, unit, what=""):
+    """a striped fp64 sum against its reference: asserts the budget (sum of |terms| of a channel < 2^24 units of the term grid:
+    every fp32 partial of every summation order is then exact, see the note on the reduce passes at the top) and equality"""
+    assert budget_ok(absref, unit), "%s: budget %.6g units >= 2^24: not an exact case" % (what, float(absref.max()) / unit)
+    ref = ref.to(got.device)
+    if not torch.equal(got, ref):
+        c = int((got != ref).nonzero()[0])
+        raise AssertionError("%s: channel %d: got %r, exact %r (%d of %d channels differ)"
+                             % (what, c, float(got[c]), float(ref[c]), int((got != ref).sum()), ref.numel()))
+
+
+def pool_out(n, stride):
+    return (n - 1) // stride + 1
+
+
+def maxpool_ref(x, xf, stride):
+    """nn.MaxPool2d(3, stride, 1) of xform(x): (pooled, argmax, transformed input), fp64 / int64 tap index ky*3+kx of the FIRST
+    maximum in scan order among the taps inside the image (strict > update, as ATen's CPU kernel)"""
+    v = _xform(x, xf)
+    N, H, W, C = v.shape
+    OH, OW = pool_out(H, stride), pool_out(W, stride)
+    vp = torch.nn.functional.pad(v, (0, 0, 1, 1, 1, 1), value=float("-inf"))
+    best = torch.full((N, OH, OW, C), float("-inf"), dtype=torch.float64, device=v.device)
+    am = torch.full((N, OH, OW, C), -1, dtype=torch.int64, device=v.device)
+    for t in range(9):
+        ky, kx = t // 3, t % 3
+        w = vp[:, ky:ky + (OH - 1) * stride + 1:stride, kx:kx + (OW - 1) * stride + 1:stride, :]
+        upd = (w > best) | ((am < 0) & (w > float("-inf")))
+        best = torch.where(upd, w, best)
+        am = torch.where(upd, torch.full_like(am, t), am)
+    return best, am, v
+
+
+def maxpool_bwd_ref(g_pooled, argmax, in_hw, stride, g_extra=None):
+    """gx = g_extra + scatter of g_pooled through the arg-max taps; fp64 [N,H,W,C]"""
+    H, W = in_hw
+    gp = g_pooled.double()
+    N, OH, OW, C = gp.shape
+    acc = torch.zeros((N, H + 2, W + 2, C), dtype=torch.float64, device=gp.device)
+    for t in range(9):
+        ky, kx = t // 3, t % 3
+        acc[:, ky:ky + (OH - 1) * stride + 1:stride, kx:kx + (OW - 1) * stride + 1:stride, :] += \
+            torch.where(argmax.to(gp.device) == t, gp, torch.zeros((), dtype=gp.dtype, device=gp.device))
+    gx = acc[:, 1:H + 1, 1:W + 1, :]
+    return gx + g_extra.double() if g_extra is not None else gx.clone()
+
+
+def stem_expand_ref(x):
+    """NCHW [N,Cin,H,W] -> NHWC [N,H,W,16*Cin]: channel 16*ci+kx = plane ci shifted by kx-3 columns (kx < 7), zero otherwise"""
+    N, Cin, H, W = x.shape
+    out = torch.zeros((N, H, W, 16 * Cin), dtype=torch.float64, device=x.device)
+    xp = torch.nn.functional.pad(x.double(), (3, 3))
+    for ci in range(Cin):
+        for kx in range(7):
+            out[..., 16 * ci + kx] = xp[:, ci, :, kx:kx + W]
+    return out
+
+
+# ubr_logsoftmax_bwd: per pixel, in fp32, s = sum_c g_c (exact on dyadic g), o_c = g_c - expf(lp_c) * s, stored as T.
+# The test hands the kernel lp^ = fl32(log p) of a dyadic probability p and compares with g - p*s in fp64.  With u = 2^-24:
+#   lp^ = log p + e0, |e0| <= u |log p|:  exp(lp^) = p (1 + e0 + ...);   expf within 2 ulp: relative 4u (kref's convention
+#   above);  so e^ = p (1 + d), |d| <= u (|log p| + 4) to first order.   fl(e^ * s): + u |p s|.   fl(g - .): + u |o|.
+#   Hence |o^ - o| <= u (|p s| (|log p| + 5) + |o|), times C_ACC for the second-order terms; a 16-bit T rounds once more:
+#   + u_T (|o| + that).  Channels >= C of the 16 stored are written as exact zeros.
+def logsoftmax_bwd_ref(g, p, dtype):
+    """g, p: fp64 NCHW (gradient w.r.t. log-probabilities; the probabilities) -> (g_logits fp64 NHWC [N,H,W,C], bound)"""
+    s = g.sum(1, keepdim=True)
+    ref = g - p * s
+    lim = C_ACC * U32 * ((p * s).abs() * (p.log().abs() + 5.0) + ref.abs())
+    if dtype != torch.float32:
+        lim = lim + UNIT_ROUNDOFF[dtype] * (ref.abs() + lim)
+    return ref.permute(0, 2, 3, 1), lim.permute(0, 2, 3, 1)
+
+
+def nll_ref(predict, target, pixelweights, classw, ignore_index):
+    """PixelWiseNLLLoss: (sum over pixels of -predict[b,t,h,w]*classw[t]*pixelweights (the caller divides by b*h*w), the sum of
+    |terms|, the number of labels outside [0,C) other than ignore_index, the mask of contributing pixels, the per-pixel weight)"""
+    N, C, H, W = predict.shape
+    ok = (target != ignore_index) & (target >= 0) & (target < C)
+    bad = int(((target != ignore_index) & ~ok).sum())
+    t = target.clamp(0, C - 1)
+    w = pixelweights.double() * (classw.double().to(t.device)[t] if classw is not None else 1.0)
+    terms = torch.where(ok, -predict.double().gather(1, t.unsqueeze(1)).squeeze(1) * w, torch.zeros((), dtype=torch.float64, device=t.device))
+    return terms.sum(), terms.abs().sum(), bad, ok, w
+
+
+def nll_bwd_ref(g_loss, target, pixelweights, classw, ignore_index, C):
+    """g_predict [N,C,H,W] fp32: -(g_loss / (b*h*w)) * pixelweights * classw[t] at channel t of contributing pixels, zero elsewhere.
+    The kernel forms gl = g_loss / float(total) in fp32 (one correctly rounded division; fp64 division rounded to fp32 is the same
+    value) and scales it by the two weights, which the tests pick as powers of two"""
+    N, H, W = target.shape
+    ok = (target != ignore_index) & (target >= 0) & (target < C)
+    gl = (torch.tensor(float(g_loss), dtype=torch.float64) / float(torch.tensor(float(N * H * W), dtype=torch.float32))).float().double()
+    w = pixelweights.double() * (classw.double().to(target.device)[target.clamp(0, C - 1)] if classw is not None else 1.0)
+    val = torch.where(ok, -gl.to(target.device) * w, torch.zeros((), dtype=torch.float64, device=target.device))
+    out = torch.zeros((N, C, H, W), dtype=torch.float64, device=target.device)
+    out.scatter_(1, target.clamp(0, C - 1).unsqueeze(1), val.unsqueeze(1))
+    return out
+
+
+def confusion_ref(logp, target):
+    """cm[true*C + pred] with pred = FIRST arg-max over channels; labels outside [0,C) are not counted"""
+    N, C, H, W = logp.shape
+    best = logp[:, 0]
+    pred = torch.zeros_like(target)
+    for c in range(1, C):
+        upd = logp[:, c] > best
+        best = torch.where(upd, logp[:, c], best)
+        pred = torch.where(upd, torch.full_like(pred, c), pred)
+    ok = (target >= 0) & (target < C)
+    return torch.bincount((target[ok] * C + pred[ok]).reshape(-1), minlength=C * C)
+
+
+def pick_blocks(npix, CU, max_blocks=2048, min_iters=1):
+    """the documented grid rule of the streaming kernels (csrc/ubr_elem.hip): workgroups of 256 threads, a multiple of
+    CU / gcd(256, CU), one thread per `min_iters` units of work, capped -- for the table rows only"""
+    mult = CU // math.gcd(256, CU)
+    want = (npix * CU + 255) // 256
+    if min_iters > 1:
+        want = (want + min_iters - 1) // min_iters
+    want = max(1, min(want, max_blocks))
+    return (want + mult - 1) // mult * mult

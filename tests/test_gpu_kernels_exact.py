@@ -21,6 +21,7 @@ import pytest
 import torch
 
 import kref
+from kref import ESZ, TV, Buffers
 
 pytestmark = pytest.mark.gpu
 
@@ -31,7 +32,6 @@ if torch.cuda.is_available():
 
 DEV = "cuda"
 Q = 0.25               # grid of every product and partial sum: x ints, xform(x) halves, weights / gradients halves
-ESZ = {torch.float32: 4, torch.bfloat16: 2, torch.float16: 2}
 _DT_NAME = {torch.float32: "float", torch.bfloat16: "bf16_t", torch.float16: "f16_t"}
 
 
@@ -39,21 +39,6 @@ if torch.cuda.is_available():
     # the operators' own parameter lists (ops._timed sets __wrapped__), taken before any test wraps them
     _SIGS = {"conv": inspect.signature(ops.conv), "phases": inspect.signature(ops.conv_phases), "wgrad": inspect.signature(ops.wgrad)}
 _VIEWS = {"conv": ("x", "y", "addend"), "phases": ("x", "y0", "y_full", "addend_full"), "wgrad": ("x", "g")}
-
-
-class TV:
-    """an NHWC tensor view as the call saw it: shape, strides, dtype, storage group and byte address"""
-
-    def __init__(self, t, gid=None):
-        self.shape, self.stride, self.dtype = tuple(t.shape), tuple(t.stride()), t.dtype
-        self.ptr = t.data_ptr()
-        self.gid = gid if gid is not None else t.untyped_storage().data_ptr()
-
-    def extent(self):
-        return 1 + sum((n - 1) * s for n, s in zip(self.shape, self.stride))
-
-    def key(self, base):
-        return (self.shape, self.stride, str(self.dtype), self.ptr - base)
 
 
 def wgrad_kernel_name(dt):
@@ -161,43 +146,6 @@ class Capture:
 # ------------------------------------------------------------------------------------------------------------------
 # replay
 # ------------------------------------------------------------------------------------------------------------------
-class Buffers:
-    """one sentinel-filled buffer per storage group, big enough for the group's views, same 256-byte alignment"""
-
-    def __init__(self, views):
-        self.groups = {}
-        for v in views:
-            g = self.groups.setdefault(v.gid, {"dtype": v.dtype, "lo": v.ptr, "hi": v.ptr})
-            assert g["dtype"] == v.dtype, "views of one storage with different element types"
-            g["lo"] = min(g["lo"], v.ptr)
-            g["hi"] = max(g["hi"], v.ptr + v.extent() * ESZ[v.dtype])
-        for g in self.groups.values():
-            esz = ESZ[g["dtype"]]
-            g["m"] = (256 + g["lo"] % 256) // esz
-            n = g["m"] + (g["hi"] - g["lo"]) // esz + 256 // esz
-            g["buf"] = torch.full((n,), float("nan"), dtype=g["dtype"], device=DEV)
-            g["written"] = torch.zeros(n, dtype=torch.bool, device=DEV)
-
-    def view(self, v):
-        g = self.groups[v.gid]
-        return g["buf"].as_strided(v.shape, v.stride, g["m"] + (v.ptr - g["lo"]) // ESZ[v.dtype])
-
-    def mark_written(self, v):
-        g = self.groups[v.gid]
-        g["written"].as_strided(v.shape, v.stride, g["m"] + (v.ptr - g["lo"]) // ESZ[v.dtype]).fill_(True)
-
-    def snapshot(self):
-        return {k: g["buf"].clone() for k, g in self.groups.items()}
-
-    def check_sentinel(self, snap, what):
-        ity = {2: torch.int16, 4: torch.int32}
-        for k, g in self.groups.items():
-            b, s = g["buf"].view(ity[ESZ[g["dtype"]]]), snap[k].view(ity[ESZ[g["dtype"]]])
-            keep = ~g["written"]
-            bad = (b != s) & keep
-            assert not bool(bad.any()), "%s: wrote %d elements outside its output view(s)" % (what, int(bad.sum()))
-
-
 _seed = [1000]
 
 
