@@ -336,7 +336,31 @@ int ubr_block_tail_bwd_apply_fin(int dtype, int64_t npix, int C, const void* go,
                                  void* g_c2, int64_t g_c2_ps, void* g_sc, int64_t g_sc_ps, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * nn.MaxPool2d(3, stride, padding=1)  (models/ub_uresnet.py:44 stride 2; ASPP_ResNet.py:222 stride 1)
+ * Frozen BatchNorm (module in eval mode, running statistics): mean / invstd are constants, so
+ *   g_c = scale * g_y,  dgamma = sum g_y*xhat,  dbeta = sum g_y
+ * and the data gradient waits for no reduction: reduce and apply are ONE pass.  The kernels below read every operand once,
+ * write the data gradient(s) and add the sums into the same striped fp64 buffers as the reduce passes above (UBR_RED_SLOTS
+ * stripes of a zeroed [UBR_STAT_SLOTS][2*C] buffer).  Per element the arithmetic is that of the apply passes with
+ * k1 = k2 = 0.
+ *   ubr_bn_bwd_frozen        : red may be NULL (the conv that produced `ga` already reduced, ubr_conv_desc.bnb_c): pure apply
+ *   ubr_block_tail_bwd_frozen: operands of ubr_block_tail_bwd_apply_fin without `count`; red2 / red_b are written, not read;
+ *                              g_sc may be NULL on an identity block
+ *   ubr_bn_bwd_finalize_frozen: dgamma / dbeta (either may be NULL) from the stripes, off the dependent chain; k1 / k2
+ *                              (both or neither) are zero-filled for the two-pass apply kernels, which then compute the
+ *                              frozen gradient too (block tails whose two sites are in different modes)
+ * ---------------------------------------------------------------------------------------- */
+int ubr_bn_bwd_frozen(int dtype, int64_t npix, int C, const void* ga, int64_t ga_ps, const void* ga2, int64_t ga2_ps,
+                      const void* c, int64_t c_ps, const float* scale, const float* shift, const float* mean,
+                      const float* invstd, int relu, double* red, void* gc, int64_t gc_ps, void* stream);
+int ubr_block_tail_bwd_frozen(int dtype, int64_t npix, int C, const void* go, int64_t go_ps, const void* go2, int64_t go2_ps,
+                              const uint8_t* relu_mask, const void* c2, int64_t c2_ps,
+                              const float* scale2, const float* shift2, const float* mean2, const float* invstd2, double* red2,
+                              const void* cb, int64_t cb_ps, const float* scale_b, const float* mean_b, const float* invstd_b,
+                              double* red_b, void* g_c2, int64_t g_c2_ps, void* g_sc, int64_t g_sc_ps, void* stream);
+int ubr_bn_bwd_finalize_frozen(const double* red, int C, float* dgamma, float* dbeta, float* k1, float* k2, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * nn.MaxPool2d(3, stride, padding=1) (models/ub_uresnet.py:44 stride 2; ASPP_ResNet.py:222 stride 1)
  * forward reads the (optionally transformed) input, writes the pooled map and optionally the
  * transformed input itself (`xcopy`, the skip tensor x0 of models/ub_uresnet.py:96);
  * backward gathers g_pooled through the arg-max (first maximum in scan order, as ATen) and adds

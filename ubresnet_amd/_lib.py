@@ -120,6 +120,7 @@ SYMBOLS = [
     "ubr_block_tail_fwd", "ubr_block_tail_bwd_reduce", "ubr_block_tail_bwd_apply",
     "ubr_block_tail_fwd_masked", "ubr_block_tail_bwd_reduce_masked", "ubr_block_tail_bwd_apply_masked",
     "ubr_bn_bwd_apply_fin", "ubr_block_tail_bwd_apply_fin", "ubr_block_tail_fwd_fin",
+    "ubr_bn_bwd_frozen", "ubr_block_tail_bwd_frozen", "ubr_bn_bwd_finalize_frozen",
     "ubr_maxpool_fwd", "ubr_maxpool_bwd",
     "ubr_logsoftmax_bwd", "ubr_pixelwise_nll_fwd", "ubr_pixelwise_nll_bwd", "ubr_confusion",
     "ubr_channel_sum", "ubr_cast_f64_to_f32", "ubr_zero", "ubr_adam_step", "ubr_sgd_step", "ubr_crop_tiles", "ubr_stitch_tiles", "ubr_last_error", "ubr_version",
@@ -163,6 +164,10 @@ def _declare(lib):
     lib.ubr_bn_bwd_apply_fin.argtypes = [i32, i64, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp, f64, vp, vp, vp, i64, vp]
     lib.ubr_block_tail_bwd_apply_fin.argtypes = [i32, i64, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp,
                                                  vp, i64, vp, vp, vp, vp, vp, vp, f64, vp, i64, vp, i64, vp]
+    lib.ubr_bn_bwd_frozen.argtypes = [i32, i64, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp, vp, i64, vp]
+    lib.ubr_block_tail_bwd_frozen.argtypes = [i32, i64, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp,
+                                              vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp]
+    lib.ubr_bn_bwd_finalize_frozen.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     lib.ubr_block_tail_fwd_fin.argtypes = [i32, i64, i32, vp, i64, C.POINTER(BnFwdFin), vp, i64, C.POINTER(BnFwdFin), f64, vp, i64, vp, vp]
     lib.ubr_block_tail_fwd.argtypes = [i32, i64, i32, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
     lib.ubr_block_tail_fwd_masked.argtypes = [i32, i64, i32, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp]

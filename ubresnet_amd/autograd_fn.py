@@ -34,7 +34,7 @@ class _NetFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, model, eng, dt, compat, *params):
-        out, sv = eng.forward(x, model.training, dt, True)
+        out, sv = eng.forward(x, eng.any_training(), dt, True)
         ctx.eng, ctx.sv, ctx.params, ctx.model, ctx.compat = eng, sv, params, model, compat
         plan = getattr(sv, "plan", None)
         if plan is not None:
@@ -119,5 +119,5 @@ def run_network(model, kind: str, x: torch.Tensor) -> torch.Tensor:
     if need_grad:
         compat = _wrapper_mode(params, x, model)
         return _NetFn.apply(x, model, eng, dt, compat, *params)
-    out, _ = eng.forward(x, model.training, dt, False)
+    out, _ = eng.forward(x, eng.any_training(), dt, False)
     return out

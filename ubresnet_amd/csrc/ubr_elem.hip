@@ -542,6 +542,151 @@ __global__ __launch_bounds__(256) void bn_bwd_kernel(const BnB k) {
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// Frozen BatchNorm sites (eval-mode module: mean / invstd are the running statistics, constants of the pass).  k1 = k2 = 0, so
+// g_c = scale * g_y needs no sum: the reduce pass and the apply pass above become ONE walk over the tensors -- every operand is
+// read once, the data gradient is stored, and sum g_y / sum g_y*xhat (dbeta / dgamma) are accumulated on the side and flushed
+// like a reduce pass's.  Same trips, same grid as the reduce passes (the per-thread fp32 partials cover the same pixels).
+// ------------------------------------------------------------------------------------------
+template <typename T, bool BYP, bool HAS_GO2>
+__global__ __launch_bounds__(256) void tail_bwd_frozen_kernel(const TailB k) {
+  ubr_main_prio();
+  constexpr int CPU = ET<T>::CPU;
+  constexpr int H2 = CPU / 2;
+  constexpr int UNR = 4;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  UnitIdx<T> ix(k.CU);
+  ubr_f2 s2[H2], t2[H2], m2[H2], i2[H2], mb[H2], ib[H2], sb[H2];
+  ldconst2<CPU>(k.s2, ix.c, s2); ldconst2<CPU>(k.t2, ix.c, t2); ldconst2<CPU>(k.m2, ix.c, m2); ldconst2<CPU>(k.i2, ix.c, i2);
+  if (BYP) { ldconst2<CPU>(k.mb, ix.c, mb); ldconst2<CPU>(k.ib, ix.c, ib); ldconst2<CPU>(k.sb, ix.c, sb); }
+  float acc[4][CPU];
+#pragma unroll
+  for (int qn = 0; qn < 4; ++qn)
+#pragma unroll
+    for (int e = 0; e < CPU; ++e) acc[qn][e] = 0.f;
+  UnitTrip<T, UNR> GO(k.go, k.npix, k.go_ps, ix), GO2(k.go2, k.npix, k.go2_ps, ix), C2(k.c2, k.npix, k.c2_ps, ix),
+      CB(k.cb, k.npix, k.cb_ps, ix), GC2(k.g_c2, k.npix, k.g_c2_ps, ix), GSC(k.g_sc, k.npix, k.g_sc_ps, ix);
+  MaskTrip<T, UNR> MK(k.relu_mask, k.npix, k.CU, ix);
+  const bool write_sc = k.g_sc != nullptr;
+
+  for (long p = ix.p; p < k.npix; p += UNR * ix.pstep) {
+    bool ok[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) ok[u] = p + u * ix.pstep < k.npix;
+    ubr_u4 rg[UNR], rg2[HAS_GO2 ? UNR : 1], rc2[UNR], rcb[BYP ? UNR : 1];
+    unsigned rm[UNR];
+    GO.ld(rg, ok);
+    if constexpr (HAS_GO2) GO2.ld(rg2, ok);
+    MK.ld(rm, ok);
+    C2.ld(rc2, ok);
+    if constexpr (BYP) CB.ld(rcb, ok);
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      float g[CPU], c2[CPU], cb[CPU];
+      unpack4<T>(rg[u], g);
+      if constexpr (HAS_GO2) {
+        float g2[CPU];
+        unpack4<T>(rg2[u], g2);
+#pragma unroll
+        for (int e = 0; e < CPU; ++e) g[e] += g2[e];
+      }
+      const unsigned mbits = rm[u];
+      unpack4<T>(rc2[u], c2);
+      if constexpr (BYP) unpack4<T>(rcb[u], cb);
+      float r2[CPU], rs[CPU];
+#pragma unroll
+      for (int h = 0; h < H2; ++h) {
+        // (gz, gy2, xh2, xhb exactly as in tail_bwd_kernel; a pixel beyond the end loaded zeros: it adds nothing)
+        const ubr_f2 d2 = ubr_f2{c2[2 * h], c2[2 * h + 1]} - m2[h];
+        const ubr_f2 bn = __builtin_elementwise_fma(d2, s2[h], t2[h]);
+        const ubr_f2 xh2 = d2 * i2[h];
+        const ubr_f2 gz = {((mbits >> (2 * h)) & 1u) != 0u ? g[2 * h] : 0.f, ((mbits >> (2 * h + 1)) & 1u) != 0u ? g[2 * h + 1] : 0.f};
+        const ubr_f2 gy2 = {bn[0] > 0.f ? gz[0] : 0.f, bn[1] > 0.f ? gz[1] : 0.f};
+        const ubr_f2 a = s2[h] * gy2;
+        r2[2 * h] = a[0]; r2[2 * h + 1] = a[1];
+        const ubr_f2 gx = gy2 * xh2;
+        acc[0][2 * h] += gy2[0]; acc[0][2 * h + 1] += gy2[1];
+        acc[1][2 * h] += gx[0]; acc[1][2 * h + 1] += gx[1];
+        ubr_f2 b = gz;
+        if (BYP) {
+          const ubr_f2 xhb = (ubr_f2{cb[2 * h], cb[2 * h + 1]} - mb[h]) * ib[h];
+          const ubr_f2 gb = gz * xhb;
+          b = sb[h] * gz;
+          acc[2][2 * h] += gz[0]; acc[2][2 * h + 1] += gz[1];
+          acc[3][2 * h] += gb[0]; acc[3][2 * h + 1] += gb[1];
+        }
+        rs[2 * h] = b[0]; rs[2 * h + 1] = b[1];
+      }
+      GC2.st(u, r2, ok[u]);
+      if (write_sc) GSC.st(u, rs, ok[u]);
+    }
+    GO.next(); GO2.next(); C2.next(); CB.next(); MK.next(); GC2.next(); GSC.next();
+  }
+  const size_t so = (size_t)(blockIdx.x % k.nslots) * 2 * k.C;
+  double* outs[4] = {k.red2 + so, k.red2 + so + k.C, BYP ? k.redb + so : nullptr, BYP ? k.redb + so + k.C : nullptr};
+  if (k.flush) flush_sums_pow2<CPU, 4>(acc, ix.c, k.CU, k.C, reinterpret_cast<float*>(smem), outs);
+  else flush_sums<CPU, 4>(acc, ix.c, k.C, reinterpret_cast<double*>(smem), outs);
+}
+
+// a = max(bn(c), 0) (or bn(c)) at a frozen site; RED = false: the sums were formed elsewhere (a conv epilogue), pure apply
+template <typename T, bool HAS_GA2, bool RELU, bool RED>
+__global__ __launch_bounds__(256) void bn_bwd_frozen_kernel(const BnB k) {
+  ubr_main_prio();
+  constexpr int CPU = ET<T>::CPU;
+  constexpr int H2 = CPU / 2;
+  constexpr int UNR = 4;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  UnitIdx<T> ix(k.CU);
+  ubr_f2 sc[H2], sh[H2], mu[H2], is[H2];
+  ldconst2<CPU>(k.scale, ix.c, sc); ldconst2<CPU>(k.shift, ix.c, sh); ldconst2<CPU>(k.mean, ix.c, mu); ldconst2<CPU>(k.invstd, ix.c, is);
+  float acc[2][CPU];
+#pragma unroll
+  for (int e = 0; e < CPU; ++e) { acc[0][e] = 0.f; acc[1][e] = 0.f; }
+  UnitTrip<T, UNR> GA(k.ga, k.npix, k.ga_ps, ix), GA2(k.ga2, k.npix, k.ga2_ps, ix), CC(k.c, k.npix, k.c_ps, ix), GC(k.gc, k.npix, k.gc_ps, ix);
+  for (long p = ix.p; p < k.npix; p += UNR * ix.pstep) {
+    bool ok[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) ok[u] = p + u * ix.pstep < k.npix;
+    ubr_u4 rg[UNR], rg2[HAS_GA2 ? UNR : 1], rc[UNR];
+    GA.ld(rg, ok);
+    if constexpr (HAS_GA2) GA2.ld(rg2, ok);
+    CC.ld(rc, ok);
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      float g[CPU], c[CPU], r[CPU];
+      unpack4<T>(rg[u], g);
+      if constexpr (HAS_GA2) {
+        float g2[CPU];
+        unpack4<T>(rg2[u], g2);
+#pragma unroll
+        for (int e = 0; e < CPU; ++e) g[e] += g2[e];
+      }
+      unpack4<T>(rc[u], c);
+#pragma unroll
+      for (int h = 0; h < H2; ++h) {
+        const ubr_f2 d = ubr_f2{c[2 * h], c[2 * h + 1]} - mu[h];
+        const ubr_f2 bn = __builtin_elementwise_fma(d, sc[h], sh[h]);
+        const ubr_f2 gy = {(!RELU || bn[0] > 0.f) ? g[2 * h] : 0.f, (!RELU || bn[1] > 0.f) ? g[2 * h + 1] : 0.f};
+        const ubr_f2 a = sc[h] * gy;
+        r[2 * h] = a[0]; r[2 * h + 1] = a[1];
+        if (RED) {
+          const ubr_f2 gx = gy * (d * is[h]);
+          acc[0][2 * h] += gy[0]; acc[0][2 * h + 1] += gy[1];
+          acc[1][2 * h] += gx[0]; acc[1][2 * h + 1] += gx[1];
+        }
+      }
+      GC.st(u, r, ok[u]);
+    }
+    GA.next(); GA2.next(); CC.next(); GC.next();
+  }
+  if (RED) {
+    const size_t so = (size_t)(blockIdx.x % k.nslots) * 2 * k.C;
+    double* outs[2] = {k.red + so, k.red + so + k.C};
+    if (k.flush) flush_sums_pow2<CPU, 2>(acc, ix.c, k.CU, k.C, reinterpret_cast<float*>(smem), outs);
+    else flush_sums<CPU, 2>(acc, ix.c, k.C, reinterpret_cast<double*>(smem), outs);
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void channel_sum_kernel(long npix, int C, int CU, const void* g, long g_ps, double* red) {
   constexpr int CPU = ET<T>::CPU;
@@ -618,6 +763,17 @@ __global__ void bn_bwd_finalize_kernel(const double* red, double count, int C, f
   if (dbeta != nullptr) dbeta[c] = accumulate ? dbeta[c] + (float)sg : (float)sg;
   k1[c] = (float)(sg / count);
   k2[c] = (float)(sgx / count);
+}
+// frozen site: dgamma / dbeta from the stripes; k1 = k2 = 0 for callers that go on to a two-pass apply kernel
+__global__ void bn_bwd_finalize_frozen_kernel(const double* red, int C, float* dgamma, float* dbeta, float* k1, float* k2) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  double sg = 0.0, sgx = 0.0;
+#pragma unroll
+  for (int sl = 0; sl < UBR_STAT_SLOTS; ++sl) { sg += red[(size_t)sl * 2 * C + c]; sgx += red[(size_t)sl * 2 * C + C + c]; }
+  if (dgamma != nullptr) dgamma[c] = (float)sgx;
+  if (dbeta != nullptr) dbeta[c] = (float)sg;
+  if (k1 != nullptr) { k1[c] = 0.f; k2[c] = 0.f; }
 }
 __global__ void cast_f64_kernel(const double* src, float* dst, int n, int stride, int slots, double scale, int accumulate) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1201,6 +1357,85 @@ extern "C" int ubr_block_tail_bwd_apply_fin(int dtype, int64_t npix, int C, cons
   return tail_bwd_common(true, dtype, npix, C, go, go_ps, go2, go2_ps, nullptr, 0, c2, c2_ps, scale2, shift2, mean2, invstd2,
                          nullptr, nullptr, cb, cb_ps, scale_b, mean_b, invstd_b, nullptr, nullptr, nullptr, nullptr,
                          g_c2, g_c2_ps, g_sc, g_sc_ps, stream, relu_mask, &fin);
+}
+
+// One-pass backward of frozen sites: the grid and the LDS carve-out of the reduce passes (every workgroup ends with a flush)
+extern "C" int ubr_block_tail_bwd_frozen(int dtype, int64_t npix, int C, const void* go, int64_t go_ps, const void* go2, int64_t go2_ps,
+                                         const uint8_t* relu_mask, const void* c2, int64_t c2_ps,
+                                         const float* scale2, const float* shift2, const float* mean2, const float* invstd2, double* red2,
+                                         const void* cb, int64_t cb_ps, const float* scale_b, const float* mean_b, const float* invstd_b,
+                                         double* red_b, void* g_c2, int64_t g_c2_ps, void* g_sc, int64_t g_sc_ps, void* stream) {
+  const char* who = "ubr_block_tail_bwd_frozen";
+  UBR_TRY(check_nhwc(who, dtype, npix, C, go, go_ps));
+  if (go2) UBR_TRY(check_nhwc(who, dtype, npix, C, go2, go2_ps));
+  UBR_TRY(check_nhwc(who, dtype, npix, C, c2, c2_ps));
+  if (cb) UBR_TRY(check_nhwc(who, dtype, npix, C, cb, cb_ps));
+  UBR_TRY(check_nhwc(who, dtype, npix, C, g_c2, g_c2_ps));
+  if (g_sc != nullptr || cb != nullptr) UBR_TRY(check_nhwc(who, dtype, npix, C, g_sc, g_sc_ps));
+  UBR_CHECK(relu_mask != nullptr && npix * (C / ubr_cpu(dtype)) < (int64_t)1 << 31, "%s: null mask, or mask exceeds 2 GiB", who);
+  UBR_CHECK(scale2 && shift2 && mean2 && invstd2 && red2, "%s: null bn2 constants or reduction buffer", who);
+  if (cb) UBR_CHECK(scale_b && mean_b && invstd_b && red_b, "%s: null bnpass constants or reduction buffer", who);
+  TailB k{};
+  k.npix = npix; k.C = C; k.CU = C / ubr_cpu(dtype);
+  k.go = go; k.go2 = go2; k.c2 = c2; k.cb = cb;
+  k.go_ps = go_ps; k.go2_ps = go2_ps; k.c2_ps = c2_ps; k.cb_ps = cb_ps;
+  k.s2 = scale2; k.t2 = shift2; k.m2 = mean2; k.i2 = invstd2;
+  k.sb = scale_b; k.mb = mean_b; k.ib = invstd_b;
+  k.red2 = red2; k.redb = red_b; k.g_c2 = g_c2; k.g_sc = g_sc; k.g_c2_ps = g_c2_ps; k.g_sc_ps = g_sc_ps;
+  k.relu_mask = relu_mask;
+  k.nslots = UBR_RED_SLOTS;
+  k.flush = red_flush_mode(k.CU, C, 4);
+  int red_iters = 8, red_blocks = 512;
+#ifdef UBR_TUNE
+  if (g_tune_red_iters) red_iters = g_tune_red_iters;
+  if (g_tune_red_blocks) red_blocks = g_tune_red_blocks;
+  if (g_tune_slots) k.nslots = g_tune_slots;
+  if (!g_tune_flush) k.flush = 0;
+#endif
+  const int blocks = pick_blocks(npix, k.CU, red_blocks, red_iters);
+  const size_t lds = (size_t)(k.flush ? 16 : 8) * 4 * C;
+  UBR_CHECK(lds <= 65536, "%s: C = %d needs more than 64 KiB of LDS", who, C);
+  const bool byp = cb != nullptr, g2 = go2 != nullptr;
+  UBR_DT_SWITCH(dtype, UBR_BOOL2(byp, g2, ubr_launch((tail_bwd_frozen_kernel<TT, B0, B1>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, k)));
+  UBR_LAUNCH_CHECK(who);
+  return UBR_OK;
+}
+extern "C" int ubr_bn_bwd_frozen(int dtype, int64_t npix, int C, const void* ga, int64_t ga_ps, const void* ga2, int64_t ga2_ps,
+                                 const void* c, int64_t c_ps, const float* scale, const float* shift, const float* mean,
+                                 const float* invstd, int relu, double* red, void* gc, int64_t gc_ps, void* stream) {
+  const char* who = "ubr_bn_bwd_frozen";
+  UBR_TRY(check_nhwc(who, dtype, npix, C, ga, ga_ps));
+  if (ga2) UBR_TRY(check_nhwc(who, dtype, npix, C, ga2, ga2_ps));
+  UBR_TRY(check_nhwc(who, dtype, npix, C, c, c_ps));
+  UBR_TRY(check_nhwc(who, dtype, npix, C, gc, gc_ps));
+  UBR_CHECK(scale && shift && mean && invstd, "%s: null bn constants", who);
+  BnB k{};
+  k.npix = npix; k.C = C; k.CU = C / ubr_cpu(dtype);
+  k.ga = ga; k.ga2 = ga2; k.c = c; k.ga_ps = ga_ps; k.ga2_ps = ga2_ps; k.c_ps = c_ps;
+  k.scale = scale; k.shift = shift; k.mean = mean; k.invstd = invstd; k.red = red; k.gc = gc; k.gc_ps = gc_ps;
+  k.nslots = UBR_RED_SLOTS;
+  k.flush = red_flush_mode(k.CU, C, 2);
+  int red_iters = 8, red_blocks = 512, app_blocks = 2048;
+#ifdef UBR_TUNE
+  if (g_tune_red_iters) red_iters = g_tune_red_iters;
+  if (g_tune_red_blocks) red_blocks = g_tune_red_blocks;
+  if (g_tune_app_blocks) app_blocks = g_tune_app_blocks;
+  if (g_tune_slots) k.nslots = g_tune_slots;
+  if (!g_tune_flush) k.flush = 0;
+#endif
+  const bool rd = red != nullptr, g2 = ga2 != nullptr, rl = relu != 0;
+  const int blocks = rd ? pick_blocks(npix, k.CU, red_blocks, red_iters) : pick_blocks(npix, k.CU, app_blocks, 4);
+  const size_t lds = rd ? (size_t)(k.flush ? 16 : 8) * 2 * C : 0;
+  UBR_CHECK(lds <= 65536, "%s: C = %d needs more than 64 KiB of LDS", who, C);
+  UBR_DT_SWITCH(dtype, UBR_BOOL3(g2, rl, rd, ubr_launch((bn_bwd_frozen_kernel<TT, B0, B1, B2>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, k)));
+  UBR_LAUNCH_CHECK(who);
+  return UBR_OK;
+}
+extern "C" int ubr_bn_bwd_finalize_frozen(const double* red, int C, float* dgamma, float* dbeta, float* k1, float* k2, void* stream) {
+  UBR_CHECK(red && C > 0 && ((k1 == nullptr) == (k2 == nullptr)), "ubr_bn_bwd_finalize_frozen: bad arguments");
+  ubr_launch(bn_bwd_finalize_frozen_kernel, dim3(ubr_cdiv(C, 128)), dim3(128), 0, (hipStream_t)stream, red, C, dgamma, dbeta, k1, k2);
+  UBR_LAUNCH_CHECK("ubr_bn_bwd_finalize_frozen");
+  return UBR_OK;
 }
 
 extern "C" int ubr_channel_sum(int dtype, int64_t npix, int C, const void* g, int64_t g_ps, double* red, void* stream) {

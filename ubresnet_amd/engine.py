@@ -9,6 +9,9 @@ only OWNS parameters; this executor runs the fused schedule explicitly:
   * train-mode BatchNorm: the producing conv accumulates sum/sum-of-squares in its epilogue,
     a tiny finalize kernel makes (scale, shift), and the CONSUMER applies scale/shift/ReLU
     while loading its operand -- conv -> BN -> ReLU costs one write and one read.
+  * frozen BatchNorm (a module in eval mode with running statistics, decided per module as nn.BatchNorm2d.forward does):
+    the site's vectors come from the running statistics (nothing is accumulated or updated), and its backward is ONE
+    pass, g_c = scale*g_y, with dgamma / dbeta summed on the side (ubr_bn_bwd_frozen, ubr_block_tail_bwd_frozen).
   * backward is scheduled by hand in reverse order; parameter gradients land in one flat fp32
     buffer laid out in completion order so data-parallel all-reduce can start per stage.
 """
@@ -76,11 +79,17 @@ def _phase(t, ry, rx):
 
 class BNSite:
     """Per-BatchNorm2d runtime vectors (views into the per-pass workspaces)."""
-    __slots__ = ("mod", "C", "stats", "scale", "shift", "mean", "invstd", "red", "k1", "k2")
+    __slots__ = ("mod", "C", "stats", "scale", "shift", "mean", "invstd", "red", "k1", "k2", "frozen")
 
     def __init__(self, mod):
         self.mod = mod
         self.C = mod.num_features
+        self.frozen = False      # this pass normalises with the running statistics (set per pass, restored for its backward)
+
+
+def _module_frozen(mod) -> bool:
+    """nn.BatchNorm2d.forward hands training=False to F.batch_norm: module in eval mode and running statistics present"""
+    return not mod.training and mod.running_mean is not None and mod.running_var is not None
 
 
 class Saved:
@@ -124,6 +133,16 @@ class Engine:
     # ------------------------------------------------------------------ helpers
     def bn(self, mod) -> BNSite:
         return self._bn_of[id(mod)]
+
+    def any_training(self) -> bool:
+        """some BatchNorm of the model would use batch statistics now"""
+        return any(not _module_frozen(s.mod) for s in self.bn_sites)
+
+    def frozen_pattern(self, training: bool) -> tuple:
+        """per BatchNorm site: frozen in a pass started now.  training = False freezes every site that has running statistics"""
+        if training:
+            return tuple(_module_frozen(s.mod) for s in self.bn_sites)
+        return tuple(s.mod.running_mean is not None and s.mod.running_var is not None for s in self.bn_sites)
 
     def const(self, device, value: float, n: int) -> torch.Tensor:
         key = (device, value)
@@ -279,27 +298,33 @@ class Engine:
             s.shift = sv.fws[off:off + s.C]; off += s.C
             s.mean = sv.fws[off:off + s.C]; off += s.C
             s.invstd = sv.fws[off:off + s.C]; off += s.C
-        sv.sites = [(s, s.scale, s.shift, s.mean, s.invstd) for s in self.bn_sites]
-        if training:
-            NS = L.STAT_SLOTS
-            nd = sum(2 * s.C for s in self.bn_sites) * NS
+        for s, fz in zip(self.bn_sites, self.frozen_pattern(training)):
+            s.frozen = fz
+        self._snapshot_sites(sv)
+        NS = L.STAT_SLOTS
+        nd = sum(2 * s.C for s in self.bn_sites if not s.frozen) * NS
+        if nd:
+            # (frozen sites accumulate no statistics: their producer convs get stats = None)
             sv.dws = self._new(nd, dtype=torch.float64, device=device)
             ops.zero_(sv.dws)
-            off = 0
-            for s in self.bn_sites:
-                s.stats = sv.dws[off:off + 2 * s.C * NS]; off += 2 * s.C * NS
-        else:
-            for s in self.bn_sites:
+        off = 0
+        for s in self.bn_sites:
+            if s.frozen:
                 s.stats = None
+            else:
+                s.stats = sv.dws[off:off + 2 * s.C * NS]; off += 2 * s.C * NS
+
+    def _snapshot_sites(self, sv: Saved):
+        sv.sites = [(s, s.scale, s.shift, s.mean, s.invstd, s.frozen) for s in self.bn_sites]
 
     def _rebind(self, sv: Saved):
-        """point the BN sites at the vectors of the pass that is being back-propagated"""
-        for s, scale, shift, mean, invstd in sv.sites:
-            s.scale, s.shift, s.mean, s.invstd = scale, shift, mean, invstd
+        """point the BN sites at the vectors (and the mode) of the pass that is being back-propagated"""
+        for s, scale, shift, mean, invstd, frozen in sv.sites:
+            s.scale, s.shift, s.mean, s.invstd, s.frozen = scale, shift, mean, invstd, frozen
 
     def _finish_bn(self, site: BNSite, count: int, training: bool):
         m = site.mod
-        if training:
+        if training and not site.frozen:
             mom = -1.0 if m.momentum is None else m.momentum     # None: cumulative moving average (factor 1 / num_batches_tracked)
             track = m.track_running_stats and m.running_mean is not None
             ops.bn_finalize(site.stats, count, m.weight, m.bias, m.running_mean if track else None,
@@ -325,14 +350,15 @@ class Engine:
         ops.conv(x, self.packed(blk.conv1.weight, dt, "fwd"), c1, T3, Cout, S=S, xf=xf_in, stats=bn1.stats)
         self._finish_bn(bn1, cnt, training)
         c2 = self._new((N, OH, OW, Cout), dtype=dt, device=dev)
-        fuse = _TAIL_FIN and training and 24 * Cout <= 65536
+        bnb = self.bn(blk.bnpass) if blk.bypass is not None else None
+        # (a frozen site has nothing to finalise: a tail with one takes the plain tail kernel and per-site finish launches)
+        fuse = _TAIL_FIN and training and not bn2.frozen and not (bnb is not None and bnb.frozen) and 24 * Cout <= 65536
         slots = L.RED_SLOTS if fuse else 0
         ops.conv(c1, self.packed(blk.conv2.weight, dt, "fwd"), c2, T3, Cout, xf=self.relu_affine(bn1), stats=bn2.stats, stats_slots=slots)
         if not fuse:
             self._finish_bn(bn2, cnt, training)
         cb = None
         if blk.bypass is not None:
-            bnb = self.bn(blk.bnpass)
             cb = self._new((N, OH, OW, Cout), dtype=dt, device=dev)
             ops.conv(x, self.packed(blk.bypass.weight, dt, "fwd"), cb, T1, Cout, S=S, xf=xf_in, stats=bnb.stats, stats_slots=slots)
             if not fuse:
@@ -415,7 +441,21 @@ class Engine:
         if b is not None:
             b.flush()
 
+    def _fin_flush(self):
+        """dgamma / dbeta of the frozen sites back-propagated since the last flush.  Their data gradients did not wait for
+        the sums, so these launches sit at the end of a stage, behind the convs, instead of between a BatchNorm backward
+        and its consumer."""
+        pend = self.__dict__.get("_fin_pending")
+        if pend:
+            for red, site, G in pend:
+                ops.bn_bwd_finalize_frozen(red, site.C, G(site.mod.weight), G(site.mod.bias))
+            del pend[:]
+
+    def _fin_later(self, red, site, G):
+        self.__dict__.setdefault("_fin_pending", []).append((red, site, G))
+
     def _side_end(self, dev):
+        self._fin_flush()
         self._wg_flush()
         if self._side_on:
             torch.cuda.current_stream(dev).wait_stream(self.side)
@@ -452,6 +492,15 @@ class Engine:
     def _bn_bwd(self, site: BNSite, ga, ga2, c, relu, G, cnt, red=None):
         """backward through a = relu(bn(c)) (or bn only): returns g_c; writes dgamma/dbeta.
         red: the reduce pass's sums, when the conv that produced `ga` already accumulated them in its epilogue"""
+        if site.frozen:
+            gc = self._new(c.shape, dtype=c.dtype, device=c.device)
+            if red is None:
+                red = self._red(2 * site.C, c.device)
+                ops.bn_bwd_frozen(ga, ga2, c, site.scale, site.shift, site.mean, site.invstd, relu, red, gc)
+            else:
+                ops.bn_bwd_frozen(ga, ga2, c, site.scale, site.shift, site.mean, site.invstd, relu, None, gc)
+            self._fin_later(red, site, G)
+            return gc
         if red is None:
             red = self._red(2 * site.C, c.device)
             ops.bn_bwd_reduce(ga, ga2, c, site.scale, site.shift, site.mean, site.invstd, relu, red)
@@ -503,21 +552,38 @@ class Engine:
         red2 = red[:2 * Cout * NS]
         redb = red[2 * Cout * NS:] if byp else None
         mask = getattr(rec, "mask", None)
-        ops.block_tail_bwd_reduce(go, go2, out, c2, bn2.scale, bn2.shift, bn2.mean, bn2.invstd,
-                                  cb, bnb.mean if byp else None, bnb.invstd if byp else None, red2, redb, relu_mask=mask)
+        # every site of the tail frozen: one pass (no sum stands between go and the data gradients); sites in different modes,
+        # or no bit mask: the two passes, with k1 = k2 = 0 for the frozen site
+        nfrozen = int(bn2.frozen) + int(byp and bnb.frozen)
+        onepass = mask is not None and nfrozen == (2 if byp else 1)
+        fin = mask is not None and Cout <= _FIN_MAX_C and nfrozen == 0
+        if not onepass:
+            ops.block_tail_bwd_reduce(go, go2, out, c2, bn2.scale, bn2.shift, bn2.mean, bn2.invstd,
+                                      cb, bnb.mean if byp else None, bnb.invstd if byp else None, red2, redb, relu_mask=mask)
         g_c2 = self._new(c2.shape, dtype=dt, device=dev)
         # identity block with one gradient operand: the skip gradient go*[out>0] is not written; conv1's data-gradient epilogue
         # re-forms it from go and the bit mask
-        lazy_sc = _MASK_ADDEND and mask is not None and not byp and go2 is None and need_gx and Cout <= _FIN_MAX_C
+        lazy_sc = _MASK_ADDEND and not byp and go2 is None and need_gx and (fin or onepass)
         g_sc = None if lazy_sc else self._new(c2.shape, dtype=dt, device=dev)
-        if mask is not None and Cout <= _FIN_MAX_C:
+        if onepass:
+            ops.block_tail_bwd_frozen(go, go2, mask, c2, bn2.scale, bn2.shift, bn2.mean, bn2.invstd, red2,
+                                      cb, bnb.scale if byp else None, bnb.mean if byp else None, bnb.invstd if byp else None, redb, g_c2, g_sc)
+            self._fin_later(red2, bn2, G)
+            if byp:
+                self._fin_later(redb, bnb, G)
+        elif fin:
             ops.block_tail_bwd_apply_fin(go, go2, mask, c2, bn2.scale, bn2.shift, bn2.mean, bn2.invstd, red2, G(blk.bn2.weight), G(blk.bn2.bias),
                                          cb, bnb.scale if byp else None, bnb.mean if byp else None, bnb.invstd if byp else None,
                                          redb, G(blk.bnpass.weight) if byp else None, G(blk.bnpass.bias) if byp else None, cnt, g_c2, g_sc)
         else:
             k = self._new(4 * Cout, dtype=torch.float32, device=dev)
-            ops.bn_bwd_finalize(red2, cnt, Cout, G(blk.bn2.weight), G(blk.bn2.bias), False, k[:Cout], k[Cout:2 * Cout])
-            if byp:
+            if bn2.frozen:
+                ops.bn_bwd_finalize_frozen(red2, Cout, G(blk.bn2.weight), G(blk.bn2.bias), k[:Cout], k[Cout:2 * Cout])
+            else:
+                ops.bn_bwd_finalize(red2, cnt, Cout, G(blk.bn2.weight), G(blk.bn2.bias), False, k[:Cout], k[Cout:2 * Cout])
+            if byp and bnb.frozen:
+                ops.bn_bwd_finalize_frozen(redb, Cout, G(blk.bnpass.weight), G(blk.bnpass.bias), k[2 * Cout:3 * Cout], k[3 * Cout:])
+            elif byp:
                 ops.bn_bwd_finalize(redb, cnt, Cout, G(blk.bnpass.weight), G(blk.bnpass.bias), False, k[2 * Cout:3 * Cout], k[3 * Cout:])
             ops.block_tail_bwd_apply(go, go2, out, c2, bn2.scale, bn2.shift, bn2.mean, bn2.invstd, k[:Cout], k[Cout:2 * Cout],
                                      cb, bnb.scale if byp else None, bnb.mean if byp else None, bnb.invstd if byp else None,
@@ -735,6 +801,7 @@ class Engine:
         ids = [id(p) for _, p in self.grad_order]
 
         def stage_done(last_param):
+            self._fin_flush()
             self._wg_flush()         # the stage's weight gradients are final only after their (batched) slab sums
             i = ids.index(id(last_param))
             hi = self.grad_offsets[self.grad_order[i][0]] + (self.grad_order[i][1].numel() + 3) // 4 * 4
@@ -844,9 +911,6 @@ class Engine:
     def aspp_forward(self, x, training, dt, save):
         m = self.model
         self._save = save
-        if save and not training:
-            raise RuntimeError("ubresnet_amd: gradients through eval-mode BatchNorm are not supported; "
-                               "call model.train() or wrap inference in torch.no_grad()")
         x = self._check_input(x, m.conv1.in_channels)
         N, Cin, H, W = x.shape
         dev, ip = x.device, m.inplanes
@@ -873,7 +937,7 @@ class Engine:
         self._bind_site(self.bn(m.ASPP_combine_enc3.ASPP_bn), arena, offs[3] + C3)
         self._bind_site(self.bn(m.ASPP_combine_enc4.ASPP_bn), arena, offs[4] + C4)
         self._bind_site(self.bn(m.ASPP_combine_enc5.ASPP_bn), arena, offs[5])
-        sv.sites = [(s, s.scale, s.shift, s.mean, s.invstd) for s in self.bn_sites]
+        self._snapshot_sites(sv)
 
         bn1 = self.bn(m.bn1)
         c0 = E(N, H, W, ip)
@@ -962,12 +1026,10 @@ class Engine:
 
     # ------------------------------------------------------------------ UResNet
     def uresnet_forward(self, x: torch.Tensor, training: bool, dt: torch.dtype, save: bool):
-        """training: BatchNorm uses batch statistics (and updates running stats); save: keep activations for backward"""
+        """training: BatchNorm modules in train mode use batch statistics (and update their running statistics), modules in eval
+        mode are frozen; training = False freezes every site.  save: keep activations for backward"""
         m = self.model
         self._save = save
-        if save and not training:
-            raise RuntimeError("ubresnet_amd: gradients through eval-mode BatchNorm are not supported; "
-                               "call model.train() or wrap inference in torch.no_grad()")
         L.require_cuda(x, "input")
         if x.dtype != torch.float32:
             raise RuntimeError("ubresnet_amd: input must be float32 NCHW (got %s)" % x.dtype)

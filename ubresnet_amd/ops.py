@@ -572,6 +572,21 @@ def bn_bwd_apply_fin(ga, ga2, c, scale, shift, mean, invstd, relu, red, count, d
             "bn_bwd_apply_fin")
 
 
+@_timed("bn_bwd_frozen")
+def bn_bwd_frozen(ga, ga2, c, scale, shift, mean, invstd, relu, red, gc):
+    """one-pass backward of a frozen site: g_c = scale * g_y, sums for dgamma / dbeta into `red` (None: already reduced)"""
+    L.check(L.lib().ubr_bn_bwd_frozen(L.dtype_id(c.dtype), _npix(c), c.shape[3], ga.data_ptr(), _ps(ga),
+                                      L.ptr(ga2), _ps(ga2) if ga2 is not None else 0, c.data_ptr(), _ps(c),
+                                      scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), 1 if relu else 0,
+                                      L.ptr(red), gc.data_ptr(), _ps(gc), L.stream_ptr()), "bn_bwd_frozen")
+
+
+def bn_bwd_finalize_frozen(red, Cn, dgamma, dbeta, k1=None, k2=None, stream=None):
+    """dgamma / dbeta of a frozen site from the striped sums; k1 / k2 (optional) are zero-filled for a two-pass apply kernel"""
+    L.check(L.lib().ubr_bn_bwd_finalize_frozen(red.data_ptr(), Cn, L.ptr(dgamma), L.ptr(dbeta), L.ptr(k1), L.ptr(k2),
+                                               L.stream_ptr() if stream is None else stream.cuda_stream), "bn_bwd_finalize_frozen")
+
+
 # ------------------------------------------------------------------------------------------
 # BasicBlock tail
 # ------------------------------------------------------------------------------------------
@@ -645,6 +660,17 @@ def block_tail_bwd_apply_fin(go, go2, relu_mask, c2, scale2, shift2, mean2, invs
         red2.data_ptr(), L.ptr(dgamma2), L.ptr(dbeta2),
         L.ptr(cb), _ps(cb) if cb is not None else 0, L.ptr(scale_b), L.ptr(mean_b), L.ptr(invstd_b), L.ptr(red_b), L.ptr(dgamma_b), L.ptr(dbeta_b),
         float(count), g_c2.data_ptr(), _ps(g_c2), L.ptr(g_sc), _ps(g_sc) if g_sc is not None else 0, L.stream_ptr()), "block_tail_bwd_apply_fin")
+
+
+@_timed("block_tail_bwd_frozen")
+def block_tail_bwd_frozen(go, go2, relu_mask, c2, scale2, shift2, mean2, invstd2, red2,
+                          cb, scale_b, mean_b, invstd_b, red_b, g_c2, g_sc):
+    """one-pass backward of a block tail whose BatchNorm sites are all frozen; g_sc may be None on an identity block"""
+    L.check(L.lib().ubr_block_tail_bwd_frozen(
+        L.dtype_id(c2.dtype), _npix(c2), c2.shape[3], go.data_ptr(), _ps(go), L.ptr(go2), _ps(go2) if go2 is not None else 0,
+        relu_mask.data_ptr(), c2.data_ptr(), _ps(c2), scale2.data_ptr(), shift2.data_ptr(), mean2.data_ptr(), invstd2.data_ptr(),
+        red2.data_ptr(), L.ptr(cb), _ps(cb) if cb is not None else 0, L.ptr(scale_b), L.ptr(mean_b), L.ptr(invstd_b), L.ptr(red_b),
+        g_c2.data_ptr(), _ps(g_c2), L.ptr(g_sc), _ps(g_sc) if g_sc is not None else 0, L.stream_ptr()), "block_tail_bwd_frozen")
 
 
 # ------------------------------------------------------------------------------------------

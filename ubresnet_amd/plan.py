@@ -190,7 +190,8 @@ def forward(eng, x, training, dt, save):
     dev = x.device
     if os.environ.get("UBR_WGRAD_STREAM", "1") != "0":
         eng._ensure_side(dev)
-    key = (tuple(x.shape), dt, bool(training), bool(save), dev.index)
+    # (the frozen pattern of the BatchNorm sites, not just the flag: a tape bakes in which launches each site got)
+    key = (tuple(x.shape), dt, bool(training), eng.frozen_pattern(training), bool(save), dev.index)
     sig = _signature(eng.model)
     plan = eng._planned.get(key)
     if plan is not None and plan.sig != sig:
