@@ -167,6 +167,27 @@ typedef struct {
 } ubr_bn_fold_item;
 int ubr_bn_fold_batched(const ubr_bn_fold_item* items_dev, int nitems, void* stream);
 
+/* Inference: the five branches of one ASPP level (models/ASPP_ResNet.py:227-263 in eval mode) in ONE launch.
+ *   y[..., 16b : 16b+16] = relu(conv_b(x) + bias[16b : 16b+16])   b = 0..3: B1 1x1, B2 3x3, B3 3x3 dilation 3, B4 3x3 dilation 5
+ *                                                                  (padding = dilation, stride 1, C -> 16 channels each)
+ *   y[..., 64 : 64+C]    = MaxPool2d(3, 1, 1)(x)                   (padding counts as minus infinity, as ubr_maxpool_fwd)
+ * w is ONE packed image [28][C/CPU][16][CPU]: the images ubr_pack_weights(_batched) writes for the four forward-orientation
+ * weights (M = 16, K = C, natural tap order), back to back: tap 0 = B1, taps 1..9 = B2, 10..18 = B3, 19..27 = B4.  BatchNorm
+ * is folded by the caller (ubr_pack_item.oscale, ubr_bn_fold_item); bias holds the 64 folded biases in concat order.
+ * x is read once (plus a 5-pixel halo per tile); y is a view whose first 64 + C channels are written, nothing else is.
+ * C a multiple of 32 (16 for UBR_F32); x / w / y 16-byte aligned with strides that keep that alignment; one image of x or y
+ * spans less than 2 GiB (32-bit offsets; UBR_EINVAL otherwise).  No statistics, nothing kept for a backward pass. */
+typedef struct {
+  int32_t dtype;
+  int32_t N, H, W, C;        /* extent of x */
+  int32_t pad_;
+  ubr_tensor x;
+  const void* w;
+  const float* bias;
+  ubr_tensor y;
+} ubr_aspp_front_desc;
+int ubr_aspp_front(const ubr_aspp_front_desc* d, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Weight gradient (autograd ConvolutionBackward, weight part) on MFMA with pixels as K.
  *   dW[t][co][ci] = sum_{n,oy,ox} g(n,oy,ox,co) * xform(x)(n, oy*S+iy0+dy[t], ox*S+ix0+dx[t], ci)

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("UBR_LIB", os.path.join(HERE, "libubresnet_hip.so"))  
 
 F32, BF16, F16 = 0, 1, 2
 MAX_TAPS = 64
+MAX_TILES = 64       # UBR_MAX_TILES
 STAT_SLOTS = 32      # UBR_STAT_SLOTS
 RED_SLOTS = 8        # UBR_RED_SLOTS
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
@@ -72,6 +73,19 @@ class ConvDesc(C.Structure):
     ]
 
 
+class AsppFrontDesc(C.Structure):
+    """ubr_aspp_front_desc"""
+    _fields_ = [
+        ("dtype", C.c_int32),
+        ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32),
+        ("pad_", C.c_int32),
+        ("x", Tensor),
+        ("w", C.c_void_p),
+        ("bias", C.c_void_p),
+        ("y", Tensor),
+    ]
+
+
 class BnFwdFin(C.Structure):
     """ubr_bn_fwd_fin"""
     _fields_ = [
@@ -114,7 +128,7 @@ class WgradDesc(C.Structure):
 
 # every symbol include/ubresnet_hip.h declares (tests check that all of them are exported)
 SYMBOLS = [
-    "ubr_conv", "ubr_conv_last_config", "ubr_conv_last_kernel", "ubr_pack_weights", "ubr_pack_weights_batched", "ubr_bn_fold_batched", "ubr_wgrad_plan", "ubr_wgrad", "ubr_wgrad_last_config", "ubr_wgrad_last_pc", "ubr_wgrad_reduce", "ubr_wgrad_reduce_batched",
+    "ubr_conv", "ubr_conv_last_config", "ubr_conv_last_kernel", "ubr_pack_weights", "ubr_pack_weights_batched", "ubr_bn_fold_batched", "ubr_aspp_front", "ubr_wgrad_plan", "ubr_wgrad", "ubr_wgrad_last_config", "ubr_wgrad_last_pc", "ubr_wgrad_reduce", "ubr_wgrad_reduce_batched",
     "ubr_stem_forward", "ubr_stem_wgrad", "ubr_stem_wgrad_workspace", "ubr_stem_expand",
     "ubr_bn_finalize", "ubr_bn_eval_affine", "ubr_bn_bwd_reduce", "ubr_bn_bwd_finalize", "ubr_bn_bwd_apply",
     "ubr_block_tail_fwd", "ubr_block_tail_bwd_reduce", "ubr_block_tail_bwd_apply",
@@ -149,6 +163,7 @@ def _declare(lib):
     lib.ubr_pack_weights.argtypes = [i32, vp, vp, i32, i32, i32, i32, i64, i64, i32, C.POINTER(C.c_int32), vp]
     lib.ubr_pack_weights_batched.argtypes = [i32, vp, i32, vp]
     lib.ubr_bn_fold_batched.argtypes = [vp, i32, vp]
+    lib.ubr_aspp_front.argtypes = [C.POINTER(AsppFrontDesc), vp]
     lib.ubr_wgrad_plan.argtypes = [C.POINTER(WgradDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     lib.ubr_wgrad.argtypes = [C.POINTER(WgradDesc), vp]
     lib.ubr_wgrad_reduce.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, i64, i64, C.POINTER(C.c_int32), i32, vp]

@@ -25,11 +25,18 @@ from . import _lib as L
 
 
 def load_model(checkpointfile: Optional[str], device, num_classes: int = 4, inplanes: int = 16, input_channels: int = 1,
-               map_location=None, state_dict=None):
-    """UResNet for deployment (deploy/ubresnet_funcs.py:41-68).  `checkpointfile` is the reference's
-    ``{iter, epoch, state_dict, best_prec1, optimizer}`` tar; tensors only are read (weights_only)."""
-    from .models.ub_uresnet import UResNet
-    model = UResNet(inplanes=inplanes, input_channels=input_channels, num_classes=num_classes, showsizes=False)
+               map_location=None, state_dict=None, arch: str = "uresnet"):
+    """UResNet (arch="uresnet") or ASPP_ResNet (arch="aspp") for deployment (deploy/ubresnet_funcs.py:41-68).
+    `checkpointfile` is the reference's ``{iter, epoch, state_dict, best_prec1, optimizer}`` tar; tensors only are
+    read (weights_only)."""
+    if arch == "uresnet":
+        from .models.ub_uresnet import UResNet
+        model = UResNet(inplanes=inplanes, input_channels=input_channels, num_classes=num_classes, showsizes=False)
+    elif arch == "aspp":
+        from .models.ASPP_ResNet import ASPP_ResNet
+        model = ASPP_ResNet(num_classes, in_channels=input_channels, inplanes=inplanes, showsizes=False)
+    else:
+        raise ValueError("load_model: arch must be 'uresnet' or 'aspp' (got %r)" % (arch,))
     if state_dict is None and checkpointfile is not None:
         ckpt = torch.load(checkpointfile, map_location=map_location or "cpu", weights_only=True)
         state_dict = ckpt["state_dict"] if isinstance(ckpt, dict) and "state_dict" in ckpt else ckpt
@@ -75,6 +82,27 @@ def regular_tiling(rows: int, cols: int, th: int = 512, tw: int = 832) -> Tuple[
     return origins(rows, th), origins(cols, tw)
 
 
+def view_tiles(rows: int, cols: int, planes: int, th: int, tw: int, stacked: bool):
+    """tile descriptors {plane, row0, col0, keep_r0, keep_r1, keep_c0, keep_c1} (ubr_crop_tiles / ubr_stitch_tiles) of the
+    regular tiling.  Per plane: one descriptor per (plane, row origin, column origin).  Stacked (a model that takes the planes
+    as channels): one descriptor per (row origin, column origin) with plane 0 -- stacked_crop_desc() expands it for the crop,
+    the stitch takes it as it is with P = 1."""
+    ro, co = regular_tiling(rows, cols, th, tw)
+    rk, ck = _keep_windows(ro, th, rows), _keep_windows(co, tw, cols)
+    tiles = []
+    for p in range(1 if stacked else planes):
+        for (r0, (rl, rh)) in zip(ro, rk):
+            for (c0, (cl, ch)) in zip(co, ck):
+                tiles.append((p, r0, c0, rl - r0, rh - r0, cl - c0, ch - c0))
+    return tiles
+
+
+def stacked_crop_desc(tiles, planes: int):
+    """a stacked tile is `planes` consecutive single-plane crops at the same origin: the crop kernel then writes
+    [len(tiles), planes, th, tw]"""
+    return [(p,) + tuple(t[1:]) for t in tiles for p in range(planes)]
+
+
 def _keep_windows(origins: Sequence[int], t: int, n: int):
     """split the overlaps in the middle: tile i keeps [lo_i, hi_i) in view coordinates"""
     out = []
@@ -91,6 +119,10 @@ class WholeViewSegmenter:
         seg = WholeViewSegmenter(model, rows=1008, cols=3456, planes=3, tile=(512, 832), batch=10,
                                  dtype=torch.float16)
         scores = seg(view)          # view [planes,1,rows,cols] float32 on the GPU -> [planes,C,rows,cols]
+
+    A model whose first conv takes one channel (UResNet, deploy/run_ubresnet_wholeview.py) sees every plane's tiles on their
+    own.  A model that takes `planes` channels (ASPP_ResNet, the three planes stacked as channels) sees one stacked tile per
+    position, and the result is one class-score map per event, [C,rows,cols].
     """
 
     def __init__(self, model, rows: int, cols: int, planes: int = 3, tile=(512, 832), batch: int = 10,
@@ -100,15 +132,15 @@ class WholeViewSegmenter:
         if self.th % 32 or self.tw % 32:
             raise ValueError("tile size must be a multiple of 32")
         self.batch, self.dtype, self.use_graph = batch, dtype, use_graph
-        ro, co = regular_tiling(rows, cols, self.th, self.tw)
-        rk, ck = _keep_windows(ro, self.th, rows), _keep_windows(co, self.tw, cols)
-        self.tiles = []          # (plane, r0, c0, kr0, kr1, kc0, kc1)
-        for p in range(planes):
-            for (r0, (rl, rh)) in zip(ro, rk):
-                for (c0, (cl, ch)) in zip(co, ck):
-                    self.tiles.append((p, r0, c0, rl - r0, rh - r0, cl - c0, ch - c0))
-        if batch > L.MAX_TAPS:
-            raise ValueError("batch must be <= 64 tiles")
+        cin = model.conv1.in_channels
+        if cin != 1 and cin != planes:
+            raise ValueError("WholeViewSegmenter: the model takes %d channels; 1 (per-plane tiles) or planes = %d (stacked tiles) "
+                             "are supported" % (cin, planes))
+        self.stacked = cin > 1
+        self.cin = cin
+        self.tiles = view_tiles(rows, cols, planes, self.th, self.tw, self.stacked)     # (plane, r0, c0, kr0, kr1, kc0, kc1)
+        if batch * cin > L.MAX_TILES:
+            raise ValueError("batch * planes must be <= %d tile descriptors (UBR_MAX_TILES)" % L.MAX_TILES)
         self.nclass = model.conv11.out_channels
         self._graph = None
         self._static_in = None
@@ -144,7 +176,7 @@ class WholeViewSegmenter:
         if self._static_in is not None:
             return
         self._captured_sig = sig
-        self._static_in = torch.zeros((self.batch, 1, self.th, self.tw), dtype=torch.float32, device=device)
+        self._static_in = torch.zeros((self.batch, self.cin, self.th, self.tw), dtype=torch.float32, device=device)
         self.model.eval()
         with torch.no_grad():
             self._forward_batch(self._static_in)            # warm-up: packs weights, raises LDS limits, fills allocator
@@ -163,14 +195,16 @@ class WholeViewSegmenter:
                                % (self.planes, self.rows, self.cols, view.dtype, tuple(view.shape)))
         view = view.contiguous()
         self._ensure_graph(view.device)
-        out = torch.empty((self.planes, self.nclass, self.rows, self.cols), dtype=torch.float32, device=view.device)
+        oplanes = 1 if self.stacked else self.planes
+        out = torch.empty((oplanes, self.nclass, self.rows, self.cols), dtype=torch.float32, device=view.device)
         lib = L.lib()
         for i in range(0, len(self.tiles), self.batch):
             chunk = self.tiles[i:i + self.batch]
             n = len(chunk)
             desc = self._desc(chunk)
+            cdesc = self._desc(stacked_crop_desc(chunk, self.planes)) if self.stacked else desc
             st = L.stream_ptr()
-            L.check(lib.ubr_crop_tiles(view.data_ptr(), self.planes, self.rows, self.cols, desc, n, self.th, self.tw,
+            L.check(lib.ubr_crop_tiles(view.data_ptr(), self.planes, self.rows, self.cols, cdesc, n * self.cin, self.th, self.tw,
                                        self._static_in.data_ptr(), st), "crop_tiles")
             if self._graph is not None:
                 self._graph.replay()
@@ -178,5 +212,5 @@ class WholeViewSegmenter:
             else:
                 scores = self._forward_batch(self._static_in)
             L.check(lib.ubr_stitch_tiles(scores.data_ptr(), self.nclass, self.th, self.tw, desc, n, out.data_ptr(),
-                                         self.planes, self.rows, self.cols, L.stream_ptr()), "stitch_tiles")
-        return out
+                                         oplanes, self.rows, self.cols, L.stream_ptr()), "stitch_tiles")
+        return out[0] if self.stacked else out

@@ -1168,7 +1168,7 @@ class Engine:
         self._red_buf = None
         return flat, views
 
-    # ------------------------------------------------------------------ inference schedule (UResNet, eval mode)
+    # ------------------------------------------------------------------ inference schedule (UResNet and ASPP_ResNet, eval mode)
     # SURVEY.md section 8d, k = 1: eval-mode BatchNorm is a fixed per-channel affine, so it is folded into the packed
     # weights (scale) and the conv bias; ReLU and the residual add run in the conv epilogue (ubr_conv_desc.act).  Every
     # tensor is written once, activated, and read by its consumers with no transform; block tails, BatchNorm finalize
@@ -1189,12 +1189,23 @@ class Engine:
                 pairs += [(mod.conv1, mod.bn1), (mod.conv2, mod.bn2)]
                 if mod.bypass is not None:
                     pairs.append((mod.bypass, mod.bnpass))
+        # ASPP levels: the four branch pairs of a level stay adjacent, so their folded biases are the 64 contiguous floats
+        # ubr_aspp_front reads, and their weights are packed into the one 28-tap image it reads
+        levels = [mod for mod in m.modules() if hasattr(mod, "branches") and hasattr(mod, "B5_gp")]
+        first_branch = {}
+        for lay in levels:
+            first_branch[id(lay.B1_bn)] = lay
+            pairs += [(conv, bn) for conv, bn, _, _ in lay.branches()]
+        pairs += [(mod.ASPP_conv, mod.ASPP_bn) for mod in m.modules() if hasattr(mod, "ASPP_conv")]
         total = sum(bn.num_features for _, bn in pairs)
         vec = self._new(2 * total, dtype=torch.float32, device=device)
         scale_of, bias_of, fold_tbl, off = {}, {}, b"", 0
+        front_bias, front_img, branch_dst = {}, {}, {}
         for conv, bn in pairs:
             Cn = bn.num_features
             sc, bi = vec[off:off + Cn], vec[total + off:total + off + Cn]
+            if id(bn) in first_branch:
+                front_bias[id(first_branch[id(bn)])] = vec[total + off:total + off + 64]
             off += Cn
             scale_of[id(conv.weight)], bias_of[id(bn)] = sc, bi
             for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
@@ -1202,6 +1213,16 @@ class Engine:
                     raise RuntimeError("ubresnet_amd: inference needs affine BatchNorm2d with float32 running statistics on %s" % device)
             fold_tbl += struct.pack("<QQQQQQQif", bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
                                     conv.bias.data_ptr() if conv.bias is not None else 0, sc.data_ptr(), bi.data_ptr(), Cn, float(bn.eps))
+        for lay in levels:
+            Cn = lay.B1_conv.in_channels
+            if Cn % cpu or any(conv.out_channels != 16 for conv, _, _, _ in lay.branches()):
+                raise RuntimeError("ubresnet_amd: ASPP level with %d input channels cannot be packed for %s" % (Cn, dt))
+            front = self._new((ops.ASPP_FRONT_TAPS, Cn // cpu, 16, cpu), dtype=dt, device=device)
+            front_img[id(lay)] = front
+            t0 = 0
+            for conv, _, kk, _ in lay.branches():
+                branch_dst[id(conv.weight)] = front[t0:t0 + kk * kk]
+                t0 += kk * kk
         images, pack_tbl, n = {}, b"", 0
         for group, k, w, soff, M, Kv, Kpad, sm, sk, ntaps, tstride in self._plan_items():
             if group != "fwd":
@@ -1210,7 +1231,11 @@ class Engine:
                 raise RuntimeError("ubresnet_amd: parameters must be contiguous float32 on %s" % device)
             Mpad = (M + 15) // 16 * 16
             Kp = Kpad if Kpad is not None else (Kv + cpu - 1) // cpu * cpu
-            dst = self._new((ntaps, Kp // cpu, Mpad, cpu), dtype=dt, device=device)
+            dst = branch_dst.get(id(w))
+            if dst is None:
+                dst = self._new((ntaps, Kp // cpu, Mpad, cpu), dtype=dt, device=device)
+            elif tuple(dst.shape) != (ntaps, Kp // cpu, Mpad, cpu):
+                raise RuntimeError("ubresnet_amd: ASPP branch image %s does not fit its slot %s" % ((ntaps, Kp // cpu, Mpad, cpu), tuple(dst.shape)))
             images[k] = dst
             sc = scale_of.get(id(w))
             pack_tbl += struct.pack("<QQqqqQiiiiii", w.data_ptr() + 4 * soff, dst.data_ptr(), sm, sk, tstride,
@@ -1218,7 +1243,7 @@ class Engine:
             n += 1
         dev_tbl = lambda b: torch.frombuffer(bytearray(b), dtype=torch.uint8).to(device)
         plan = {"ptrs": ptrs, "images": images, "bias": bias_of, "vec": vec, "fold": dev_tbl(fold_tbl), "nfold": len(pairs),
-                "pack": dev_tbl(pack_tbl), "npack": n}
+                "pack": dev_tbl(pack_tbl), "npack": n, "front_img": front_img, "front_bias": front_bias}
         self._plans[key] = plan
         return plan
 
@@ -1250,30 +1275,96 @@ class Engine:
                     ops.conv(x, wp, _phase(up, ry, rx), ops.transposed_phase_taps(4, 1, 1, 2, ry, rx), Cd)
         self._double_infer(dl.res, cat, out, img, fb, dt)
 
-    def uresnet_infer(self, x, dt):
-        """eval-mode UResNet.forward (models/ub_uresnet.py:88-147), nothing saved"""
-        m = self.model
-        x = self._check_input(x, m.conv1.in_channels)
-        N, Cin, H, W = x.shape
-        dev, ip = x.device, m.inplanes
+    def _infer_begin(self, dt, dev):
+        """fold every BatchNorm and repack every forward image for this pass (two launches) -> the inference plan"""
         plan = self._infer_plan(dt, dev)
         st = L.stream_ptr()
         L.check(L.lib().ubr_bn_fold_batched(plan["fold"].data_ptr(), plan["nfold"], st), "bn_fold_batched")
         L.check(L.lib().ubr_pack_weights_batched(L.dtype_id(dt), plan["pack"].data_ptr(), plan["npack"], st), "pack_weights_batched")
-        img, fb = plan["images"], plan["bias"]
-        E = lambda *shape: self._new(shape, dtype=dt, device=dev)
-        # stem: conv1 (+bn1 folded, ReLU in the epilogue) writes x0 straight into dec1's concat buffer; pool reads it
-        cat1 = E(N, H, W, 2 * ip)
+        return plan
+
+    def _stem_infer(self, m, x, cat1, p0, img, fb, dt):
+        """conv1 (+bn1 folded, ReLU in the epilogue) writes x0 straight into dec1's concat buffer; the pool reads it"""
+        N, Cin, H, W = x.shape
+        ip = m.inplanes
         x0 = cat1[..., ip:]
-        x16 = E(N, H, W, 16 * Cin)
+        x16 = self._new((N, H, W, 16 * Cin), dtype=dt, device=x.device)
         self._untaped(lambda: ops.stem_expand(x, x16))
         if self._rec is not None:
             self._rec.pre = lambda xx: ops.stem_expand(xx, x16)
         for ci in range(Cin):
             ops.conv(x16[..., 16 * ci:16 * ci + 16], img[(id(m.conv1.weight), "stem%d" % ci)], x0, self.STEM_TAPS, ip,
                      bias=fb[id(m.bn1)] if ci == 0 else None, addend=x0 if ci > 0 else None, act=2 if ci == Cin - 1 else 0)
-        p0 = E(N, H // 2, W // 2, ip)
         ops.maxpool_fwd(x0, None, p0, None, 2)
+
+    def _head_infer(self, m, d1o, img, fb, dt):
+        N, H, W, _ = d1o.shape
+        nk = m.conv10.out_channels
+        c10 = self._new((N, H, W, nk), dtype=dt, device=d1o.device)
+        ops.conv(d1o, img[(id(m.conv10.weight), "fwd")], c10, T7, nk, bias=fb[id(m.bn10)], act=1)
+        ncls = m.conv11.out_channels
+        return self._final_logsoftmax(m, c10, img[(id(m.conv11.weight), "fwd")], None, (N, ncls, H, W))
+
+    def _aspp_level_infer(self, layer, post, e, cpost, plan, dt):
+        """ASPP.forward + ASPP_post.forward (models/ASPP_ResNet.py:227-263,280-286), BatchNorms folded: the five branches in
+        one launch, then the 1x1 back to C channels straight into its slice of the decoder's concat buffer"""
+        N, h, w, Cn = e.shape
+        acat = self._new((N, h, w, 64 + Cn), dtype=dt, device=e.device)
+        ops.aspp_front(e, plan["front_img"][id(layer)], plan["front_bias"][id(layer)], acat)
+        ops.conv(acat, plan["images"][(id(post.ASPP_conv.weight), "fwd")], cpost, T1, Cn, bias=plan["bias"][id(post.ASPP_bn)], act=1)
+
+    def aspp_infer(self, x, dt):
+        """eval-mode ASPP_ResNet.forward (models/ASPP_ResNet.py:416-523), nothing saved; buffer layout of aspp_forward"""
+        m = self.model
+        x = self._check_input(x, m.conv1.in_channels)
+        N, Cin, H, W = x.shape
+        dev, ip = x.device, m.inplanes
+        plan = self._infer_begin(dt, dev)
+        img, fb = plan["images"], plan["bias"]
+        E = lambda *shape: self._new(shape, dtype=dt, device=dev)
+        C3, C4, C5 = 8 * ip, 16 * ip, 32 * ip
+        cat1 = E(N, H, W, 2 * ip)
+        p0 = E(N, H // 2, W // 2, ip)
+        self._stem_infer(m, x, cat1, p0, img, fb, dt)
+        cat2 = E(N, H // 2, W // 2, 4 * ip)
+        cat3 = E(N, H // 4, W // 4, 8 * ip)
+        cat4 = E(N, H // 8, W // 8, 3 * C3)           # [deconv | ASPP_post(e3) | e3]
+        cat5 = E(N, H // 16, W // 16, 3 * C4)         # [deconv | ASPP_post(e4) | e4]
+        skip5 = E(N, H // 32, W // 32, 2 * C5)        # [ASPP_post(e5) | e5]
+        e1, e2 = cat2[..., 2 * ip:], cat3[..., 4 * ip:]
+        e3, e4, e5 = cat4[..., 2 * C3:], cat5[..., 2 * C4:], skip5[..., C5:]
+        self._double_infer(m.enc_layer1, p0, e1, img, fb, dt)
+        self._double_infer(m.enc_layer2, e1, e2, img, fb, dt)
+        self._double_infer(m.enc_layer3, e2, e3, img, fb, dt)
+        self._double_infer(m.enc_layer4, e3, e4, img, fb, dt)
+        self._double_infer(m.enc_layer5, e4, e5, img, fb, dt)
+        self._aspp_level_infer(m.ASPP_layer_enc3, m.ASPP_combine_enc3, e3, cat4[..., C3:2 * C3], plan, dt)
+        self._aspp_level_infer(m.ASPP_layer_enc4, m.ASPP_combine_enc4, e4, cat5[..., C4:2 * C4], plan, dt)
+        self._aspp_level_infer(m.ASPP_layer_enc5, m.ASPP_combine_enc5, e5, skip5[..., :C5], plan, dt)
+        d5o = E(N, H // 16, W // 16, 32 * ip)
+        self._declayer_infer(m.dec_layer5, skip5, cat5, C4, d5o, img, fb, dt)
+        d4o = E(N, H // 8, W // 8, 16 * ip)
+        self._declayer_infer(m.dec_layer4, d5o, cat4, C3, d4o, img, fb, dt)
+        d3o = E(N, H // 4, W // 4, 4 * ip)
+        self._declayer_infer(m.dec_layer3, d4o, cat3, 4 * ip, d3o, img, fb, dt)
+        d2o = E(N, H // 2, W // 2, 2 * ip)
+        self._declayer_infer(m.dec_layer2, d3o, cat2, 2 * ip, d2o, img, fb, dt)
+        d1o = E(N, H, W, ip)
+        self._declayer_infer(m.dec_layer1, d2o, cat1, ip, d1o, img, fb, dt)
+        return self._head_infer(m, d1o, img, fb, dt)
+
+    def uresnet_infer(self, x, dt):
+        """eval-mode UResNet.forward (models/ub_uresnet.py:88-147), nothing saved"""
+        m = self.model
+        x = self._check_input(x, m.conv1.in_channels)
+        N, Cin, H, W = x.shape
+        dev, ip = x.device, m.inplanes
+        plan = self._infer_begin(dt, dev)
+        img, fb = plan["images"], plan["bias"]
+        E = lambda *shape: self._new(shape, dtype=dt, device=dev)
+        cat1 = E(N, H, W, 2 * ip)
+        p0 = E(N, H // 2, W // 2, ip)
+        self._stem_infer(m, x, cat1, p0, img, fb, dt)
         cat2 = E(N, H // 2, W // 2, 4 * ip)
         cat3 = E(N, H // 4, W // 4, 8 * ip)
         cat4 = E(N, H // 8, W // 8, 16 * ip)
@@ -1295,11 +1386,7 @@ class Engine:
         self._declayer_infer(m.dec_layer2, d3o, cat2, 2 * ip, d2o, img, fb, dt)
         d1o = E(N, H, W, ip)
         self._declayer_infer(m.dec_layer1, d2o, cat1, ip, d1o, img, fb, dt)
-        nk = m.conv10.out_channels
-        c10 = E(N, H, W, nk)
-        ops.conv(d1o, img[(id(m.conv10.weight), "fwd")], c10, T7, nk, bias=fb[id(m.bn10)], act=1)
-        ncls = m.conv11.out_channels
-        return self._final_logsoftmax(m, c10, img[(id(m.conv11.weight), "fwd")], None, (N, ncls, H, W))
+        return self._head_infer(m, d1o, img, fb, dt)
 
     # ------------------------------------------------------------------ dispatch
     def forward(self, x, training, dt, save):
@@ -1316,6 +1403,8 @@ class Engine:
                 return self.uresnet_infer(x, dt), None
             return self.uresnet_forward(x, training, dt, save)
         if self.kind == "aspp":
+            if not training and not save and _INFER_FOLD:
+                return self.aspp_infer(x, dt), None
             return self.aspp_forward(x, training, dt, save)
         raise RuntimeError("ubresnet_amd: unknown network kind %r" % self.kind)
 

@@ -687,6 +687,28 @@ def maxpool_fwd(x, xf, pooled, xcopy, stride, argmax=None):
                                     L.ptr(argmax), L.stream_ptr()), "maxpool_fwd")
 
 
+ASPP_FRONT_TAPS = 28     # B1 (1) + B2, B3, B4 (9 each) in the packed image of ubr_aspp_front
+
+
+@_timed("aspp_front")
+def aspp_front(e: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, acat: torch.Tensor):
+    """One ubr_aspp_front launch (inference): e NHWC [N,h,w,C]; wp the 28-tap packed image [28][C/CPU][16][CPU] of the four
+    branch convs with BatchNorm folded in; bias the 64 folded biases; acat an NHWC view whose channels [0,64) receive
+    relu(conv_b(e) + bias_b) and [64,64+C) MaxPool2d(3,1,1)(e).  A wider view keeps its other channels."""
+    N, H, W, Cn = e.shape
+    if tuple(wp.shape) != (ASPP_FRONT_TAPS, Cn // L.chans_per_unit(e.dtype), 16, L.chans_per_unit(e.dtype)) or wp.dtype != e.dtype or not wp.is_contiguous():
+        raise RuntimeError("aspp_front: packed weights %s %s do not match %d input channels of %s" % (tuple(wp.shape), wp.dtype, Cn, e.dtype))
+    if acat.dtype != e.dtype or tuple(acat.shape[:3]) != (N, H, W) or acat.shape[3] < 64 + Cn:
+        raise RuntimeError("aspp_front: output view %s %s does not hold [%d,%d,%d,>=%d] %s" % (tuple(acat.shape), acat.dtype, N, H, W, 64 + Cn, e.dtype))
+    if bias.dtype != torch.float32 or bias.numel() < 64 or not bias.is_contiguous():
+        raise RuntimeError("aspp_front: bias must be 64 contiguous float32 values")
+    d = L.AsppFrontDesc()
+    d.dtype = L.dtype_id(e.dtype)
+    d.N, d.H, d.W, d.C = N, H, W, Cn
+    d.x, d.w, d.bias, d.y = _tv(e), wp.data_ptr(), bias.data_ptr(), _tv(acat)
+    L.check(L.lib().ubr_aspp_front(C.byref(d), L.stream_ptr()), "aspp_front")
+
+
 @_timed("maxpool_bwd")
 def maxpool_bwd(x, xf, g_pooled, g_extra, gx, stride, argmax=None):
     N, H, W, Cn = x.shape

@@ -120,6 +120,20 @@ class Recording:
         self.labels[idx] = meta
         self.tape.set_label(-1)
 
+    def operator_names(self):
+        """name of every labelled operator call of the pass, in issue order (None: a call that recorded nothing)"""
+        return [None if meta is None else meta[0] for meta in self.labels]
+
+    def launches_per_operator(self, streams):
+        """[launches on the tape] per labelled operator call, index = position in operator_names().  Replays the tape once
+        (the tape's nodes carry the labels; ubr_tape_replay_timed is the C ABI's way to read them back)."""
+        _, labs = self.tape.replay_timed(streams)
+        out = [0] * len(self.labels)
+        for l in labs:
+            if l >= 0:
+                out[l] += 1
+        return out
+
     def replay(self, streams):
         """ordinary replay, or -- while `TIMED` collects -- a replay with timing events around every launch"""
         if TIMED is None:
@@ -239,6 +253,15 @@ def forward(eng, x, training, dt, save):
         plan.live = None
         sv.plan = plan
     return out, sv
+
+
+def recorded_forward(eng, x, dt):
+    """the Recording of the engine's no-grad forward plan for this input shape and dtype (None: not recorded), and the
+    streams to replay it on -- for tests and probes that count launches"""
+    for key, p in eng._planned.items():
+        if key[0] == tuple(x.shape) and key[1] == dt and not key[4] and p.fwd is not None:
+            return p.fwd, _streams(eng, x.device)[:p.fwd.nstreams]
+    return None, None
 
 
 def backward(eng, sv, g_out, grad_ready, allow_plan=True):
