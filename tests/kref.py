@@ -491,20 +491,44 @@ def mask_unpack(mask, shape, cpu):
     return mask_bits(mask, shape, cpu) > 0
 
 
-def bn_finalize_ref(s1, s2, count, gamma, beta, eps, rmean=None, rvar=None, momentum=0.1):
+def fma64(a, b, c):
+    """round(a*b + c) of fp64 tensors with ONE rounding, as v_fma_f64 does: the product's rounding error exactly (Veltkamp split,
+    Dekker), the sum by TwoSum; the last addition can double-round only on a tie at the 2^-106 level"""
+    def split(x):
+        t = x * 134217729.0
+        h = t - (t - x)
+        return h, x - h
+    p = a * b
+    ah, al = split(a)
+    bh, bl = split(b)
+    e = ((ah * bh - p) + ah * bl + al * bh) + al * bl
+    s = p + c
+    bb = s - p
+    t = (p - (s - bb)) + (c - bb)
+    return s + (t + e)
+
+
+def bn_finalize_ref(s1, s2, count, gamma, beta, eps, rmean=None, rvar=None, momentum=0.1, fused=False):
     """ubr_bn_finalize's arithmetic in fp64 from the summed statistics: (scale, shift, mean, invstd, running_mean, running_var),
     every vector rounded to fp32 once as the kernel stores it.  momentum: the factor in fp64 (the kernel widens its fp32 argument;
-    for cumulative averaging the caller passes float32(1 / (batches tracked + 1)))."""
+    for cumulative averaging the caller passes float32(1 / (batches tracked + 1))).
+    fused: the two contractions C++ allows and hipcc makes in bn_finalize_kernel -- var = fma(-m, m, s2/count) and
+    running = fma(new, momentum, fl((1 - momentum) * running)); either form is a correct evaluation of the kernel's statements."""
     s1, s2 = s1.double(), s2.double()
     m = s1 / count
-    var = (s2 / count - m * m).clamp_min(0)
+    var = (fma64(-m, m, s2 / count) if fused else s2 / count - m * m).clamp_min(0)
     inv = 1.0 / torch.sqrt(var + float(torch.tensor(eps, dtype=torch.float32)))
     scale = (_vec(gamma, s1) * inv).float()
     out = [scale, beta.float().to(s1.device), m.float(), inv.float(), None, None]
     if rmean is not None:
         unb = var * count / (count - 1.0) if count > 1.0 else var
-        out[4] = ((1.0 - momentum) * _vec(rmean, s1) + momentum * m).float()
-        out[5] = ((1.0 - momentum) * _vec(rvar, s1) + momentum * unb).float()
+        if fused:
+            mom = torch.full_like(m, momentum)
+            out[4] = fma64(m, mom, (1.0 - momentum) * _vec(rmean, s1)).float()
+            out[5] = fma64(unb, mom, (1.0 - momentum) * _vec(rvar, s1)).float()
+        else:
+            out[4] = ((1.0 - momentum) * _vec(rmean, s1) + momentum * m).float()
+            out[5] = ((1.0 - momentum) * _vec(rvar, s1) + momentum * unb).float()
     return tuple(out)
 
 
@@ -666,3 +690,194 @@ def pick_blocks(npix, CU, max_blocks=2048, min_iters=1):
         want = (want + min_iters - 1) // min_iters
     want = max(1, min(want, max_blocks))
     return (want + mult - 1) // mult * mult
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# parameter-side launches: weight images, BatchNorm fold / finalizes, flat optimizer steps, tile crop and stitch
+# (tests/test_gpu_param_exact.py; self-tests in tests/test_cpu_kref.py)
+# ------------------------------------------------------------------------------------------------------------------
+def bits(t):
+    """the raw bit pattern of a floating tensor as integers (so that -0.0 != +0.0 and NaN == NaN)"""
+    return t.contiguous().view(_ITY[t.element_size()])
+
+
+def pack_ref(src_f32, M, Mpad, Kvalid, Kpad, sm, sk, taps, dtype, oscale=None, src_offset=0):
+    """ubr_pack_weights / ubr_pack_item: dst[t][ku][m][e] = (T) (oscale[m] *) src[src_offset + m*sm + (ku*CPU+e)*sk + taps[t]],
+    zero for m >= M and k >= Kvalid.  The gather is fp64; the scale is ONE fp32 multiply (the fp64 product of two fp32 numbers is
+    exact, so .float() is that rounding); then one rounding to `dtype` (torch's .to(): round to nearest even, subnormals kept)."""
+    cpu = CPU[dtype]
+    src = src_f32.reshape(-1)
+    assert src.dtype == torch.float32 and Mpad % 16 == 0 and Kpad % cpu == 0 and M <= Mpad and Kvalid <= Kpad
+    dev = src.device
+    m = torch.arange(M, device=dev).view(1, 1, M)
+    k = torch.arange(Kvalid, device=dev).view(1, Kvalid, 1)
+    t = torch.tensor(list(taps), dtype=torch.int64, device=dev).view(-1, 1, 1)
+    v = src.double()[src_offset + m * sm + k * sk + t]                    # [T][Kvalid][M]
+    if oscale is not None:
+        v = (v * oscale.double().to(dev).view(1, 1, -1)[..., :M]).float().double()
+    full = torch.zeros((t.numel(), Kpad, Mpad), dtype=torch.float64, device=dev)
+    full[:, :Kvalid, :M] = v
+    return full.float().to(dtype).view(t.numel(), Kpad // cpu, cpu, Mpad).permute(0, 1, 3, 2).contiguous()
+
+
+def ulp32(x):
+    """spacing of fp32 numbers at |x| (fp64 tensor): 2^(e-24) for |x| in [2^(e-1), 2^e), never below 2^-149"""
+    _, e = torch.frexp(x.abs())
+    e = torch.where(x == 0, torch.full_like(e, -125), e).clamp_min(-125)
+    return torch.ldexp(torch.ones_like(x), e - 24)
+
+
+def f32(v):
+    """the fp32 value a C `float` argument receives, as a Python float"""
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+def bn_fold_ref(gamma, beta, rmean, rvar, eps, conv_bias=None):
+    """ubr_bn_fold_item in fp64: scale = gamma / sqrt(running_var + eps), bias = (conv_bias - running_mean) * scale + beta.
+    -> (scale rounded to fp32, bias fp64, bound on |stored bias - bias|): half an fp32 ulp for the store plus 2^-50 of the terms,
+    because the device may fuse the multiply-add, so the last fp64 bits are not fixed.  An fp32 evaluation misses the bound."""
+    s = gamma.double() / torch.sqrt(rvar.double() + f32(eps))
+    b = conv_bias.double() if conv_bias is not None else torch.zeros_like(s)
+    t = (b - rmean.double()) * s
+    bias = t + beta.double()
+    return s.float(), bias, 0.5 * ulp32(bias) + 2.0 ** -50 * (t.abs() + beta.double().abs())
+
+
+def stripe_sum(buf, slots, stride, n):
+    """sum_{sl < slots} buf[sl*stride + i], i < n, added in stripe order in fp64 (the finalize / cast kernels' loop)"""
+    a = torch.zeros(n, dtype=torch.float64, device=buf.device)
+    for sl in range(slots):
+        a = a + buf[sl * stride: sl * stride + n]
+    return a
+
+
+def bn_eval_affine_ref(gamma, rvar, eps):
+    """fp64 (invstd, scale) of ubr_bn_eval_affine, which works in fp32: fl(rvar + eps), sqrtf, 1/ (three roundings: gamma(3) on
+    invstd) and one more multiply (gamma(4) on scale)"""
+    inv = 1.0 / torch.sqrt(rvar.double() + f32(eps))
+    return inv, gamma.double() * inv
+
+
+def bn_bwd_finalize_ref(red, C, count, dgamma0=None, dbeta0=None, accumulate=False, slots=STAT_SLOTS):
+    """ubr_bn_bwd_finalize from the stripes [slots][2C] (sum g_y | sum g_y*xhat): (dgamma, dbeta, k1, k2) as stored (fp32).
+    accumulate adds the fp32-rounded sum onto the old fp32 value: one more fp32 rounding.  count None: the frozen form, k = 0."""
+    s = stripe_sum(red.reshape(-1), slots, 2 * C, 2 * C)
+    sg, sgx = s[:C], s[C:]
+    dg, db = sgx.float(), sg.float()
+    if accumulate:
+        dg, db = (dgamma0.double() + dg.double()).float(), (dbeta0.double() + db.double()).float()
+    if count is None:
+        return dg, db, torch.zeros_like(dg), torch.zeros_like(dg)
+    return dg, db, (sg / count).float(), (sgx / count).float()
+
+
+def cast_ref(src, stride, slots, n, scale=1.0, dst0=None, accumulate=False):
+    """ubr_cast_f64_to_f32: dst[i] (+)= fl32(scale * sum_slots src[slot*stride + i])"""
+    v = (stripe_sum(src.reshape(-1), slots, stride, n) * float(scale)).float()
+    return (dst0.double() + v.double()).float() if accumulate else v
+
+
+# Flat optimizer steps (csrc/ubr_head.hip: adam_kernel, sgd_kernel).  The references are torch.optim's single-tensor formulas in
+# fp64 from the kernel's fp32 inputs; with them comes a running-error bound |fp32 result - fp64 value| <= bound, built from
+# gamma(k), k = the number of fp32 roundings on the path of a term, applied to the ABSOLUTE values of the terms (so that the
+# cancellation in gr - m is covered).  A fused multiply-add drops a rounding, never adds one: the counts assume none is fused, so
+# the bound holds either way.  Common to both: gr = wd*p + g*grad_scale: each term is rounded by its multiply and by the add, k = 2.
+def _grad_term(p, g, wd, gs):
+    gr = g * gs + wd * p
+    return gr, (g * gs).abs() + (wd * p).abs()
+
+
+def adam_ref(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, round_bc=True):
+    """one torch.optim.Adam step (L2 weight decay, no amsgrad) -> ((param, exp_avg, exp_avg_sq) fp64, (bounds) fp64).
+    round_bc: the bias corrections as ubr_adam_step forms them -- pow in double, 1 - beta1^step and sqrt(1 - beta2^step) rounded to
+    fp32 (False: kept in double, which is torch.optim's arithmetic)."""
+    lr, b1, b2, eps, wd, gs = (f32(x) for x in (lr, beta1, beta2, eps, weight_decay, grad_scale))
+    bc1, sbc2 = 1.0 - b1 ** step, math.sqrt(1.0 - b2 ** step)
+    if round_bc:
+        bc1, sbc2 = f32(bc1), f32(sbc2)
+    p, g, m, v = (t.double() for t in (p, g, m, v))
+    gr, A_gr = _grad_term(p, g, wd, gs)
+    c1, c2 = 1.0 - b1, 1.0 - b2
+    m1 = m + c1 * (gr - m)
+    v1 = b2 * v + c2 * gr * gr
+    den = torch.sqrt(v1) / sbc2 + eps
+    step_size = lr / bc1
+    r = m1 / den
+    p1 = p - step_size * r
+    # exp_avg: k = 6 on the term c1*gr (gr 2, the subtraction, fl(1 - beta1), the multiply, the add), fewer on m and c1*m
+    E_m = gamma(6) * (m.abs() + c1 * (A_gr + m.abs()))
+    # exp_avg_sq: k = 9 on the term c2*gr*gr (gr twice: 4, fl(1 - beta2), two multiplies, the add), 2 on beta2*v
+    A_v = b2 * v.abs() + c2 * A_gr * A_gr
+    E_v = gamma(9) * A_v
+    # param: running error through sqrtf (1), / sqrt_bc2 (1), + eps (1), exp_avg / denom (1), step_size = fl(lr / bc1) (1),
+    # the multiply (1) and the subtraction (1): k = 4 on the update term, 1 on p, plus what E_m and E_v carry in
+    sq = torch.sqrt(v1)
+    E_s = torch.minimum(torch.sqrt(E_v), E_v / sq.clamp_min(1e-300))             # |sqrt(a) - sqrt(b)| <= min(sqrt|a-b|, |a-b|/sqrt(b))
+    q = sq / sbc2
+    E_q = (E_s / sbc2) * (1.0 + gamma(2)) + gamma(2) * q
+    E_den = E_q + gamma(1) * (q + eps + E_q)
+    lo = (den - E_den).clamp_min(1e-300)
+    E_r = (E_m + r.abs() * E_den) / lo
+    E_r = E_r + gamma(1) * (r.abs() + E_r)
+    E_t = step_size * (E_r * (1.0 + gamma(2)) + gamma(2) * r.abs())
+    E_p = E_t + gamma(1) * (p.abs() + step_size * r.abs() + E_t)
+    return (p1, m1, v1), (E_p, E_m, E_v)
+
+
+def sgd_ref(p, g, buf, lr, momentum, dampening, weight_decay, nesterov, first_step, grad_scale=1.0):
+    """one torch.optim.SGD step -> ((param, momentum buffer or None) fp64, (bounds)).  buf None iff momentum == 0; on the first
+    step the buffer is the gradient and is NOT read."""
+    lr, mom, damp, wd, gs = (f32(x) for x in (lr, momentum, dampening, weight_decay, grad_scale))
+    p, g = p.double(), g.double()
+    gr, A_gr = _grad_term(p, g, wd, gs)
+    k_gr, b1, E_b = 2, None, None
+    if momentum != 0:
+        if first_step:
+            b1, A_b, k_b = gr, A_gr, 2                     # momentum buffer, first step: the gradient itself, k = 2
+        else:
+            b = buf.double()
+            c = 1.0 - damp
+            b1 = mom * b + c * gr
+            A_b = (mom * b).abs() + c * A_gr
+            k_b = 5                                        # momentum buffer: k = 5 on c*gr (gr 2, fl(1 - dampening), multiply, add)
+        E_b = gamma(k_b) * A_b
+        if nesterov:
+            gr, A_gr, k_gr = gr + mom * b1, A_gr + mom * A_b, k_b + 2      # momentum*buf: buf's k, the multiply, the add
+        else:
+            gr, A_gr, k_gr = b1, A_b, k_b
+    p1 = p - lr * gr
+    # param: k = k_gr + 2 on the update term (the multiply by lr and the subtraction: at most 9), 1 on p
+    E_p = gamma(1) * p.abs() + gamma(k_gr + 2) * lr * A_gr
+    return (p1, b1), (E_p, E_b)
+
+
+def crop_tiles_ref(view, desc, th, tw):
+    """ubr_crop_tiles with plain index loops: view numpy [P][rows][cols], desc rows (plane, r0, c0, ...) -> [ntiles][th][tw];
+    pixels of a tile beyond the view are zero"""
+    import numpy as np
+    P, rows, cols = view.shape
+    out = np.zeros((len(desc), th, tw), dtype=view.dtype)
+    for t, d in enumerate(desc):
+        for y in range(th):
+            sy = d[1] + y
+            if sy >= rows:
+                break
+            n = max(0, min(tw, cols - d[2]))
+            out[t, y, :n] = view[d[0], sy, d[2]:d[2] + n]
+    return out
+
+
+def stitch_tiles_ref(scores, desc, out):
+    """ubr_stitch_tiles with plain index loops, in place on `out` numpy [P][C][rows][cols]: tile pixels inside the keep window
+    (kr0, kr1, kc0, kc1, tile coordinates) go to out[plane][c][r0 + y][c0 + x] where that lies inside the view"""
+    P, C, rows, cols = out.shape
+    for t, d in enumerate(desc):
+        p, r0, c0, kr0, kr1, kc0, kc1 = d
+        for y in range(kr0, kr1):
+            if r0 + y >= rows:
+                break
+            for x in range(kc0, kc1):
+                if c0 + x >= cols:
+                    break
+                out[p, :, r0 + y, c0 + x] = scores[t, :, y, x]
+    return out

@@ -461,3 +461,217 @@ def test_fault_element_written_past_C_in_a_sliced_view_is_caught():
     g["buf"][first - 1] = 0.0                             # channel 63 of pixel 0: just in front of the slice
     with pytest.raises(AssertionError, match="outside its output view"):
         B.check_sentinel(snap, "one element in front")
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# parameter-side references (tests/test_gpu_param_exact.py)
+# ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("fwd", [True, False])
+def test_pack_ref_equals_pack_dense(dt, fwd):
+    Cout, Cin, k = 24, 16, 3
+    w = kref.exact_operands((Cout, Cin, k, k), torch.float32, seed=21, density=0.7)
+    kk = k * k
+    M, K, sm, sk = (Cout, Cin, Cin * kk, kk) if fwd else (Cin, Cout, kk, Cin * kk)
+    img = kref.pack_ref(w, M, 32, K, K, sm, sk, range(kk), dt)
+    assert img.dtype == dt and tuple(img.shape) == (kk, K // kref.CPU[dt], 32, kref.CPU[dt])
+    assert torch.equal(kref.unpack_weights(img, K, M), kref.pack_dense(w, range(kk), fwd=fwd))
+    assert not bool(img[:, :, M:, :].any())
+
+
+def test_pack_ref_rounds_once_pads_and_scales():
+    bf, h = torch.bfloat16, torch.float16
+    src = torch.tensor([1 + 2.0 ** -8, 1 + 3 * 2.0 ** -8, -0.0, 1023 * 2.0 ** -24, 2.0 ** -25, 3 * 2.0 ** -25, 1 + 2.0 ** -11, 0.3],
+                       dtype=torch.float32)
+    got = kref.pack_ref(src, 1, 16, 8, 8, 0, 1, [0], bf)[0, 0, 0]
+    assert got[0] == 1.0 and got[1] == 1 + 2.0 ** -6 and kref.bits(got[2:3]).item() == -32768       # ties to even; -0.0 kept
+    goth = kref.pack_ref(src, 1, 16, 8, 8, 0, 1, [0], h)[0, 0, 0]
+    assert goth[3] == 1023 * 2.0 ** -24 and goth[4] == 0 and goth[5] == 2 * 2.0 ** -24 and goth[6] == 1.0
+    # K and M padding are +0; an offset and a scattered tap list address the source as the header says
+    img = kref.pack_ref(torch.arange(100, dtype=torch.float32), 3, 16, 5, 8, 10, 2, [1, 0], torch.float32, src_offset=7)
+    assert img[0, 1, 2, 0] == 7 + 2 * 10 + 4 * 2 + 1 and img[1, 0, 1, 3] == 7 + 10 + 3 * 2
+    assert not bool(kref.bits(img[:, 1, :, 1:]).any()) and not bool(kref.bits(img[:, :, 3:, :]).any())
+    # the scale is one fp32 multiply, then one rounding to the stored type: not the rounding of the exact product
+    s = torch.tensor([1 + 2.0 ** -12])
+    v = torch.tensor([1 + 2.0 ** -11 + 2.0 ** -13])               # v*s = 1 + 2^-11 + 2^-12 + ... -> fp32 -> f16 tie region
+    one = kref.pack_ref(v, 1, 16, 1, 8, 0, 0, [0], h, oscale=s)[0, 0, 0, 0]
+    assert one == (v.double() * s.double()).float().to(h)[0]
+
+
+def test_bn_fold_ref_is_fp64_and_an_fp32_evaluation_misses_its_bound():
+    g = torch.Generator().manual_seed(5)
+    C = 256
+    gamma, beta, mean = (torch.randn(C, generator=g) for _ in range(3))
+    var = torch.rand(C, generator=g) + 0.01
+    cb = torch.randn(C, generator=g)
+    sc, bias, lim = kref.bn_fold_ref(gamma, beta, mean, var, 1e-5, cb)
+    exact = (cb.double() - mean.double()) * (gamma.double() / (var.double() + kref.f32(1e-5)).sqrt()) + beta.double()
+    assert torch.equal(bias, exact) and torch.equal(sc, (gamma.double() / (var.double() + kref.f32(1e-5)).sqrt()).float())
+    assert bool(((bias.float().double() - bias).abs() <= lim).all())            # the correctly rounded value passes
+    s32 = gamma / torch.sqrt(var + 1e-5)
+    b32 = (cb - mean) * s32 + beta
+    assert bool(((b32.double() - bias).abs() > lim).any())                      # fp32 arithmetic does not
+    assert kref.ulp32(torch.tensor([1.0, 1.5, 0.75, 0.0], dtype=D)).tolist() == [2.0 ** -23, 2.0 ** -23, 2.0 ** -24, 2.0 ** -149]
+
+
+def test_finalize_refs_sum_in_stripe_order_and_model_the_accumulate_rounding():
+    C = 5
+    red = torch.zeros((32, 2 * C), dtype=D)
+    red[0], red[1], red[2] = 1.0, 2.0 ** -60, -1.0                       # stripe order: (1 + 2^-60) - 1 = 0; any other order: 2^-60
+    dg, db, k1, k2 = kref.bn_bwd_finalize_ref(red, C, 4.0)
+    assert not bool(dg.any()) and not bool(k1.any())
+    red[3] = 3.0
+    dg0 = torch.full((C,), 2.0 ** 24)
+    dg, db, k1, k2 = kref.bn_bwd_finalize_ref(red, C, 4.0, dg0, dg0.clone(), accumulate=True)
+    assert torch.equal(dg, torch.full((C,), 2.0 ** 24 + 4)) and torch.equal(k2, torch.full((C,), 0.75))     # 2^24 + 3 rounds to even
+    assert torch.equal(kref.bn_bwd_finalize_ref(red, C, None)[2], torch.zeros(C))
+    src = torch.arange(64, dtype=D)
+    assert torch.equal(kref.cast_ref(src, 16, 3, 3, 0.5), torch.tensor([24., 25.5, 27.]))
+    inv, sc = kref.bn_eval_affine_ref(torch.tensor([2.0]), torch.tensor([0.75]), 0.25)
+    assert inv.item() == 1.0 and sc.item() == 2.0
+    # the clamp and count == 1 of bn_finalize_ref
+    out = kref.bn_finalize_ref(torch.tensor([3.0], dtype=D), torch.tensor([8.9], dtype=D), 1.0, torch.ones(1), torch.zeros(1), 0.25,
+                               torch.zeros(1), torch.ones(1), 0.5)
+    assert out[3].item() == 2.0 and out[4].item() == 1.5 and out[5].item() == 0.5
+
+
+def test_fma64_rounds_once():
+    from fractions import Fraction
+    g = torch.Generator().manual_seed(3)
+    a = torch.randn(200, generator=g, dtype=D) * 1000
+    b = a.clone()
+    b[100:] = torch.randn(100, generator=g, dtype=D)
+    c = -(a * b) * (1 + torch.randint(-4, 5, (200,), generator=g).double() * 2.0 ** -52)      # a*b + c cancels to the last bits
+    c[150:] = torch.randn(50, generator=g, dtype=D)
+    got = kref.fma64(a, b, c)
+    exp = torch.tensor([float(Fraction(x) * Fraction(y) + Fraction(z)) for x, y, z in zip(a.tolist(), b.tolist(), c.tolist())], dtype=D)
+    assert torch.equal(got, exp) and not torch.equal(got, a * b + c)
+    # bn_finalize_ref: both evaluations clamp a constant channel whose s2/count lies below m*m
+    cnt, mc = 4096.0, 1000.1
+    for fused in (False, True):
+        out = kref.bn_finalize_ref(torch.tensor([cnt * mc], dtype=D), torch.tensor([cnt * (mc * mc * (1 - 2.0 ** -49))], dtype=D), cnt,
+                                   torch.ones(1), torch.zeros(1), 0.25, torch.zeros(1), torch.ones(1), 0.5, fused=fused)
+        assert out[3].item() == 2.0 and out[5].item() == 0.5
+
+
+ADAM_FLAGS = [(s, wd, lr) for s in (1, 2, 100000) for wd in (0.0, 1e-4) for lr in (1e-5, 1e-3)]
+# torch.optim.SGD refuses Nesterov momentum with zero momentum or non-zero dampening: those combinations have no torch.optim run
+SGD_FLAGS = [(mom, damp, nest) for mom in (0.0, 0.9) for damp in (0.0, 0.5) for nest in (False, True)
+             if not (nest and (mom == 0.0 or damp != 0.0))]
+
+
+def _opt_operands(n, seed):
+    g = torch.Generator().manual_seed(seed)
+    p = torch.randn(n, generator=g)
+    grads = [torch.randn(n, generator=g) * 10.0 ** torch.empty(n).uniform_(-8, 3, generator=g) for _ in range(3)]
+    return p, grads
+
+
+@pytest.mark.parametrize("step0,wd,lr", ADAM_FLAGS)
+def test_adam_ref_equals_torch_optim_in_float64(step0, wd, lr):
+    p0, grads = _opt_operands(64, 7)
+    f = kref.f32
+    q = torch.nn.Parameter(p0.double().clone())
+    opt = torch.optim.Adam([q], lr=f(lr), betas=(f(0.9), f(0.999)), eps=f(1e-8), weight_decay=f(wd))
+    m, v = torch.zeros(64, dtype=D), torch.zeros(64, dtype=D)
+    if step0 > 1:           # start from a state as of step0 - 1
+        q.grad = grads[0].double()
+        opt.step()
+        st = opt.state[q]
+        st["step"] = torch.tensor(float(step0 - 1)) if torch.is_tensor(st["step"]) else step0 - 1
+        m, v = st["exp_avg"].clone(), st["exp_avg_sq"].clone()
+    p = q.detach().clone()
+    for i in range(3):
+        (p, m, v), lims = kref.adam_ref(p, grads[i], m, v, lr, 0.9, 0.999, 1e-8, wd, step0 + i, round_bc=False)
+        q.grad = grads[i].double()
+        opt.step()
+        for a, b in ((p, q.detach()), (m, opt.state[q]["exp_avg"]), (v, opt.state[q]["exp_avg_sq"])):
+            assert float(((a - b).abs() / b.abs().clamp_min(1e-300)).max()) <= 1e-12
+        assert all(bool(torch.isfinite(e).all()) and bool((e >= 0).all()) for e in lims)
+    # the fp32-rounded bias corrections of the entry point move the step by at most two fp32 roundings
+    (pa, _, _), _ = kref.adam_ref(p0, grads[0], m, v, lr, 0.9, 0.999, 1e-8, wd, step0, round_bc=True)
+    (pb, _, _), _ = kref.adam_ref(p0, grads[0], m, v, lr, 0.9, 0.999, 1e-8, wd, step0, round_bc=False)
+    assert bool(((pa - pb).abs() <= kref.gamma(3) * (pb - p0.double()).abs()).all())
+
+
+@pytest.mark.parametrize("mom,damp,nest", SGD_FLAGS)
+@pytest.mark.parametrize("wd", [0.0, 1e-4])
+def test_sgd_ref_equals_torch_optim_in_float64(mom, damp, nest, wd):
+    p0, grads = _opt_operands(64, 9)
+    f = kref.f32
+    q = torch.nn.Parameter(p0.double().clone())
+    opt = torch.optim.SGD([q], lr=f(1e-2), momentum=f(mom), dampening=f(damp), weight_decay=f(wd), nesterov=nest)
+    p, buf = p0.double(), None
+    for i in range(3):
+        (p, buf), lims = kref.sgd_ref(p, grads[i], buf, 1e-2, mom, damp, wd, nest, i == 0)
+        q.grad = grads[i].double()
+        opt.step()
+        assert float(((p - q.detach()).abs() / q.detach().abs().clamp_min(1e-300)).max()) <= 1e-12
+        if mom:
+            b = opt.state[q]["momentum_buffer"]
+            assert float(((buf - b).abs() / b.abs().clamp_min(1e-300)).max()) <= 1e-12
+        else:
+            assert buf is None and lims[1] is None
+
+
+def _f(x):
+    return torch.tensor(x, dtype=torch.float32)
+
+
+def _adam_f32(p, g, m, v, lr, b1, b2, eps, wd, step, gs):
+    """adam_kernel's statements, one fp32 torch op per rounding (nothing fused)"""
+    lr, b1, b2, eps, wd, gs = (_f(x) for x in (lr, b1, b2, eps, wd, gs))
+    bc1, sbc2 = _f(1.0 - float(b1) ** step), _f((1.0 - float(b2) ** step) ** 0.5)
+    gr = wd * p + g * gs
+    m = m + (1 - b1) * (gr - m)
+    v = b2 * v + (1 - b2) * gr * gr
+    return p - (lr / bc1) * (m / (v.sqrt() / sbc2 + eps)), m, v
+
+
+def _sgd_f32(p, g, buf, lr, mom, damp, wd, nest, first, gs):
+    lr, mom, damp, wd, gs = (_f(x) for x in (lr, mom, damp, wd, gs))
+    gr = wd * p + g * gs
+    if float(mom) != 0:
+        buf = gr if first else mom * buf + (1 - damp) * gr
+        gr = mom * buf + gr if nest else buf
+    return p - lr * gr, buf
+
+
+@pytest.mark.parametrize("gs", [1.0, 0.5])
+def test_optimizer_bounds_cover_a_float32_run_and_catch_a_skipped_element(gs):
+    """the running-error bounds hold for the kernels' statements evaluated in fp32 with nothing fused, and an element that was
+    left untouched is outside them"""
+    p, grads = _opt_operands(4096, 11)
+    for step0, wd, lr in ADAM_FLAGS:
+        m, v = torch.zeros(4096), torch.zeros(4096)
+        for i in range(3):
+            (p64, m64, v64), lims = kref.adam_ref(p, grads[i], m, v, lr, 0.9, 0.999, 1e-8, wd, step0 + i, gs)
+            got = _adam_f32(p, grads[i], m, v, lr, 0.9, 0.999, 1e-8, wd, step0 + i, gs)
+            for a, ref, lim in zip(got, (p64, m64, v64), lims):
+                assert bool(((a.double() - ref).abs() <= lim).all())
+            assert bool(((m.double() - m64).abs() > lims[1]).any()) and bool(((v.double() - v64).abs() > lims[2]).any())
+            if lr == 1e-3:
+                assert bool(((p.double() - p64).abs() > lims[0]).any())
+            _, m, v = got
+    for mom in (0.0, 0.9):
+        for damp in (0.0, 0.5):
+            for nest in (False, True):
+                buf = None
+                for i in range(3):
+                    (p64, b64), (Ep, Eb) = kref.sgd_ref(p, grads[i], buf, 1e-2, mom, damp, 1e-4, nest, i == 0, gs)
+                    gp, buf = _sgd_f32(p, grads[i], buf, 1e-2, mom, damp, 1e-4, nest, i == 0, gs)
+                    assert bool(((gp.double() - p64).abs() <= Ep).all()) and bool(((p.double() - p64).abs() > Ep).any())
+                    if mom:
+                        assert bool(((buf.double() - b64).abs() <= Eb).all())
+
+
+def test_tile_refs_crop_with_zero_fill_and_stitch_only_inside_keep_windows():
+    import numpy as np
+    view = np.arange(2 * 5 * 7, dtype=np.float32).reshape(2, 5, 7) + 1
+    crop = kref.crop_tiles_ref(view, [(1, 3, 4, 0, 0, 0, 0), (0, 0, 0, 0, 0, 0, 0)], 4, 6)
+    assert np.array_equal(crop[0, :2, :3], view[1, 3:5, 4:7]) and not crop[0, 2:].any() and not crop[0, :, 3:].any()
+    assert np.array_equal(crop[1], view[0, :4, :6])
+    out = np.full((2, 1, 5, 7), np.nan, dtype=np.float32)
+    scores = np.stack([crop[0][None], crop[1][None]])
+    kref.stitch_tiles_ref(scores, [(1, 3, 4, 0, 4, 0, 6), (0, 0, 0, 1, 3, 2, 2)], out)
+    assert np.array_equal(out[1, 0, 3:5, 4:7], view[1, 3:5, 4:7]) and int(np.isnan(out).sum()) == out.size - 6

@@ -2476,6 +2476,14 @@ namespace {
 //   mode B (sm == ntaps): src[k*sk + m*ntaps + t]  -> per k one run over (m, t)      (Conv2d dgrad, deconv forward)
 //   otherwise: per-element gather (column-expanded stem, zero-padded head dgrad: tiny)
 constexpr int kPackLdsFloats = 8192;
+// oscale: ONE fp32 multiply, then the one rounding to T of ET<T>::pack, in every element type.  The empty asm keeps the fp32
+// product: without it the compiler folds the multiply into the f16 conversion (v_fma_mixlo_f16), which rounds the exact product
+// once -- an f16 image then differs from the bf16 / fp32 arithmetic at ties -- and turns a -0.0 product into +0.0.
+__device__ __forceinline__ float pack_scaled(float v, float sc) {
+  float p = v * sc;
+  asm volatile("" : "+v"(p));
+  return p;
+}
 template <typename T>
 __global__ __launch_bounds__(256) void pack_batched_kernel(const ubr_pack_item* items) {
   constexpr int CPU = ET<T>::CPU;
@@ -2491,12 +2499,18 @@ __global__ __launch_bounds__(256) void pack_batched_kernel(const ubr_pack_item* 
       long r = i / it.Mpad;
       const int ku = (int)(r % it.KU);
       const int t = (int)(r / it.KU);
-      const float sc = (it.oscale != nullptr && m < it.M) ? it.oscale[m] : 1.f;
+      const bool scaled = it.oscale != nullptr && m < it.M;
+      const float sc = scaled ? it.oscale[m] : 1.f;
       float f[CPU];
 #pragma unroll
       for (int e = 0; e < CPU; ++e) {
         const int kc = ku * CPU + e;
-        f[e] = (m < it.M && kc < it.Kvalid) ? it.src[(long)m * it.sm + (long)kc * it.sk + (long)t * it.tap_stride] * sc : 0.f;
+        float v = 0.f;
+        if (m < it.M && kc < it.Kvalid) {
+          v = it.src[(long)m * it.sm + (long)kc * it.sk + (long)t * it.tap_stride];
+          if (scaled) v = pack_scaled(v, sc);
+        }
+        f[e] = v;
       }
       *reinterpret_cast<uint4*>((char*)it.dst + i * 16) = ET<T>::pack(f);
     }
@@ -2534,14 +2548,18 @@ __global__ __launch_bounds__(256) void pack_batched_kernel(const ubr_pack_item* 
     for (int o = threadIdx.x; o < nt * kb * 16; o += 256) {
       const int m = o & 15;
       const int kul = (o >> 4) % kb, t = (o >> 4) / kb;
-      const float sc = (it.oscale != nullptr && m < mn) ? it.oscale[m0 + m] : 1.f;
+      const bool scaled = it.oscale != nullptr && m < mn;
+      const float sc = scaled ? it.oscale[m0 + m] : 1.f;
       float f[CPU];
 #pragma unroll
       for (int e = 0; e < CPU; ++e) {
         const int kl = kul * CPU + e;
-        float v = 0.f;
-        if (m < mn && kl < kn) v = modeA ? lds[m * rowlen + kl * nt + t] : lds[kl * rowlen + m * nt + t];
-        f[e] = v * sc;
+        float v = 0.f;      // padding is +0 whatever the sign of the scale (0.f * sc stored -0.0 under a negative BatchNorm gamma)
+        if (m < mn && kl < kn) {
+          v = modeA ? lds[m * rowlen + kl * nt + t] : lds[kl * rowlen + m * nt + t];
+          if (scaled) v = pack_scaled(v, sc);
+        }
+        f[e] = v;
       }
       *reinterpret_cast<uint4*>((char*)it.dst + (((long)t * it.KU + ku0 + kul) * it.Mpad + m0 + m) * 16) = ET<T>::pack(f);
     }
