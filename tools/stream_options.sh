@@ -1,6 +1,7 @@
 #!/bin/bash
-# The three schedules of the weight gradients, same box, same build (profiles/r03_stream_options.txt):
-#   side stream (default) | one stream, weight gradient before its block's data gradient | one stream, right after it
+# The two schedules of the weight gradients, same box, same build (profiles/r03_stream_options.txt also has the removed
+# "one stream, weight gradient right after its block's data gradient" order):
+#   side stream (default) | one stream, weight gradient before its block's data gradient
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 run() { python bench.py --steps 30 --warmup 5 --full --no-infer --no-cpu-baseline --no-extra-legs | python -c "
@@ -9,5 +10,4 @@ d=json.loads(sys.stdin.read()); print('%.3f ms/step  %.1f img/s  sum of kernel t
 for i in 1 2; do
 echo -n "two streams (side stream for weight gradients):        "; run
 echo -n "one stream, weight gradient BEFORE the data gradient:  "; UBR_WGRAD_STREAM=0 run
-echo -n "one stream, weight gradient AFTER the data gradient:   "; UBR_WGRAD_STREAM=0 UBR_WGRAD_ORDER=after run
 done

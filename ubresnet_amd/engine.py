@@ -17,6 +17,8 @@ only OWNS parameters; this executor runs the fused schedule explicitly:
 """
 from __future__ import annotations
 
+import os
+import struct
 from typing import Callable, Dict, List, Optional
 
 import torch
@@ -33,32 +35,22 @@ DG1 = ops.conv_dgrad_taps_s1(1, 1, 0)
 DG7 = ops.conv_dgrad_taps_s1(7, 1, 3)
 
 
-import os as _os
 # UBR_INFER_FOLD=0: eval forward on the training schedule (BatchNorm applied on load, separate block tails) -- for A/B tests
-_INFER_FOLD = _os.environ.get("UBR_INFER_FOLD", "1") != "0"
-_RELU_MASK = _os.environ.get("UBR_RELU_MASK", "1") != "0"      # block tails keep their final ReLU's mask as bits for the backward
+_INFER_FOLD = os.environ.get("UBR_INFER_FOLD", "1") != "0"
 # BatchNorm-backward finalize fused into the apply pass (every workgroup re-sums the reduce pass's 8 stripes) up to this many
 # channels.  Measured: isolated, the fused apply costs +0.3 ... +2 us over the plain one at every width (512 channels: 8.7 vs
 # 8.4 us) against ~5 us of finalize launch; in the train step 64 vs all widths is within noise -- all widths, for the launches.
-_FIN_MAX_C = int(_os.environ.get("UBR_FIN_MAX_C", "1024"))
-# BatchNorm-backward reduce passes folded into the epilogue of the data-gradient conv that produces their gradient operand
-# (ubr_conv_desc.bnb_c), and identity-block skip gradients re-formed from the ReLU bit mask in the consuming conv's epilogue
-# (ubr_conv_desc.addend_mask) instead of being written by the tail's backward
-_BNB_FUSE = _os.environ.get("UBR_BNB_FUSE", "0") != "0"
-_MASK_ADDEND = _os.environ.get("UBR_MASK_ADDEND", "1") != "0"
-# every k-th weight gradient of a backward pass stays on the compute stream (0 = all on the side stream): static balancing of
-# the two streams of the backward pass
-_WG_MAIN_EVERY = int(_os.environ.get("UBR_WGRAD_MAIN_EVERY", "0"))
-# UBR_WGRAD_ORDER=after: a block's weight gradients are issued right AFTER the data-gradient conv that shares their gradient
-# operand (single-stream schedule: the operand is then still in L2 / MALL); default: before it (side stream: earliest start)
-_WG_AFTER = _os.environ.get("UBR_WGRAD_ORDER", "before") == "after"
-# train-mode forward: the finalize launches of a block's bn2 / bnpass are fused into the block tail kernel
-_DEFER_REDUCE = _os.environ.get("UBR_DEFER_REDUCE", "1") != "0"     # weight-gradient slab sums: one launch per backward stage
-_TAIL_FIN = _os.environ.get("UBR_TAIL_FIN", "1") != "0"
+_FIN_MAX_C = 1024
 # the four output phases of a transposed conv / of a stride-2 conv's data gradient in ONE launch when the layer has at least this
 # many output channels (conv_igemm_kernel: a phase per blockIdx.z; conv_thin_kernel, Cin <= 32 without an addend: a phase loop over
 # one staged halo)
-_PHASE_MIN_C = int(_os.environ.get("UBR_PHASE_MIN_C", "16"))
+_PHASE_MIN_C = 16
+
+
+def wgrad_stream_enabled() -> bool:
+    """UBR_WGRAD_STREAM=0 keeps the weight gradients (and the early repack of the backward weight images) on the compute
+    stream.  Read per pass, not at import: tests and tools set it around single runs."""
+    return os.environ.get("UBR_WGRAD_STREAM", "1") != "0"
 
 
 def _phased(k, pad):
@@ -70,6 +62,7 @@ def _phased(k, pad):
 
 _PH4 = _phased(4, 1)
 _PH3 = _phased(3, 1)
+assert len(_PH4[0]) == 4 and len(_PH3[0]) == 4      # (the one-launch paths below hand all four phases to ops.conv_phases)
 
 
 def _phase(t, ry, rx):
@@ -107,9 +100,10 @@ class Engine:
         self.wws = ops.WgradWorkspace()
         self.side = None
         self._side_on = False
-        self._wg_count = 0
         self._evs, self._ev_next, self._main = [], 0, None
         self._red_buf, self._red_off, self._red_elems = None, 0, 0
+        self._red_batch = ops.ReduceBatch(self.wws)    # slab sums of the weight gradients issued since the last _wg_flush
+        self._fin_pending = []                         # frozen sites whose dgamma / dbeta wait for the next _fin_flush
         self._bwd_packed, self._pack_evs = None, None
         self._rec = None                      # plan being recorded (ubresnet_amd/plan.py)
         self._planned: Dict[tuple, object] = {}
@@ -222,28 +216,45 @@ class Engine:
                         items.append(("fwd", (id(w), "stem%d" % ci), w, ci * 49, w.shape[0], 7, 16, w.shape[1] * 49, 1, 7, 7))
         return items
 
+    def _image_tables(self, dt, device, groups, scale_of=None, slot_of=None):
+        """ubr_pack_item tables of this model's weight images -> (images {key: tensor}, {group: table bytes}, {group: items}).
+        scale_of: {id(weight): per-output-channel scale folded into its image}; slot_of: {id(weight): preallocated image}"""
+        cpu = L.chans_per_unit(dt)
+        images, tables, counts = {}, {g: b"" for g in groups}, {g: 0 for g in groups}
+        for group, k, w, soff, M, Kv, Kpad, sm, sk, ntaps, tstride in self._plan_items():
+            if group not in tables:
+                continue
+            if not w.is_contiguous() or w.dtype != torch.float32 or w.device != device:
+                raise RuntimeError("ubresnet_amd: parameters must be contiguous float32 on %s" % device)
+            Mpad = (M + 15) // 16 * 16
+            Kp = Kpad if Kpad is not None else (Kv + cpu - 1) // cpu * cpu
+            shape = (ntaps, Kp // cpu, Mpad, cpu)
+            dst = slot_of.get(id(w)) if slot_of else None
+            if dst is None:
+                dst = self._new(shape, dtype=dt, device=device)
+            elif tuple(dst.shape) != shape:
+                raise RuntimeError("ubresnet_amd: ASPP branch image %s does not fit its slot %s" % (shape, tuple(dst.shape)))
+            images[k] = dst
+            sc = scale_of.get(id(w)) if scale_of else None
+            tables[group] += struct.pack("<QQqqqQiiiiii", w.data_ptr() + 4 * soff, dst.data_ptr(), sm, sk, tstride,
+                                         sc.data_ptr() if sc is not None else 0, M, Mpad, Kv, Kp // cpu, ntaps, 0)
+            counts[group] += 1
+        return images, tables, counts
+
+    @staticmethod
+    def _device_table(table: bytes, device):
+        return torch.frombuffer(bytearray(table), dtype=torch.uint8).to(device)
+
     def _pack_plan(self, dt, device):
-        import struct
         key = (dt, device)
         plan = self._plans.get(key)
         ptrs = tuple(p.data_ptr() for _, p in self.grad_order)
         if plan is not None and plan["ptrs"] == ptrs:
             return plan
-        cpu = L.chans_per_unit(dt)
-        images, tables = {}, {"fwd": b"", "bwd": b""}
-        counts = {"fwd": 0, "bwd": 0}
-        for group, k, w, soff, M, Kv, Kpad, sm, sk, ntaps, tstride in self._plan_items():
-            if not w.is_contiguous() or w.dtype != torch.float32 or w.device != device:
-                raise RuntimeError("ubresnet_amd: parameters must be contiguous float32 on %s" % device)
-            Mpad = (M + 15) // 16 * 16
-            Kp = Kpad if Kpad is not None else (Kv + cpu - 1) // cpu * cpu
-            dst = self._new((ntaps, Kp // cpu, Mpad, cpu), dtype=dt, device=device)
-            images[k] = dst
-            tables[group] += struct.pack("<QQqqqQiiiiii", w.data_ptr() + 4 * soff, dst.data_ptr(), sm, sk, tstride, 0, M, Mpad, Kv, Kp // cpu, ntaps, 0)
-            counts[group] += 1
+        images, tables, counts = self._image_tables(dt, device, ("fwd", "bwd"))
         plan = {"ptrs": ptrs, "images": images, "counts": counts}
         for g in ("fwd", "bwd"):
-            plan[g] = torch.frombuffer(bytearray(tables[g]), dtype=torch.uint8).to(device) if counts[g] else None
+            plan[g] = self._device_table(tables[g], device) if counts[g] else None
         self._plans[key] = plan
         return plan
 
@@ -258,9 +269,8 @@ class Engine:
     def _pack_bwd_early(self, dt, dev):
         """Training forward: the backward-orientation weight images are not needed before backward starts, so their
         repack runs on the side stream under the forward pass instead of at the head of the backward chain."""
-        import os
         self._bwd_packed = None
-        if dev.type != "cuda" or os.environ.get("UBR_WGRAD_STREAM", "1") == "0":
+        if dev.type != "cuda" or not wgrad_stream_enabled():
             return
         self._ensure_side(dev)
         if self._pack_evs is None:
@@ -282,12 +292,9 @@ class Engine:
         else:
             self.pack_all(dt, dev, "bwd")
 
-    def packed(self, param: torch.Tensor, dtype, orient: str) -> torch.Tensor:
+    def packed(self, param: torch.Tensor, orient: str) -> torch.Tensor:
         """packed image of a weight for this pass (written by pack_all)"""
         return self._images[(id(param), orient)]
-
-    def _packed_dgrad_padded(self, w_param, dt):
-        return self._images[(id(w_param), "dgrad")]
 
     def _alloc_pass_workspaces(self, sv: Saved, device, training: bool):
         nf = sum(4 * s.C for s in self.bn_sites)
@@ -347,25 +354,25 @@ class Engine:
         bn1, bn2 = self.bn(blk.bn1), self.bn(blk.bn2)
         cnt = N * OH * OW
         c1 = self._new((N, OH, OW, Cout), dtype=dt, device=dev)
-        ops.conv(x, self.packed(blk.conv1.weight, dt, "fwd"), c1, T3, Cout, S=S, xf=xf_in, stats=bn1.stats)
+        ops.conv(x, self.packed(blk.conv1.weight, "fwd"), c1, T3, Cout, S=S, xf=xf_in, stats=bn1.stats)
         self._finish_bn(bn1, cnt, training)
         c2 = self._new((N, OH, OW, Cout), dtype=dt, device=dev)
         bnb = self.bn(blk.bnpass) if blk.bypass is not None else None
         # (a frozen site has nothing to finalise: a tail with one takes the plain tail kernel and per-site finish launches)
-        fuse = _TAIL_FIN and training and not bn2.frozen and not (bnb is not None and bnb.frozen) and 24 * Cout <= 65536
+        fuse = training and not bn2.frozen and not (bnb is not None and bnb.frozen) and 24 * Cout <= 65536
         slots = L.RED_SLOTS if fuse else 0
-        ops.conv(c1, self.packed(blk.conv2.weight, dt, "fwd"), c2, T3, Cout, xf=self.relu_affine(bn1), stats=bn2.stats, stats_slots=slots)
+        ops.conv(c1, self.packed(blk.conv2.weight, "fwd"), c2, T3, Cout, xf=self.relu_affine(bn1), stats=bn2.stats, stats_slots=slots)
         if not fuse:
             self._finish_bn(bn2, cnt, training)
         cb = None
         if blk.bypass is not None:
             cb = self._new((N, OH, OW, Cout), dtype=dt, device=dev)
-            ops.conv(x, self.packed(blk.bypass.weight, dt, "fwd"), cb, T1, Cout, S=S, xf=xf_in, stats=bnb.stats, stats_slots=slots)
+            ops.conv(x, self.packed(blk.bypass.weight, "fwd"), cb, T1, Cout, S=S, xf=xf_in, stats=bnb.stats, stats_slots=slots)
             if not fuse:
                 self._finish_bn(bnb, cnt, training)
         # the final ReLU's mask as one byte per 16-byte channel unit: the backward's two passes read it instead of `out`
         mask = None
-        if self._save and _RELU_MASK:
+        if self._save:
             mask = self._new((cnt * (Cout // L.chans_per_unit(dt)),), dtype=torch.uint8, device=dev)
         if fuse:
             f2 = ops.bn_fwd_fin(bn2.stats, blk.bn2, bn2.scale, bn2.shift, bn2.mean, bn2.invstd)
@@ -413,19 +420,15 @@ class Engine:
         on their own.  UBR_WGRAD_STREAM=0 serialises everything on one stream (clean per-kernel timings); the
         launch profiler otherwise times kernels under the same two-stream contention as the real step (and as
         rocprofv3 sees them)."""
-        import os
-        self._side_on = dev.type == "cuda" and os.environ.get("UBR_WGRAD_STREAM", "1") != "0"
-        self._wg_count = 0
+        self._side_on = dev.type == "cuda" and wgrad_stream_enabled()
         if self._side_on:
             self._ensure_side(dev)
-        if self._side_on:
             self._main = torch.cuda.current_stream(dev)
             self._ev_next = 0
 
     def _ensure_side(self, dev):
         if self.side is not None:
             return
-        import os
         # HIP maps normal-priority streams round-robin onto a few hardware queues; once RCCL has created its own
         # streams the side stream can land on the compute stream's queue and the two serialise (measured under
         # torchrun: 17.7 instead of 15.1 ms/step).  High-priority streams use separate queues, so in a
@@ -437,22 +440,18 @@ class Engine:
 
     def _wg_flush(self):
         """one launch for the slab sums of every weight gradient issued since the last flush (ops.ReduceBatch)"""
-        b = self.__dict__.get("_red_batch")
-        if b is not None:
-            b.flush()
+        self._red_batch.flush()
 
     def _fin_flush(self):
         """dgamma / dbeta of the frozen sites back-propagated since the last flush.  Their data gradients did not wait for
         the sums, so these launches sit at the end of a stage, behind the convs, instead of between a BatchNorm backward
         and its consumer."""
-        pend = self.__dict__.get("_fin_pending")
-        if pend:
-            for red, site, G in pend:
-                ops.bn_bwd_finalize_frozen(red, site.C, G(site.mod.weight), G(site.mod.bias))
-            del pend[:]
+        for red, site, G in self._fin_pending:
+            ops.bn_bwd_finalize_frozen(red, site.C, G(site.mod.weight), G(site.mod.bias))
+        del self._fin_pending[:]
 
     def _fin_later(self, red, site, G):
-        self.__dict__.setdefault("_fin_pending", []).append((red, site, G))
+        self._fin_pending.append((red, site, G))
 
     def _side_end(self, dev):
         self._fin_flush()
@@ -463,13 +462,9 @@ class Engine:
             self._side_on = False
 
     def _wg(self, x, g, *args, **kw):
-        self._wg_count += 1
-        if _DEFER_REDUCE and "defer" not in kw:
-            b = self.__dict__.get("_red_batch")
-            if b is None:
-                b = self.__dict__["_red_batch"] = ops.ReduceBatch(self.wws)
-            kw["defer"] = b
-        if not self._side_on or (_WG_MAIN_EVERY > 0 and self._wg_count % _WG_MAIN_EVERY == 0):
+        """weight gradient of one conv; its slab sum is deferred to the stage's _wg_flush"""
+        kw["defer"] = self._red_batch
+        if not self._side_on:
             return ops.wgrad(x, g, *args, **kw)
         # side stream waits for everything queued on the compute stream so far (x and g are produced there); the
         # launch goes straight to the side stream's handle -- no stream-context switch, one pooled event per call
@@ -489,21 +484,15 @@ class Engine:
         self._ev_next = i + 1
         return self._evs[i]
 
-    def _bn_bwd(self, site: BNSite, ga, ga2, c, relu, G, cnt, red=None):
-        """backward through a = relu(bn(c)) (or bn only): returns g_c; writes dgamma/dbeta.
-        red: the reduce pass's sums, when the conv that produced `ga` already accumulated them in its epilogue"""
+    def _bn_bwd(self, site: BNSite, ga, ga2, c, relu, G, cnt):
+        """backward through a = relu(bn(c)) (or bn only): returns g_c; writes dgamma/dbeta."""
+        red = self._red(2 * site.C, c.device)
         if site.frozen:
             gc = self._new(c.shape, dtype=c.dtype, device=c.device)
-            if red is None:
-                red = self._red(2 * site.C, c.device)
-                ops.bn_bwd_frozen(ga, ga2, c, site.scale, site.shift, site.mean, site.invstd, relu, red, gc)
-            else:
-                ops.bn_bwd_frozen(ga, ga2, c, site.scale, site.shift, site.mean, site.invstd, relu, None, gc)
+            ops.bn_bwd_frozen(ga, ga2, c, site.scale, site.shift, site.mean, site.invstd, relu, red, gc)
             self._fin_later(red, site, G)
             return gc
-        if red is None:
-            red = self._red(2 * site.C, c.device)
-            ops.bn_bwd_reduce(ga, ga2, c, site.scale, site.shift, site.mean, site.invstd, relu, red)
+        ops.bn_bwd_reduce(ga, ga2, c, site.scale, site.shift, site.mean, site.invstd, relu, red)
         gc = self._new(c.shape, dtype=c.dtype, device=c.device)
         if site.C <= _FIN_MAX_C:
             ops.bn_bwd_apply_fin(ga, ga2, c, site.scale, site.shift, site.mean, site.invstd, relu, red, cnt,
@@ -515,17 +504,17 @@ class Engine:
         ops.bn_bwd_apply(ga, ga2, c, site.scale, site.shift, site.mean, site.invstd, relu, k1, k2, gc)
         return gc
 
-    def _conv_dgrad(self, conv_mod, g, gx, S, addend=None, k=3, addend_mask=None, bnb=None, stats=None):
+    def _conv_dgrad(self, conv_mod, g, gx, S, addend=None, k=3, addend_mask=None):
         """data gradient of Conv2d(k, stride S, pad k//2): g (conv output grad) -> gx (input grad view)"""
         dt = g.dtype
-        wp = self.packed(conv_mod.weight, dt, "dgrad")
+        wp = self.packed(conv_mod.weight, "dgrad")
         Cin = gx.shape[3]
         pad = k // 2
         if S == 1:
             taps = DG3 if k == 3 else (DG1 if k == 1 else DG7)
-            ops.conv(g, wp, gx, taps, Cin, addend=addend, addend_mask=addend_mask, bnb=bnb, stats=stats)
+            ops.conv(g, wp, gx, taps, Cin, addend=addend, addend_mask=addend_mask)
         else:
-            if k == 3 and Cin >= _PHASE_MIN_C and len(_PH3[0]) == 4 and addend_mask is None and bnb is None:
+            if k == 3 and Cin >= _PHASE_MIN_C and addend_mask is None:
                 ops.conv_phases(g, wp, _phase(gx, 0, 0), _PH3[1], Cin, phases=_PH3[0], y_full=gx, addend_full=addend)
                 return
             for ry in range(2):
@@ -551,19 +540,19 @@ class Engine:
         red = self._red((4 if byp else 2) * Cout, dev)
         red2 = red[:2 * Cout * NS]
         redb = red[2 * Cout * NS:] if byp else None
-        mask = getattr(rec, "mask", None)
-        # every site of the tail frozen: one pass (no sum stands between go and the data gradients); sites in different modes,
-        # or no bit mask: the two passes, with k1 = k2 = 0 for the frozen site
+        mask = rec.mask         # (the final ReLU's bit mask: block_fwd keeps one whenever it keeps a record)
+        # every site of the tail frozen: one pass (no sum stands between go and the data gradients); sites in different modes:
+        # the two passes, with k1 = k2 = 0 for the frozen site
         nfrozen = int(bn2.frozen) + int(byp and bnb.frozen)
-        onepass = mask is not None and nfrozen == (2 if byp else 1)
-        fin = mask is not None and Cout <= _FIN_MAX_C and nfrozen == 0
+        onepass = nfrozen == (2 if byp else 1)
+        fin = Cout <= _FIN_MAX_C and nfrozen == 0
         if not onepass:
             ops.block_tail_bwd_reduce(go, go2, out, c2, bn2.scale, bn2.shift, bn2.mean, bn2.invstd,
                                       cb, bnb.mean if byp else None, bnb.invstd if byp else None, red2, redb, relu_mask=mask)
         g_c2 = self._new(c2.shape, dtype=dt, device=dev)
         # identity block with one gradient operand: the skip gradient go*[out>0] is not written; conv1's data-gradient epilogue
         # re-forms it from go and the bit mask
-        lazy_sc = _MASK_ADDEND and not byp and go2 is None and need_gx and (fin or onepass)
+        lazy_sc = not byp and go2 is None and need_gx and (fin or onepass)
         g_sc = None if lazy_sc else self._new(c2.shape, dtype=dt, device=dev)
         if onepass:
             ops.block_tail_bwd_frozen(go, go2, mask, c2, bn2.scale, bn2.shift, bn2.mean, bn2.invstd, red2,
@@ -588,34 +577,19 @@ class Engine:
             ops.block_tail_bwd_apply(go, go2, out, c2, bn2.scale, bn2.shift, bn2.mean, bn2.invstd, k[:Cout], k[Cout:2 * Cout],
                                      cb, bnb.scale if byp else None, bnb.mean if byp else None, bnb.invstd if byp else None,
                                      k[2 * Cout:3 * Cout] if byp else None, k[3 * Cout:] if byp else None, g_c2, g_sc, relu_mask=mask)
-        # conv2: weight grad (input = relu(bn1(c1)) re-formed on load) and data grad
+        # conv2: weight grad (input = relu(bn1(c1)) re-formed on load) and data grad.  Every weight gradient is issued BEFORE the
+        # data-gradient conv that shares its gradient operand: on the side stream it then starts earliest
         kk = 9
-        if not _WG_AFTER:
-            self._wg(c1, g_c2, T3, G(blk.conv2.weight), Cout * kk, kk, Cout, Cout, self.wws, xf=self.relu_affine(bn1))
+        self._wg(c1, g_c2, T3, G(blk.conv2.weight), Cout * kk, kk, Cout, Cout, self.wws, xf=self.relu_affine(bn1))
         g_a1 = self._new(c1.shape, dtype=dt, device=dev)
-        if _BNB_FUSE:
-            # the reduce pass of bn1's backward rides in the epilogue of the conv that produces its gradient operand
-            red1 = self._red(2 * Cout, dev)
-            self._conv_dgrad(blk.conv2, g_c2, g_a1, 1, bnb=(c1, bn1.mean, bn1.scale, bn1.shift, bn1.invstd), stats=red1)
-            if _WG_AFTER:
-                self._wg(c1, g_c2, T3, G(blk.conv2.weight), Cout * kk, kk, Cout, Cout, self.wws, xf=self.relu_affine(bn1))
-            del g_c2
-            g_c1 = self._bn_bwd(bn1, g_a1, None, c1, True, G, cnt, red=red1)
-        else:
-            self._conv_dgrad(blk.conv2, g_c2, g_a1, 1)
-            if _WG_AFTER:
-                self._wg(c1, g_c2, T3, G(blk.conv2.weight), Cout * kk, kk, Cout, Cout, self.wws, xf=self.relu_affine(bn1))
-            del g_c2
-            g_c1 = self._bn_bwd(bn1, g_a1, None, c1, True, G, cnt)
+        self._conv_dgrad(blk.conv2, g_c2, g_a1, 1)
+        del g_c2
+        g_c1 = self._bn_bwd(bn1, g_a1, None, c1, True, G, cnt)
         del g_a1
         Cin = x.shape[3]
-
-        def wg_conv1():
-            self._wg(x, g_c1, T3, G(blk.conv1.weight), Cin * kk, kk, Cout, Cin, self.wws, S=S, xf=rec.xf_in)
-            if byp:
-                self._wg(x, g_sc, T1, G(blk.bypass.weight), Cin, 1, Cout, Cin, self.wws, S=S, xf=rec.xf_in)
-        if not _WG_AFTER or not need_gx:
-            wg_conv1()
+        self._wg(x, g_c1, T3, G(blk.conv1.weight), Cin * kk, kk, Cout, Cin, self.wws, S=S, xf=rec.xf_in)
+        if byp:
+            self._wg(x, g_sc, T1, G(blk.bypass.weight), Cin, 1, Cout, Cin, self.wws, S=S, xf=rec.xf_in)
         if not need_gx:
             return None
         gx = self._new(x.shape, dtype=dt, device=dev)
@@ -626,8 +600,6 @@ class Engine:
             self._conv_dgrad(blk.conv1, g_c1, gx, S, addend=go, addend_mask=mask)
         else:
             self._conv_dgrad(blk.conv1, g_c1, gx, S, addend=g_sc)
-        if _WG_AFTER:
-            wg_conv1()
         return gx
 
     # ------------------------------------------------------------------ DoubleResNet
@@ -647,9 +619,9 @@ class Engine:
     # ------------------------------------------------------------------ ConvTransposeLayer
     def deconv_fwd(self, dl, x, cat, Cd, dt, xf_x=None):
         """ConvTranspose2d(k4,s2,p1) of x into channels [0,Cd) of the concat buffer (4 output phases)."""
-        wp = self.packed(dl.deconv.weight, dt, "tfwd")
+        wp = self.packed(dl.deconv.weight, "tfwd")
         up = cat[..., :Cd]
-        if Cd >= _PHASE_MIN_C and len(_PH4[0]) == 4:
+        if Cd >= _PHASE_MIN_C:
             ops.conv_phases(x, wp, _phase(up, 0, 0), _PH4[1], Cd, phases=_PH4[0], y_full=up, xf=xf_x)
             return
         for ry in range(2):
@@ -682,7 +654,7 @@ class Engine:
                 self._wg(x, _phase(g_up, ry, rx), taps, dW, 16, Cd * 16, Cd, Cin, self.wws, xf=xf_x)
         # data gradient of the transposed conv = ordinary stride-2 conv over g_up
         gx = self._new(x.shape, dtype=x.dtype, device=x.device)
-        wp = self.packed(dl.deconv.weight, x.dtype, "tdgrad")
+        wp = self.packed(dl.deconv.weight, "tdgrad")
         ops.conv(g_up, wp, gx, ops.conv_taps(4, 1, 1), Cin, S=2)
         return gx, g_cat
 
@@ -701,7 +673,7 @@ class Engine:
         w = conv1.weight
         for ci in range(Cin):
             last = ci == Cin - 1
-            ops.conv(x16[..., 16 * ci:16 * ci + 16], self.packed(w, dt, "stem%d" % ci), c0, self.STEM_TAPS, Cout,
+            ops.conv(x16[..., 16 * ci:16 * ci + 16], self.packed(w, "stem%d" % ci), c0, self.STEM_TAPS, Cout,
                      bias=conv1.bias if ci == 0 else None, addend=c0 if ci > 0 else None, stats=stats if last else None)
         return x16
 
@@ -718,22 +690,26 @@ class Engine:
         ops.cast_f64_to_f32(red, G(conv1.bias), Cout)
 
 
-    # ------------------------------------------------------------------ head (shared by both networks)
-    def head_fwd(self, m, d1o, training, dt):
+    # ------------------------------------------------------------------ head
+    def head_fwd(self, m, d1o, training, dt, sv):
+        """conv10 + bias -> bn10 -> relu -> conv11 + bias -> log-softmax (fused epilogue, NCHW fp32)"""
         N, H, W, _ = d1o.shape
         bn10 = self.bn(m.bn10)
         nk = m.conv10.out_channels
         c10 = self._new((N, H, W, nk), dtype=dt, device=d1o.device)
-        ops.conv(d1o, self.packed(m.conv10.weight, dt, "fwd"), c10, T7, nk, bias=m.conv10.bias, stats=bn10.stats)
+        ops.conv(d1o, self.packed(m.conv10.weight, "fwd"), c10, T7, nk, bias=m.conv10.bias, stats=bn10.stats)
         self._finish_bn(bn10, N * H * W, training)
         ncls = m.conv11.out_channels
-        out = self._final_logsoftmax(m, c10, self.packed(m.conv11.weight, dt, "fwd"), self.relu_affine(bn10), (N, ncls, H, W))
-        return c10, out
+        out = self._final_logsoftmax(m, c10, self.packed(m.conv11.weight, "fwd"), self.relu_affine(bn10), (N, ncls, H, W))
+        sv.d1o, sv.c10, sv.out, sv.dt = d1o, c10, out.detach(), dt     # (an alias without grad_fn: autograd attaches the node to `out` itself, and node -> ctx -> sv -> out would be a cycle)
+        return out
 
     def head_bwd(self, m, sv, g_logp, G):
         dt, dev = sv.dt, sv.x.device
         N, ncls, H, W = sv.out.shape
         ip = m.conv10.in_channels
+        if not g_logp.is_contiguous():
+            g_logp = g_logp.contiguous()
         g_l = self._new((N, H, W, 16), dtype=dt, device=dev)
         self._logsoftmax_bwd(g_logp, sv.out, g_l)
         bn10 = self.bn(m.bn10)
@@ -744,11 +720,10 @@ class Engine:
         ops.channel_sum(g_l, red[:16 * NS])
         ops.cast_f64_to_f32(red[:16 * NS], G(m.conv11.bias), ncls, stride=16)
         g_a10 = self._new((N, H, W, nk), dtype=dt, device=dev)
-        red10 = self._red(2 * nk, dev) if _BNB_FUSE else None
-        ops.conv(g_l, self._packed_dgrad_padded(m.conv11.weight, dt), g_a10, DG7, nk,
-                 bnb=(sv.c10, bn10.mean, bn10.scale, bn10.shift, bn10.invstd) if _BNB_FUSE else None, stats=red10)
+        # data gradient of conv11: K = the 16 (zero-padded) logit channels
+        ops.conv(g_l, self.packed(m.conv11.weight, "dgrad"), g_a10, DG7, nk)
         del g_l
-        g_c10 = self._bn_bwd(bn10, g_a10, None, sv.c10, True, G, N * H * W, red=red10)
+        g_c10 = self._bn_bwd(bn10, g_a10, None, sv.c10, True, G, N * H * W)
         del g_a10
         self._wg(sv.d1o, g_c10, T7, G(m.conv10.weight), ip * 49, 49, nk, ip, self.wws)
         ops.channel_sum(g_c10, red[16 * NS:])
@@ -826,7 +801,7 @@ class Engine:
                 done[0] = hi
         return stage_done
 
-    # ------------------------------------------------------------------ ASPP_ResNet (models/ASPP_ResNet.py:416-523)
+    # ------------------------------------------------------------------ ASPP levels (models/ASPP_ResNet.py:227-286)
     def _affine_arena(self, sv, device, sizes, relu_ranges):
         """per-pass [4][T] float arena of per-channel affines: identity (sub 0, scale 1, shift 0, lo -inf) except
         lo = 0 on `relu_ranges` (where BatchNorm+ReLU sites will be bound).  One template copy per pass."""
@@ -865,13 +840,13 @@ class Engine:
         cnt = N * h * w
         for b, (conv, bn, k, dil) in enumerate(layer.branches()):
             site = self.bn(bn)
-            ops.conv(e, self.packed(conv.weight, dt, "fwd"), acat[..., 16 * b:16 * b + 16], ops.conv_taps(k, dil, dil * (k // 2)),
+            ops.conv(e, self.packed(conv.weight, "fwd"), acat[..., 16 * b:16 * b + 16], ops.conv_taps(k, dil, dil * (k // 2)),
                      16, bias=conv.bias, stats=site.stats)
             self._finish_bn(site, cnt, training)
         ops.maxpool_fwd(e, None, acat[..., 64:], None, 1)
         psite = self.bn(post.ASPP_bn)
         xf = self._arena_affine(arena, off_acat, 64 + Cn)
-        ops.conv(acat, self.packed(post.ASPP_conv.weight, dt, "fwd"), cpost, T1, Cn, xf=xf, bias=post.ASPP_conv.bias, stats=psite.stats)
+        ops.conv(acat, self.packed(post.ASPP_conv.weight, "fwd"), cpost, T1, Cn, xf=xf, bias=post.ASPP_conv.bias, stats=psite.stats)
         self._finish_bn(psite, cnt, training)
         if not self._save:
             return None
@@ -892,7 +867,7 @@ class Engine:
         ops.channel_sum(g_cpost, red)
         ops.cast_f64_to_f32(red, G(post.ASPP_conv.bias), Cn)
         g_acat = self._new(acat.shape, dtype=dt, device=dev)
-        ops.conv(g_cpost, self.packed(post.ASPP_conv.weight, dt, "dgrad"), g_acat, DG1, 64 + Cn)
+        ops.conv(g_cpost, self.packed(post.ASPP_conv.weight, "dgrad"), g_acat, DG1, 64 + Cn)
         del g_cpost
         g_e = self._new(e.shape, dtype=dt, device=dev)
         ops.maxpool_bwd(e, None, g_acat[..., 64:], g_base, g_e, 1)
@@ -905,22 +880,159 @@ class Engine:
             redb = self._red(16, dev)
             ops.channel_sum(g_cb, redb)
             ops.cast_f64_to_f32(redb, G(conv.bias), 16)
-            ops.conv(g_cb, self.packed(conv.weight, dt, "dgrad"), g_e, ops.conv_dgrad_taps_s1(k, dil, dil * (k // 2)), Cn, addend=g_e)
+            ops.conv(g_cb, self.packed(conv.weight, "dgrad"), g_e, ops.conv_dgrad_taps_s1(k, dil, dil * (k // 2)), Cn, addend=g_e)
         return g_e
+
+    # ------------------------------------------------------------------ stages of a pass (shared by both networks)
+    # uresnet_* and aspp_* below are a buffer layout plus calls to these.  What differs between the networks arrives as
+    # arguments: the concat buffers [deconv | ASPP_post | skip], the bottom tensor, the input affines of dec_layer5 /
+    # dec_layer4, and in backward the gradient each encoder level is owed beside the chain's.
+    def _forward_begin(self, x, training, dt, save):
+        self._save = save
+        x = self._check_input(x, self.model.conv1.in_channels)
+        sv = Saved()
+        self._alloc_pass_workspaces(sv, x.device, training)
+        self.pack_all(dt, x.device, "fwd")
+        if save:
+            self._pack_bwd_early(dt, x.device)
+        return x, sv
+
+    def _concat_buffers(self, x, dt, widths):
+        """cat1 .. cat5, the decoder levels' input buffers: level i at 1 / 2^(i-1) of the input resolution"""
+        N, _, H, W = x.shape
+        return [self._new((N, H >> i, W >> i, c), dtype=dt, device=x.device) for i, c in enumerate(widths)]
+
+    def stem_pool_fwd(self, m, x, cat1, training, dt, sv):
+        """conv1 -> (bn1 + relu folded into consumers) -> pool; x0 goes into the skip half of dec_layer1's concat buffer"""
+        N, _, H, W = x.shape
+        ip, dev = m.inplanes, x.device
+        bn1 = self.bn(m.bn1)
+        c0 = self._new((N, H, W, ip), dtype=dt, device=dev)
+        x16 = self.stem_fwd(m.conv1, x, c0, bn1.stats, dt)
+        self._finish_bn(bn1, N * H * W, training)
+        p0 = self._new((N, H // 2, W // 2, ip), dtype=dt, device=dev)
+        amax = self._new((N, H // 2, W // 2, ip), dtype=torch.uint8, device=dev) if self._save else None   # window arg-max for the backward
+        ops.maxpool_fwd(c0, self.relu_affine(bn1), p0, cat1[..., ip:], 2, argmax=amax)
+        sv.x, sv.x16, sv.c0, sv.amax = x, x16, c0, amax
+        return p0
+
+    def stem_pool_bwd(self, m, sv, g_p0, g_x0, G):
+        """g_p0: gradient of the pooled tensor; g_x0: gradient the skip connection into dec_layer1 owes relu(bn1(c0))"""
+        bn1 = self.bn(m.bn1)
+        N, H, W, _ = sv.c0.shape
+        g_a0 = self._new(sv.c0.shape, dtype=sv.dt, device=sv.c0.device)
+        ops.maxpool_bwd(sv.c0, self.relu_affine(bn1), g_p0, g_x0, g_a0, 2, argmax=sv.amax)
+        g_c0 = self._bn_bwd(bn1, g_a0, None, sv.c0, True, G, N * H * W)
+        self.stem_bwd(m.conv1, sv.x16, g_c0, G)
+
+    def encoder_fwd(self, m, x, outs, training, dt):
+        """enc_layer1 .. enc_layer5; outs: each level's output view (the skip channels of the next decoder level's concat buffer)"""
+        recs = []
+        for i, out in enumerate(outs, 1):
+            recs.append(self.double_fwd(getattr(m, "enc_layer%d" % i), x, out, training, dt))
+            x = out
+        return tuple(recs)
+
+    def encoder_bwd(self, m, sv, g, owed, G, stage_done):
+        """g: gradient of enc_layer5's output.  owed[i - 1]: what the output of level i is owed beside the chain's gradient --
+        None, a tensor (a concat buffer's skip channels), or a callable that issues the launches producing it right before
+        the level's own (an ASPP level's backward)"""
+        for i in (5, 4, 3, 2, 1):
+            g2 = owed[i - 1]() if callable(owed[i - 1]) else owed[i - 1]
+            g = self.double_bwd(sv.enc[i - 1], g, g2, G); stage_done(getattr(m, "enc_layer%d" % i).res1.conv1.weight)
+        return g
+
+    def decoder_fwd(self, m, x, cats, training, dt, xf={}):
+        """dec_layer5 .. dec_layer1 from the bottom tensor x; the skip channels of cats = (cat1 .. cat5) are already filled.
+        xf: {level: (affine of a virtual deconv input, affine of virtual concat channels)}.  -> (dec_layer1's output, records)"""
+        recs = [None] * 5
+        for i in (5, 4, 3, 2, 1):
+            dl, cat = getattr(m, "dec_layer%d" % i), cats[i - 1]
+            out = self._new(tuple(cat.shape[:3]) + (dl.res.res2.conv2.out_channels,), dtype=dt, device=x.device)
+            xf_x, xf_cat = xf.get(i, (None, None))
+            recs[i - 1] = self.declayer_fwd(dl, x, cat, dl.deconv.out_channels, out, training, dt, xf_x=xf_x, xf_cat=xf_cat)
+            x = out
+        return x, tuple(recs)
+
+    def decoder_bwd(self, m, sv, g, G, stage_done):
+        """-> (gradient of the bottom tensor, gradients of cat1 .. cat5: their skip channels are what the encoder is owed)"""
+        g_cats = []
+        for i, rec in enumerate(sv.dec, 1):
+            g, g_cat = self.declayer_bwd(rec, g, G); stage_done(getattr(m, "dec_layer%d" % i).deconv.weight)
+            g_cats.append(g_cat)
+        return g, g_cats
+
+    def _backward_begin(self, sv, grad_ready):
+        dev = sv.x.device
+        self._rebind(sv)
+        self._pack_bwd(sv.dt, dev)
+        flat, views = self._grad_views(dev)
+        stage_done = self._stage_notifier(flat, grad_ready)
+        self._side_begin(dev)
+        self._red_begin(dev)
+        return flat, views, (lambda p: views[id(p)]), stage_done
+
+    def _backward_end(self, sv, stage_done):
+        stage_done(self.grad_order[-1][1])
+        self._side_end(sv.x.device)
+        self._red_buf = None
+
+    # ------------------------------------------------------------------ UResNet (models/ub_uresnet.py:88-147)
+    def _uresnet_buffers(self, x, dt):
+        """-> (cat1 .. cat5 = [deconv | skip], the bottom tensor, the encoder levels' outputs: the skip halves and the bottom)"""
+        N, _, H, W = x.shape
+        ip = self.model.inplanes
+        cats = self._concat_buffers(x, dt, [2 * ip, 4 * ip, 8 * ip, 16 * ip, 32 * ip])
+        x5 = self._new((N, H // 32, W // 32, 32 * ip), dtype=dt, device=x.device)
+        return cats, x5, [cats[1][..., 2 * ip:], cats[2][..., 4 * ip:], cats[3][..., 8 * ip:], cats[4][..., 16 * ip:], x5]
+
+    def uresnet_forward(self, x: torch.Tensor, training: bool, dt: torch.dtype, save: bool):
+        """training: BatchNorm modules in train mode use batch statistics (and update their running statistics), modules in eval
+        mode are frozen; training = False freezes every site.  save: keep activations for backward"""
+        m = self.model
+        x, sv = self._forward_begin(x, training, dt, save)
+        cats, x5, enc = self._uresnet_buffers(x, dt)
+        p0 = self.stem_pool_fwd(m, x, cats[0], training, dt, sv)
+        sv.enc, sv.aspp = self.encoder_fwd(m, p0, enc, training, dt), ()
+        d1o, sv.dec = self.decoder_fwd(m, x5, cats, training, dt)
+        out = self.head_fwd(m, d1o, training, dt, sv)
+        return out, (sv if save else None)
+
+    def uresnet_backward(self, sv: Saved, g_logp: torch.Tensor, grad_ready: Optional[Callable] = None):
+        """-> flat fp32 gradient buffer (layout self.grad_offsets)."""
+        m = self.model
+        flat, views, G, stage_done = self._backward_begin(sv, grad_ready)
+        g = self.head_bwd(m, sv, g_logp, G); stage_done(m.bn10.bias)
+        g, gc = self.decoder_bwd(m, sv, g, G, stage_done)
+        # skip gradients arrive through the concat buffers' second halves
+        owed = [gc[i][..., sv.dec[i].Cd:] for i in (1, 2, 3, 4)] + [None]
+        g = self.encoder_bwd(m, sv, g, owed, G, stage_done)
+        self.stem_pool_bwd(m, sv, g, gc[0][..., sv.dec[0].Cd:], G)
+        self._backward_end(sv, stage_done)
+        return flat, views
+
+    # ------------------------------------------------------------------ ASPP_ResNet (models/ASPP_ResNet.py:416-523)
+    def _aspp_levels(self):
+        m = self.model
+        return [(m.ASPP_layer_enc3, m.ASPP_combine_enc3), (m.ASPP_layer_enc4, m.ASPP_combine_enc4), (m.ASPP_layer_enc5, m.ASPP_combine_enc5)]
+
+    def _aspp_buffers(self, x, dt):
+        """-> (cat1 .. cat5 with cat4 / cat5 = [deconv | ASPP_post | skip], skip5 = [ASPP_post(e5) | e5] (the bottom tensor),
+        the encoder levels' outputs, the destinations of the three ASPP_post convs)"""
+        N, _, H, W = x.shape
+        ip = self.model.inplanes
+        C3, C4, C5 = 8 * ip, 16 * ip, 32 * ip
+        cats = self._concat_buffers(x, dt, [2 * ip, 4 * ip, 8 * ip, 3 * C3, 3 * C4])
+        skip5 = self._new((N, H // 32, W // 32, 2 * C5), dtype=dt, device=x.device)
+        enc = [cats[1][..., 2 * ip:], cats[2][..., 4 * ip:], cats[3][..., 2 * C3:], cats[4][..., 2 * C4:], skip5[..., C5:]]
+        return cats, skip5, enc, [cats[3][..., C3:2 * C3], cats[4][..., C4:2 * C4], skip5[..., :C5]]
 
     def aspp_forward(self, x, training, dt, save):
         m = self.model
-        self._save = save
-        x = self._check_input(x, m.conv1.in_channels)
-        N, Cin, H, W = x.shape
-        dev, ip = x.device, m.inplanes
-        sv = Saved()
-        self._alloc_pass_workspaces(sv, dev, training)
-        self.pack_all(dt, dev, "fwd")
-        if save:
-            self._pack_bwd_early(dt, dev)
-        E = lambda *shape: self._new(shape, dtype=dt, device=dev)
+        x, sv = self._forward_begin(x, training, dt, save)
+        ip = m.inplanes
         C3, C4, C5 = 8 * ip, 16 * ip, 32 * ip
+        levels = self._aspp_levels()
         # affine arena: [acat3 | acat4 | acat5 | cat4 (up,post3,e3) | cat5 (up,post4,e4) | skip5 (post5,e5)]
         sizes = [64 + C3, 64 + C4, 64 + C5, C3 + 2 * C3, C4 + 2 * C4, 2 * C5]
         o, offs0 = 0, []
@@ -929,243 +1041,40 @@ class Engine:
             o += n
         relu_ranges = [(offs0[0], offs0[0] + 64), (offs0[1], offs0[1] + 64), (offs0[2], offs0[2] + 64),
                        (offs0[3] + C3, offs0[3] + 2 * C3), (offs0[4] + C4, offs0[4] + 2 * C4), (offs0[5], offs0[5] + C5)]
-        arena, offs = self._affine_arena(sv, dev, sizes, relu_ranges)
-        for lvl, o_acat in ((3, offs[0]), (4, offs[1]), (5, offs[2])):
-            layer = getattr(m, "ASPP_layer_enc%d" % lvl)
+        arena, offs = self._affine_arena(sv, x.device, sizes, relu_ranges)
+        for (layer, post), o_acat, o_post in zip(levels, offs[:3], (offs[3] + C3, offs[4] + C4, offs[5])):
             for b, (_, bn, _, _) in enumerate(layer.branches()):
                 self._bind_site(self.bn(bn), arena, o_acat + 16 * b)
-        self._bind_site(self.bn(m.ASPP_combine_enc3.ASPP_bn), arena, offs[3] + C3)
-        self._bind_site(self.bn(m.ASPP_combine_enc4.ASPP_bn), arena, offs[4] + C4)
-        self._bind_site(self.bn(m.ASPP_combine_enc5.ASPP_bn), arena, offs[5])
+            self._bind_site(self.bn(post.ASPP_bn), arena, o_post)
         self._snapshot_sites(sv)
 
-        bn1 = self.bn(m.bn1)
-        c0 = E(N, H, W, ip)
-        x16 = self.stem_fwd(m.conv1, x, c0, bn1.stats, dt)
-        self._finish_bn(bn1, N * H * W, training)
-        cat1 = E(N, H, W, 2 * ip)
-        p0 = E(N, H // 2, W // 2, ip)
-        amax = self._new((N, H // 2, W // 2, ip), dtype=torch.uint8, device=dev) if save else None   # window arg-max for the backward
-        ops.maxpool_fwd(c0, self.relu_affine(bn1), p0, cat1[..., ip:], 2, argmax=amax)
-        cat2 = E(N, H // 2, W // 2, 4 * ip)
-        cat3 = E(N, H // 4, W // 4, 8 * ip)
-        cat4 = E(N, H // 8, W // 8, 3 * C3)
-        cat5 = E(N, H // 16, W // 16, 3 * C4)
-        skip5 = E(N, H // 32, W // 32, 2 * C5)
-        e1, e2 = cat2[..., 2 * ip:], cat3[..., 4 * ip:]
-        e3, e4, e5 = cat4[..., 2 * C3:], cat5[..., 2 * C4:], skip5[..., C5:]
-        r1 = self.double_fwd(m.enc_layer1, p0, e1, training, dt)
-        r2 = self.double_fwd(m.enc_layer2, e1, e2, training, dt)
-        r3 = self.double_fwd(m.enc_layer3, e2, e3, training, dt)
-        r4 = self.double_fwd(m.enc_layer4, e3, e4, training, dt)
-        r5 = self.double_fwd(m.enc_layer5, e4, e5, training, dt)
-        a3 = self.aspp_level_fwd(m.ASPP_layer_enc3, m.ASPP_combine_enc3, e3, cat4[..., C3:2 * C3], arena, offs[0], training, dt)
-        a4 = self.aspp_level_fwd(m.ASPP_layer_enc4, m.ASPP_combine_enc4, e4, cat5[..., C4:2 * C4], arena, offs[1], training, dt)
-        a5 = self.aspp_level_fwd(m.ASPP_layer_enc5, m.ASPP_combine_enc5, e5, skip5[..., :C5], arena, offs[2], training, dt)
-
-        d5o = E(N, H // 16, W // 16, 32 * ip)
-        d5 = self.declayer_fwd(m.dec_layer5, skip5, cat5, C4, d5o, training, dt,
-                               xf_x=self._arena_affine(arena, offs[5], 2 * C5), xf_cat=self._arena_affine(arena, offs[4], 3 * C4))
-        d4o = E(N, H // 8, W // 8, 16 * ip)
-        d4 = self.declayer_fwd(m.dec_layer4, d5o, cat4, C3, d4o, training, dt, xf_cat=self._arena_affine(arena, offs[3], 3 * C3))
-        d3o = E(N, H // 4, W // 4, 4 * ip)
-        d3 = self.declayer_fwd(m.dec_layer3, d4o, cat3, 4 * ip, d3o, training, dt)
-        d2o = E(N, H // 2, W // 2, 2 * ip)
-        d2 = self.declayer_fwd(m.dec_layer2, d3o, cat2, 2 * ip, d2o, training, dt)
-        d1o = E(N, H, W, ip)
-        d1 = self.declayer_fwd(m.dec_layer1, d2o, cat1, ip, d1o, training, dt)
-        c10, out = self.head_fwd(m, d1o, training, dt)
-        if not save:
-            return out, None
-        sv.x, sv.x16, sv.c0, sv.amax = x, x16, c0, amax
-        sv.enc, sv.aspp, sv.dec = (r1, r2, r3, r4, r5), (a3, a4, a5), (d1, d2, d3, d4, d5)
-        sv.d1o, sv.c10, sv.out, sv.dt = d1o, c10, out.detach(), dt     # (an alias without grad_fn: autograd attaches the node to `out` itself, and node -> ctx -> sv -> out would be a cycle)
-        return out, sv
+        cats, skip5, enc, posts = self._aspp_buffers(x, dt)
+        p0 = self.stem_pool_fwd(m, x, cats[0], training, dt, sv)
+        sv.enc = self.encoder_fwd(m, p0, enc, training, dt)
+        sv.aspp = tuple(self.aspp_level_fwd(layer, post, e, cpost, arena, o_acat, training, dt)
+                        for (layer, post), e, cpost, o_acat in zip(levels, enc[2:], posts, offs[:3]))
+        xf = {5: (self._arena_affine(arena, offs[5], 2 * C5), self._arena_affine(arena, offs[4], 3 * C4)),
+              4: (None, self._arena_affine(arena, offs[3], 3 * C3))}
+        d1o, sv.dec = self.decoder_fwd(m, skip5, cats, training, dt, xf)
+        out = self.head_fwd(m, d1o, training, dt, sv)
+        return out, (sv if save else None)
 
     def aspp_backward(self, sv, g_logp, grad_ready=None):
         m = self.model
-        dt, dev = sv.dt, sv.x.device
-        self._rebind(sv)
-        self._pack_bwd(dt, dev)
-        flat, views = self._grad_views(dev)
-        G = lambda p: views[id(p)]
-        stage_done = self._stage_notifier(flat, grad_ready)
-        self._side_begin(dev)
-        self._red_begin(dev)
-        N, ncls, H, W = sv.out.shape
+        flat, views, G, stage_done = self._backward_begin(sv, grad_ready)
         ip = m.inplanes
         C3, C4, C5 = 8 * ip, 16 * ip, 32 * ip
-        if not g_logp.is_contiguous():
-            g_logp = g_logp.contiguous()
         g = self.head_bwd(m, sv, g_logp, G); stage_done(m.bn10.bias)
-        d1, d2, d3, d4, d5 = sv.dec
-        g, gc1 = self.declayer_bwd(d1, g, G); stage_done(m.dec_layer1.deconv.weight)
-        g, gc2 = self.declayer_bwd(d2, g, G); stage_done(m.dec_layer2.deconv.weight)
-        g, gc3 = self.declayer_bwd(d3, g, G); stage_done(m.dec_layer3.deconv.weight)
-        g, gc4 = self.declayer_bwd(d4, g, G); stage_done(m.dec_layer4.deconv.weight)
-        gs5, gc5 = self.declayer_bwd(d5, g, G); stage_done(m.dec_layer5.deconv.weight)
-        r1, r2, r3, r4, r5 = sv.enc
+        gs5, gc = self.decoder_bwd(m, sv, g, G, stage_done)
         a3, a4, a5 = sv.aspp
+        # an ASPP level's backward turns [gradient of its post conv's output | gradient of the direct skip] into the level's g_e
         g_e5 = self.aspp_level_bwd(a5, gs5[..., :C5], gs5[..., C5:], G)
-        g = self.double_bwd(r5, g_e5, None, G); stage_done(m.enc_layer5.res1.conv1.weight)
-        g_e4 = self.aspp_level_bwd(a4, gc5[..., C4:2 * C4], gc5[..., 2 * C4:], G)
-        g = self.double_bwd(r4, g, g_e4, G); stage_done(m.enc_layer4.res1.conv1.weight)
-        g_e3 = self.aspp_level_bwd(a3, gc4[..., C3:2 * C3], gc4[..., 2 * C3:], G)
-        g = self.double_bwd(r3, g, g_e3, G); stage_done(m.enc_layer3.res1.conv1.weight)
-        g = self.double_bwd(r2, g, gc3[..., 4 * ip:], G); stage_done(m.enc_layer2.res1.conv1.weight)
-        g = self.double_bwd(r1, g, gc2[..., 2 * ip:], G); stage_done(m.enc_layer1.res1.conv1.weight)
-        bn1 = self.bn(m.bn1)
-        g_x0 = self._new(sv.c0.shape, dtype=dt, device=dev)
-        ops.maxpool_bwd(sv.c0, self.relu_affine(bn1), g, gc1[..., ip:], g_x0, 2, argmax=sv.amax)
-        g_c0 = self._bn_bwd(bn1, g_x0, None, sv.c0, True, G, N * H * W)
-        self.stem_bwd(m.conv1, sv.x16, g_c0, G)
-        stage_done(self.grad_order[-1][1])
-        self._side_end(dev)
-        self._red_buf = None
-        return flat, views
-
-    # ------------------------------------------------------------------ UResNet
-    def uresnet_forward(self, x: torch.Tensor, training: bool, dt: torch.dtype, save: bool):
-        """training: BatchNorm modules in train mode use batch statistics (and update their running statistics), modules in eval
-        mode are frozen; training = False freezes every site.  save: keep activations for backward"""
-        m = self.model
-        self._save = save
-        L.require_cuda(x, "input")
-        if x.dtype != torch.float32:
-            raise RuntimeError("ubresnet_amd: input must be float32 NCHW (got %s)" % x.dtype)
-        if x.dim() != 4 or x.shape[1] != m.conv1.in_channels:
-            raise RuntimeError("ubresnet_amd: expected input [B,%d,H,W], got %s" % (m.conv1.in_channels, tuple(x.shape)))
-        N, Cin, H, W = x.shape
-        if H % 32 or W % 32:
-            raise RuntimeError("ubresnet_amd: H and W must be multiples of 32 (ConvTranspose2d output_size contract of the "
-                               "reference, models/common_layers.py:128); got %dx%d" % (H, W))
-        if not x.is_contiguous():
-            x = x.contiguous()
-        dev = x.device
-        ip = m.inplanes
-        sv = Saved()
-        self._alloc_pass_workspaces(sv, dev, training)
-        self.pack_all(dt, dev, "fwd")
-        if save:
-            self._pack_bwd_early(dt, dev)
-        E = lambda *shape: self._new(shape, dtype=dt, device=dev)
-
-        # stem: conv1 -> (bn1 + relu folded into consumers) -> pool ; x0 goes into dec1's concat buffer
-        bn1 = self.bn(m.bn1)
-        c0 = E(N, H, W, ip)
-        x16 = self.stem_fwd(m.conv1, x, c0, bn1.stats, dt)
-        self._finish_bn(bn1, N * H * W, training)
-        cat1 = E(N, H, W, 2 * ip)
-        p0 = E(N, H // 2, W // 2, ip)
-        amax = self._new((N, H // 2, W // 2, ip), dtype=torch.uint8, device=dev) if save else None   # window arg-max for the backward
-        ops.maxpool_fwd(c0, self.relu_affine(bn1), p0, cat1[..., ip:], 2, argmax=amax)
-
-        # encoder: each level's output is written into the skip half of the matching concat buffer
-        cat2 = E(N, H // 2, W // 2, 4 * ip)
-        cat3 = E(N, H // 4, W // 4, 8 * ip)
-        cat4 = E(N, H // 8, W // 8, 16 * ip)
-        cat5 = E(N, H // 16, W // 16, 32 * ip)
-        x5 = E(N, H // 32, W // 32, 32 * ip)
-        x1, x2, x3, x4 = cat2[..., 2 * ip:], cat3[..., 4 * ip:], cat4[..., 8 * ip:], cat5[..., 16 * ip:]
-        e1 = self.double_fwd(m.enc_layer1, p0, x1, training, dt)
-        e2 = self.double_fwd(m.enc_layer2, x1, x2, training, dt)
-        e3 = self.double_fwd(m.enc_layer3, x2, x3, training, dt)
-        e4 = self.double_fwd(m.enc_layer4, x3, x4, training, dt)
-        e5 = self.double_fwd(m.enc_layer5, x4, x5, training, dt)
-
-        d5o = E(N, H // 16, W // 16, 16 * ip)
-        d5 = self.declayer_fwd(m.dec_layer5, x5, cat5, 16 * ip, d5o, training, dt)
-        d4o = E(N, H // 8, W // 8, 8 * ip)
-        d4 = self.declayer_fwd(m.dec_layer4, d5o, cat4, 8 * ip, d4o, training, dt)
-        d3o = E(N, H // 4, W // 4, 4 * ip)
-        d3 = self.declayer_fwd(m.dec_layer3, d4o, cat3, 4 * ip, d3o, training, dt)
-        d2o = E(N, H // 2, W // 2, 2 * ip)
-        d2 = self.declayer_fwd(m.dec_layer2, d3o, cat2, 2 * ip, d2o, training, dt)
-        d1o = E(N, H, W, ip)
-        d1 = self.declayer_fwd(m.dec_layer1, d2o, cat1, ip, d1o, training, dt)
-
-        # head: conv10 + bias -> bn10 -> relu -> conv11 + bias -> log-softmax (fused epilogue, NCHW fp32)
-        bn10 = self.bn(m.bn10)
-        nk = m.conv10.out_channels
-        c10 = E(N, H, W, nk)
-        ops.conv(d1o, self.packed(m.conv10.weight, dt, "fwd"), c10, T7, nk, bias=m.conv10.bias, stats=bn10.stats)
-        self._finish_bn(bn10, N * H * W, training)
-        ncls = m.conv11.out_channels
-        out = self._final_logsoftmax(m, c10, self.packed(m.conv11.weight, dt, "fwd"), self.relu_affine(bn10), (N, ncls, H, W))
-        if not save:
-            return out, None
-        sv.x, sv.x16, sv.c0, sv.cat1, sv.p0, sv.amax = x, x16, c0, cat1, p0, amax
-        sv.enc = (e1, e2, e3, e4, e5)
-        sv.dec = (d1, d2, d3, d4, d5)
-        sv.cats = (cat1, cat2, cat3, cat4, cat5)
-        sv.d1o, sv.c10, sv.out, sv.dt = d1o, c10, out.detach(), dt     # (an alias without grad_fn: autograd attaches the node to `out` itself, and node -> ctx -> sv -> out would be a cycle)
-        return out, sv
-
-    def uresnet_backward(self, sv: Saved, g_logp: torch.Tensor, grad_ready: Optional[Callable] = None):
-        """-> flat fp32 gradient buffer (layout self.grad_offsets)."""
-        m = self.model
-        dt = sv.dt
-        dev = sv.x.device
-        self._rebind(sv)
-        self._pack_bwd(dt, dev)
-        flat, views = self._grad_views(dev)
-        G = lambda p: views[id(p)]
-        stage_done = self._stage_notifier(flat, grad_ready)
-        self._side_begin(dev)
-        self._red_begin(dev)
-
-        N, ncls, H, W = sv.out.shape
-        ip = m.inplanes
-        if not g_logp.is_contiguous():
-            g_logp = g_logp.contiguous()
-        # ---- head ----
-        g_l = self._new((N, H, W, 16), dtype=dt, device=dev)
-        self._logsoftmax_bwd(g_logp, sv.out, g_l)
-        bn10 = self.bn(m.bn10)
-        nk = m.conv10.out_channels
-        self._wg(sv.c10, g_l, T7, G(m.conv11.weight), nk * 49, 49, ncls, nk, self.wws, xf=self.relu_affine(bn10))
-        NS = L.STAT_SLOTS
-        red = self._red(16 + nk, dev)
-        ops.channel_sum(g_l, red[:16 * NS])
-        ops.cast_f64_to_f32(red[:16 * NS], G(m.conv11.bias), ncls, stride=16)
-        g_a10 = self._new((N, H, W, nk), dtype=dt, device=dev)
-        # data gradient of conv11: K = the 16 (zero-padded) logit channels
-        wp = self._packed_dgrad_padded(m.conv11.weight, dt)
-        red10 = self._red(2 * nk, dev) if _BNB_FUSE else None
-        ops.conv(g_l, wp, g_a10, DG7, nk, bnb=(sv.c10, bn10.mean, bn10.scale, bn10.shift, bn10.invstd) if _BNB_FUSE else None, stats=red10)
-        del g_l
-        g_c10 = self._bn_bwd(bn10, g_a10, None, sv.c10, True, G, N * H * W, red=red10)
-        del g_a10
-        self._wg(sv.d1o, g_c10, T7, G(m.conv10.weight), ip * 49, 49, nk, ip, self.wws)
-        ops.channel_sum(g_c10, red[16 * NS:])
-        ops.cast_f64_to_f32(red[16 * NS:], G(m.conv10.bias), nk)
-        g = self._new(sv.d1o.shape, dtype=dt, device=dev)
-        self._conv_dgrad(m.conv10, g_c10, g, 1, k=7)
-        del g_c10
-        stage_done(m.bn10.bias)
-        # ---- decoder ----
-        d1, d2, d3, d4, d5 = sv.dec
-        g, gc1 = self.declayer_bwd(d1, g, G); stage_done(m.dec_layer1.deconv.weight)
-        g, gc2 = self.declayer_bwd(d2, g, G); stage_done(m.dec_layer2.deconv.weight)
-        g, gc3 = self.declayer_bwd(d3, g, G); stage_done(m.dec_layer3.deconv.weight)
-        g, gc4 = self.declayer_bwd(d4, g, G); stage_done(m.dec_layer4.deconv.weight)
-        g, gc5 = self.declayer_bwd(d5, g, G); stage_done(m.dec_layer5.deconv.weight)
-        # ---- encoder (skip gradients arrive through the concat buffers' second halves) ----
-        e1, e2, e3, e4, e5 = sv.enc
-        g = self.double_bwd(e5, g, None, G); stage_done(m.enc_layer5.res1.conv1.weight)
-        g = self.double_bwd(e4, g, gc5[..., 16 * ip:], G); stage_done(m.enc_layer4.res1.conv1.weight)
-        g = self.double_bwd(e3, g, gc4[..., 8 * ip:], G); stage_done(m.enc_layer3.res1.conv1.weight)
-        g = self.double_bwd(e2, g, gc3[..., 4 * ip:], G); stage_done(m.enc_layer2.res1.conv1.weight)
-        g = self.double_bwd(e1, g, gc2[..., 2 * ip:], G); stage_done(m.enc_layer1.res1.conv1.weight)
-        # ---- stem ----
-        bn1 = self.bn(m.bn1)
-        g_x0 = self._new(sv.c0.shape, dtype=dt, device=dev)
-        ops.maxpool_bwd(sv.c0, self.relu_affine(bn1), g, gc1[..., ip:], g_x0, 2, argmax=sv.amax)
-        g_c0 = self._bn_bwd(bn1, g_x0, None, sv.c0, True, G, N * H * W)
-        self.stem_bwd(m.conv1, sv.x16, g_c0, G)
-        stage_done(self.grad_order[-1][1])
-        self._side_end(dev)
-        self._red_buf = None
+        owed = [gc[1][..., 2 * ip:], gc[2][..., 4 * ip:],
+                lambda: self.aspp_level_bwd(a3, gc[3][..., C3:2 * C3], gc[3][..., 2 * C3:], G),
+                lambda: self.aspp_level_bwd(a4, gc[4][..., C4:2 * C4], gc[4][..., 2 * C4:], G), None]
+        g = self.encoder_bwd(m, sv, g_e5, owed, G, stage_done)
+        self.stem_pool_bwd(m, sv, g, gc[0][..., ip:], G)
+        self._backward_end(sv, stage_done)
         return flat, views
 
     # ------------------------------------------------------------------ inference schedule (UResNet and ASPP_ResNet, eval mode)
@@ -1175,7 +1084,6 @@ class Engine:
     # launches and the raw conv2 / bypass outputs of the training schedule disappear (201 M instead of 250 M elements
     # per 512x512 image).  Reference call sites: deploy/run_ubresnet_precropped.py:88-89,147 (model.eval(); forward).
     def _infer_plan(self, dt, device):
-        import struct
         m = self.model
         key = ("inf", dt, device)
         ptrs = tuple(p.data_ptr() for _, p in self.grad_order) + tuple(b.data_ptr() for b in m.buffers())
@@ -1223,67 +1131,40 @@ class Engine:
             for conv, _, kk, _ in lay.branches():
                 branch_dst[id(conv.weight)] = front[t0:t0 + kk * kk]
                 t0 += kk * kk
-        images, pack_tbl, n = {}, b"", 0
-        for group, k, w, soff, M, Kv, Kpad, sm, sk, ntaps, tstride in self._plan_items():
-            if group != "fwd":
-                continue
-            if not w.is_contiguous() or w.dtype != torch.float32 or w.device != device:
-                raise RuntimeError("ubresnet_amd: parameters must be contiguous float32 on %s" % device)
-            Mpad = (M + 15) // 16 * 16
-            Kp = Kpad if Kpad is not None else (Kv + cpu - 1) // cpu * cpu
-            dst = branch_dst.get(id(w))
-            if dst is None:
-                dst = self._new((ntaps, Kp // cpu, Mpad, cpu), dtype=dt, device=device)
-            elif tuple(dst.shape) != (ntaps, Kp // cpu, Mpad, cpu):
-                raise RuntimeError("ubresnet_amd: ASPP branch image %s does not fit its slot %s" % ((ntaps, Kp // cpu, Mpad, cpu), tuple(dst.shape)))
-            images[k] = dst
-            sc = scale_of.get(id(w))
-            pack_tbl += struct.pack("<QQqqqQiiiiii", w.data_ptr() + 4 * soff, dst.data_ptr(), sm, sk, tstride,
-                                    sc.data_ptr() if sc is not None else 0, M, Mpad, Kv, Kp // cpu, ntaps, 0)
-            n += 1
-        dev_tbl = lambda b: torch.frombuffer(bytearray(b), dtype=torch.uint8).to(device)
-        plan = {"ptrs": ptrs, "images": images, "bias": bias_of, "vec": vec, "fold": dev_tbl(fold_tbl), "nfold": len(pairs),
-                "pack": dev_tbl(pack_tbl), "npack": n, "front_img": front_img, "front_bias": front_bias}
+        images, tables, counts = self._image_tables(dt, device, ("fwd",), scale_of=scale_of, slot_of=branch_dst)
+        plan = {"ptrs": ptrs, "images": images, "bias": bias_of, "vec": vec, "fold": self._device_table(fold_tbl, device), "nfold": len(pairs),
+                "pack": self._device_table(tables["fwd"], device), "npack": counts["fwd"], "front_img": front_img, "front_bias": front_bias}
         self._plans[key] = plan
         return plan
 
-    def _block_infer(self, blk, x, out, img, fb, dt):
+    def _block_infer(self, blk, x, out, fb, dt):
         """BasicBlock.forward (models/common_layers.py:39-58) with folded BatchNorms: 2 launches (3 with a bypass conv)"""
         N, OH, OW, Cout = out.shape
         S = blk.stride
         c1 = self._new((N, OH, OW, Cout), dtype=dt, device=x.device)
-        ops.conv(x, img[(id(blk.conv1.weight), "fwd")], c1, T3, Cout, S=S, bias=fb[id(blk.bn1)], act=1)
+        ops.conv(x, self.packed(blk.conv1.weight, "fwd"), c1, T3, Cout, S=S, bias=fb[id(blk.bn1)], act=1)
         sc = x
         if blk.bypass is not None:
             sc = self._new((N, OH, OW, Cout), dtype=dt, device=x.device)
-            ops.conv(x, img[(id(blk.bypass.weight), "fwd")], sc, T1, Cout, S=S, bias=fb[id(blk.bnpass)])
-        ops.conv(c1, img[(id(blk.conv2.weight), "fwd")], out, T3, Cout, bias=fb[id(blk.bn2)], addend=sc, act=3)
+            ops.conv(x, self.packed(blk.bypass.weight, "fwd"), sc, T1, Cout, S=S, bias=fb[id(blk.bnpass)])
+        ops.conv(c1, self.packed(blk.conv2.weight, "fwd"), out, T3, Cout, bias=fb[id(blk.bn2)], addend=sc, act=3)
 
-    def _double_infer(self, dbl, x, out, img, fb, dt):
+    def _double_infer(self, dbl, x, out, fb, dt):
         mid = self._new(out.shape, dtype=dt, device=x.device)
-        self._block_infer(dbl.res1, x, mid, img, fb, dt)
-        self._block_infer(dbl.res2, mid, out, img, fb, dt)
+        self._block_infer(dbl.res1, x, mid, fb, dt)
+        self._block_infer(dbl.res2, mid, out, fb, dt)
 
-    def _declayer_infer(self, dl, x, cat, Cd, out, img, fb, dt):
-        wp = img[(id(dl.deconv.weight), "tfwd")]
-        up = cat[..., :Cd]
-        if Cd >= _PHASE_MIN_C:
-            ops.conv_phases(x, wp, _phase(up, 0, 0), _PH4[1], Cd, phases=_PH4[0], y_full=up)
-        else:
-            for ry in range(2):
-                for rx in range(2):
-                    ops.conv(x, wp, _phase(up, ry, rx), ops.transposed_phase_taps(4, 1, 1, 2, ry, rx), Cd)
-        self._double_infer(dl.res, cat, out, img, fb, dt)
-
-    def _infer_begin(self, dt, dev):
-        """fold every BatchNorm and repack every forward image for this pass (two launches) -> the inference plan"""
-        plan = self._infer_plan(dt, dev)
+    def _infer_begin(self, x, dt):
+        """fold every BatchNorm and repack every forward image for this pass (two launches) -> (checked input, inference plan)"""
+        x = self._check_input(x, self.model.conv1.in_channels)
+        plan = self._infer_plan(dt, x.device)
         st = L.stream_ptr()
         L.check(L.lib().ubr_bn_fold_batched(plan["fold"].data_ptr(), plan["nfold"], st), "bn_fold_batched")
         L.check(L.lib().ubr_pack_weights_batched(L.dtype_id(dt), plan["pack"].data_ptr(), plan["npack"], st), "pack_weights_batched")
-        return plan
+        self._images = plan["images"]
+        return x, plan
 
-    def _stem_infer(self, m, x, cat1, p0, img, fb, dt):
+    def _stem_infer(self, m, x, cat1, fb, dt):
         """conv1 (+bn1 folded, ReLU in the epilogue) writes x0 straight into dec1's concat buffer; the pool reads it"""
         N, Cin, H, W = x.shape
         ip = m.inplanes
@@ -1293,17 +1174,33 @@ class Engine:
         if self._rec is not None:
             self._rec.pre = lambda xx: ops.stem_expand(xx, x16)
         for ci in range(Cin):
-            ops.conv(x16[..., 16 * ci:16 * ci + 16], img[(id(m.conv1.weight), "stem%d" % ci)], x0, self.STEM_TAPS, ip,
+            ops.conv(x16[..., 16 * ci:16 * ci + 16], self.packed(m.conv1.weight, "stem%d" % ci), x0, self.STEM_TAPS, ip,
                      bias=fb[id(m.bn1)] if ci == 0 else None, addend=x0 if ci > 0 else None, act=2 if ci == Cin - 1 else 0)
+        p0 = self._new((N, H // 2, W // 2, ip), dtype=dt, device=x.device)
         ops.maxpool_fwd(x0, None, p0, None, 2)
+        return p0
 
-    def _head_infer(self, m, d1o, img, fb, dt):
+    def _encoder_infer(self, m, x, outs, fb, dt):
+        for i, out in enumerate(outs, 1):
+            self._double_infer(getattr(m, "enc_layer%d" % i), x, out, fb, dt)
+            x = out
+
+    def _decoder_infer(self, m, x, cats, fb, dt):
+        for i in (5, 4, 3, 2, 1):
+            dl, cat = getattr(m, "dec_layer%d" % i), cats[i - 1]
+            out = self._new(tuple(cat.shape[:3]) + (dl.res.res2.conv2.out_channels,), dtype=dt, device=x.device)
+            self.deconv_fwd(dl, x, cat, dl.deconv.out_channels, dt)
+            self._double_infer(dl.res, cat, out, fb, dt)
+            x = out
+        return x
+
+    def _head_infer(self, m, d1o, fb, dt):
         N, H, W, _ = d1o.shape
         nk = m.conv10.out_channels
         c10 = self._new((N, H, W, nk), dtype=dt, device=d1o.device)
-        ops.conv(d1o, img[(id(m.conv10.weight), "fwd")], c10, T7, nk, bias=fb[id(m.bn10)], act=1)
+        ops.conv(d1o, self.packed(m.conv10.weight, "fwd"), c10, T7, nk, bias=fb[id(m.bn10)], act=1)
         ncls = m.conv11.out_channels
-        return self._final_logsoftmax(m, c10, img[(id(m.conv11.weight), "fwd")], None, (N, ncls, H, W))
+        return self._final_logsoftmax(m, c10, self.packed(m.conv11.weight, "fwd"), None, (N, ncls, H, W))
 
     def _aspp_level_infer(self, layer, post, e, cpost, plan, dt):
         """ASPP.forward + ASPP_post.forward (models/ASPP_ResNet.py:227-263,280-286), BatchNorms folded: the five branches in
@@ -1311,82 +1208,29 @@ class Engine:
         N, h, w, Cn = e.shape
         acat = self._new((N, h, w, 64 + Cn), dtype=dt, device=e.device)
         ops.aspp_front(e, plan["front_img"][id(layer)], plan["front_bias"][id(layer)], acat)
-        ops.conv(acat, plan["images"][(id(post.ASPP_conv.weight), "fwd")], cpost, T1, Cn, bias=plan["bias"][id(post.ASPP_bn)], act=1)
+        ops.conv(acat, self.packed(post.ASPP_conv.weight, "fwd"), cpost, T1, Cn, bias=plan["bias"][id(post.ASPP_bn)], act=1)
+
+    def uresnet_infer(self, x, dt):
+        """eval-mode UResNet.forward (models/ub_uresnet.py:88-147), nothing saved; buffer layout of uresnet_forward"""
+        m = self.model
+        x, plan = self._infer_begin(x, dt)
+        fb = plan["bias"]
+        cats, x5, enc = self._uresnet_buffers(x, dt)
+        p0 = self._stem_infer(m, x, cats[0], fb, dt)
+        self._encoder_infer(m, p0, enc, fb, dt)
+        return self._head_infer(m, self._decoder_infer(m, x5, cats, fb, dt), fb, dt)
 
     def aspp_infer(self, x, dt):
         """eval-mode ASPP_ResNet.forward (models/ASPP_ResNet.py:416-523), nothing saved; buffer layout of aspp_forward"""
         m = self.model
-        x = self._check_input(x, m.conv1.in_channels)
-        N, Cin, H, W = x.shape
-        dev, ip = x.device, m.inplanes
-        plan = self._infer_begin(dt, dev)
-        img, fb = plan["images"], plan["bias"]
-        E = lambda *shape: self._new(shape, dtype=dt, device=dev)
-        C3, C4, C5 = 8 * ip, 16 * ip, 32 * ip
-        cat1 = E(N, H, W, 2 * ip)
-        p0 = E(N, H // 2, W // 2, ip)
-        self._stem_infer(m, x, cat1, p0, img, fb, dt)
-        cat2 = E(N, H // 2, W // 2, 4 * ip)
-        cat3 = E(N, H // 4, W // 4, 8 * ip)
-        cat4 = E(N, H // 8, W // 8, 3 * C3)           # [deconv | ASPP_post(e3) | e3]
-        cat5 = E(N, H // 16, W // 16, 3 * C4)         # [deconv | ASPP_post(e4) | e4]
-        skip5 = E(N, H // 32, W // 32, 2 * C5)        # [ASPP_post(e5) | e5]
-        e1, e2 = cat2[..., 2 * ip:], cat3[..., 4 * ip:]
-        e3, e4, e5 = cat4[..., 2 * C3:], cat5[..., 2 * C4:], skip5[..., C5:]
-        self._double_infer(m.enc_layer1, p0, e1, img, fb, dt)
-        self._double_infer(m.enc_layer2, e1, e2, img, fb, dt)
-        self._double_infer(m.enc_layer3, e2, e3, img, fb, dt)
-        self._double_infer(m.enc_layer4, e3, e4, img, fb, dt)
-        self._double_infer(m.enc_layer5, e4, e5, img, fb, dt)
-        self._aspp_level_infer(m.ASPP_layer_enc3, m.ASPP_combine_enc3, e3, cat4[..., C3:2 * C3], plan, dt)
-        self._aspp_level_infer(m.ASPP_layer_enc4, m.ASPP_combine_enc4, e4, cat5[..., C4:2 * C4], plan, dt)
-        self._aspp_level_infer(m.ASPP_layer_enc5, m.ASPP_combine_enc5, e5, skip5[..., :C5], plan, dt)
-        d5o = E(N, H // 16, W // 16, 32 * ip)
-        self._declayer_infer(m.dec_layer5, skip5, cat5, C4, d5o, img, fb, dt)
-        d4o = E(N, H // 8, W // 8, 16 * ip)
-        self._declayer_infer(m.dec_layer4, d5o, cat4, C3, d4o, img, fb, dt)
-        d3o = E(N, H // 4, W // 4, 4 * ip)
-        self._declayer_infer(m.dec_layer3, d4o, cat3, 4 * ip, d3o, img, fb, dt)
-        d2o = E(N, H // 2, W // 2, 2 * ip)
-        self._declayer_infer(m.dec_layer2, d3o, cat2, 2 * ip, d2o, img, fb, dt)
-        d1o = E(N, H, W, ip)
-        self._declayer_infer(m.dec_layer1, d2o, cat1, ip, d1o, img, fb, dt)
-        return self._head_infer(m, d1o, img, fb, dt)
-
-    def uresnet_infer(self, x, dt):
-        """eval-mode UResNet.forward (models/ub_uresnet.py:88-147), nothing saved"""
-        m = self.model
-        x = self._check_input(x, m.conv1.in_channels)
-        N, Cin, H, W = x.shape
-        dev, ip = x.device, m.inplanes
-        plan = self._infer_begin(dt, dev)
-        img, fb = plan["images"], plan["bias"]
-        E = lambda *shape: self._new(shape, dtype=dt, device=dev)
-        cat1 = E(N, H, W, 2 * ip)
-        p0 = E(N, H // 2, W // 2, ip)
-        self._stem_infer(m, x, cat1, p0, img, fb, dt)
-        cat2 = E(N, H // 2, W // 2, 4 * ip)
-        cat3 = E(N, H // 4, W // 4, 8 * ip)
-        cat4 = E(N, H // 8, W // 8, 16 * ip)
-        cat5 = E(N, H // 16, W // 16, 32 * ip)
-        x5 = E(N, H // 32, W // 32, 32 * ip)
-        x1, x2, x3, x4 = cat2[..., 2 * ip:], cat3[..., 4 * ip:], cat4[..., 8 * ip:], cat5[..., 16 * ip:]
-        self._double_infer(m.enc_layer1, p0, x1, img, fb, dt)
-        self._double_infer(m.enc_layer2, x1, x2, img, fb, dt)
-        self._double_infer(m.enc_layer3, x2, x3, img, fb, dt)
-        self._double_infer(m.enc_layer4, x3, x4, img, fb, dt)
-        self._double_infer(m.enc_layer5, x4, x5, img, fb, dt)
-        d5o = E(N, H // 16, W // 16, 16 * ip)
-        self._declayer_infer(m.dec_layer5, x5, cat5, 16 * ip, d5o, img, fb, dt)
-        d4o = E(N, H // 8, W // 8, 8 * ip)
-        self._declayer_infer(m.dec_layer4, d5o, cat4, 8 * ip, d4o, img, fb, dt)
-        d3o = E(N, H // 4, W // 4, 4 * ip)
-        self._declayer_infer(m.dec_layer3, d4o, cat3, 4 * ip, d3o, img, fb, dt)
-        d2o = E(N, H // 2, W // 2, 2 * ip)
-        self._declayer_infer(m.dec_layer2, d3o, cat2, 2 * ip, d2o, img, fb, dt)
-        d1o = E(N, H, W, ip)
-        self._declayer_infer(m.dec_layer1, d2o, cat1, ip, d1o, img, fb, dt)
-        return self._head_infer(m, d1o, img, fb, dt)
+        x, plan = self._infer_begin(x, dt)
+        fb = plan["bias"]
+        cats, skip5, enc, posts = self._aspp_buffers(x, dt)
+        p0 = self._stem_infer(m, x, cats[0], fb, dt)
+        self._encoder_infer(m, p0, enc, fb, dt)
+        for (layer, post), e, cpost in zip(self._aspp_levels(), enc[2:], posts):
+            self._aspp_level_infer(layer, post, e, cpost, plan, dt)
+        return self._head_infer(m, self._decoder_infer(m, skip5, cats, fb, dt), fb, dt)
 
     # ------------------------------------------------------------------ dispatch
     def forward(self, x, training, dt, save):

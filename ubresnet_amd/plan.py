@@ -20,12 +20,15 @@ capture.  Everything else takes the ordinary schedule, which stays the reference
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
 import torch
 
 from . import _lib as L
+from . import ops
+from .engine import wgrad_stream_enabled
 
 ENABLED = os.environ.get("UBR_PLAN", "1") != "0"
 MAX_PLANS = 4
@@ -186,13 +189,28 @@ def _signature(model):
 
 def _streams(eng, dev):
     main = L.stream_ptr()
-    if eng.side is not None and os.environ.get("UBR_WGRAD_STREAM", "1") != "0":
+    if eng.side is not None and wgrad_stream_enabled():
         return [main, eng.side.cuda_stream]
     return [main]
 
 
+@contextlib.contextmanager
+def recording(eng, streams):
+    """record the eager pass run inside the block onto a new tape: the engine pins its buffers to the Recording, the
+    operators label their launches on it"""
+    rec = Recording(len(streams))
+    eng._rec = rec
+    rec.tape.begin(streams)
+    ops._rec_sink = rec
+    try:
+        yield rec
+    finally:
+        ops._rec_sink = None
+        eng._rec = None
+        rec.tape.end()
+
+
 def usable(eng, x) -> bool:
-    from . import ops
     return (ENABLED and eng.kind in ("uresnet", "aspp") and x.is_cuda and (ops._prof is None or TIMED is not None)
             and not torch.cuda.is_current_stream_capturing())
 
@@ -202,7 +220,7 @@ def forward(eng, x, training, dt, save):
     if not usable(eng, x):
         return eng.forward_eager(x, training, dt, save)
     dev = x.device
-    if os.environ.get("UBR_WGRAD_STREAM", "1") != "0":
+    if wgrad_stream_enabled():
         eng._ensure_side(dev)
     # (the frozen pattern of the BatchNorm sites, not just the flag: a tape bakes in which launches each site got)
     key = (tuple(x.shape), dt, bool(training), eng.frozen_pattern(training), bool(save), dev.index)
@@ -225,17 +243,8 @@ def forward(eng, x, training, dt, save):
                 return eng.forward_eager(x, training, dt, save)
             del eng._planned[min(victims, key=lambda k: eng._planned[k].uses)]
         plan = PlannedPass(key, sig)
-        rec = Recording(len(streams))
-        eng._rec = rec
-        rec.tape.begin(streams)
-        from . import ops
-        ops._rec_sink = rec
-        try:
+        with recording(eng, streams) as rec:
             out, sv = eng.forward_eager(x, training, dt, save)
-        finally:
-            ops._rec_sink = None
-            eng._rec = None
-            rec.tape.end()
         plan.fwd, plan.sv = rec, sv
         eng._planned[key] = plan
     else:
@@ -276,17 +285,8 @@ def backward(eng, sv, g_out, grad_ready, allow_plan=True):
         if plan.bwd is None:
             if len(streams) != plan.fwd.nstreams:
                 return eng.backward_eager(sv, g_out, grad_ready)
-            rec = Recording(len(streams))
-            eng._rec = rec
-            rec.tape.begin(streams)
-            from . import ops
-            ops._rec_sink = rec
-            try:
+            with recording(eng, streams) as rec:
                 flat, views = eng.backward_eager(sv, g_out, grad_ready)
-            finally:
-                ops._rec_sink = None
-                eng._rec = None
-                rec.tape.end()
             plan.bwd, plan.flat, plan.views = rec, flat, views
             return flat, views
         if not g_out.is_contiguous():
