@@ -568,6 +568,28 @@ def apply_ref(gy, xhat, scale, k1, k2):
     return _vec(scale, gy) * (gy - _vec(k1, gy) - xhat * _vec(k2, gy))
 
 
+def bn_bwd_frozen_ref(ga, ga2, c, scale, shift, mean, invstd, relu):
+    """backward through a = relu(bn(c)) (or bn(c)) at a FROZEN site -- mean / invstd are constants of the pass, so no sum stands
+    between the incoming gradient and the data gradient:  g_c = scale * g_y,  dbeta = sum g_y,  dgamma = sum g_y * xhat.
+    -> (g_c fp64 NHWC, (dbeta, sum |terms|), (dgamma, sum |terms|)), the sums fp64 [C]"""
+    gy, xh = bn_bwd_ref(ga, ga2, c, scale, shift, mean, invstd, relu)
+    s, sx, a1, a2 = reduce_ref(gy, xh)
+    return _vec(scale, gy) * gy, (s, a1), (sx, a2)
+
+
+def tail_bwd_frozen_ref(go, go2, positive, c2, scale2, shift2, mean2, invstd2, cb=None, scale_b=None, mean_b=None, invstd_b=None):
+    """backward of a block tail out = relu(relu(bn2(c2)) + shortcut) whose BatchNorm sites are all frozen; positive = [out > 0]:
+        g_z = (go + go2) * positive,   g_y2 = g_z * [bn2(c2) > 0],   g_c2 = scale2 * g_y2,   dbeta2 = sum g_y2,  dgamma2 = sum g_y2 * xhat2
+        bypass block (shortcut = bnpass(cb)): g_sc = scale_b * g_z,  dbeta_b = sum g_z,  dgamma_b = sum g_z * xhat_b;   identity: g_sc = g_z
+    -> (g_c2, g_sc, [(dbeta2, abs), (dgamma2, abs)], [(dbeta_b, abs), (dgamma_b, abs)] or None)"""
+    gz, gy2, xh2, xhb = tail_bwd_ref(go, go2, positive, c2, scale2, shift2, mean2, invstd2, cb, mean_b, invstd_b)
+    s, sx, a1, a2 = reduce_ref(gy2, xh2)
+    if cb is None:
+        return _vec(scale2, gy2) * gy2, gz, [(s, a1), (sx, a2)], None
+    sb, sxb, b1, b2 = reduce_ref(gz, xhb)
+    return _vec(scale2, gy2) * gy2, _vec(scale_b, gz) * gz, [(s, a1), (sx, a2)], [(sb, b1), (sxb, b2)]
+
+
 def assert_sums_exact(got, ref, absref, unit, what=""):
     """a striped fp64 sum against its reference: asserts the budget (sum of |terms| of a channel < 2^24 units of the term grid:
     every fp32 partial of every summation order is then exact, see the note on the reduce passes at the top) and equality"""

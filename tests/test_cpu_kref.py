@@ -283,6 +283,91 @@ def test_bn_bwd_ref_equals_autograd(relu):
     assert torch.allclose(kref.apply_ref(gy, xh, gamma * inv, s / n, sx / n), c.grad, rtol=0, atol=1e-10)
 
 
+def _frozen_site(C, seed):
+    """a frozen site as the module holds it: running statistics (not the batch's), gamma / beta as autograd leaves"""
+    mean, var, gamma, beta, eps = _site(C, seed)
+    return mean, var, gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True), eps
+
+
+@pytest.mark.parametrize("two", [False, True])
+@pytest.mark.parametrize("relu", [False, True])
+def test_bn_bwd_frozen_ref_equals_autograd_through_eval_mode_batch_norm(relu, two):
+    """g_c = scale*g_y, dbeta = sum g_y, dgamma = sum g_y*xhat against autograd through F.batch_norm(training=False) (+ relu)"""
+    N, H, W, C = 2, 7, 13, 8
+    c = operands(N, C, H, W, 86, density=0.8, zero_tiles=0).requires_grad_(True)
+    ga = operands(N, C, H, W, 87, density=0.6, zero_tiles=0, exp=-1)
+    ga2 = operands(N, C, H, W, 88, density=0.6, zero_tiles=0, exp=-1) if two else None
+    mean, var, gamma, beta, eps = _frozen_site(C, 89)
+    f = c.detach().reshape(-1, C)
+    assert not torch.allclose(f.mean(0), mean) and not torch.allclose(f.var(0, unbiased=False), var)      # not the batch's statistics
+    y = F.batch_norm(nchw(c), mean, var, gamma, beta, False, 0.0, eps)
+    (F.relu(y) if relu else y).backward(nchw(ga + ga2 if two else ga))
+    inv = 1.0 / torch.sqrt(var + eps)
+    gc, (db, a1), (dg, a2) = kref.bn_bwd_frozen_ref(ga, ga2, c.detach(), gamma.detach() * inv, beta.detach(), mean, inv, relu)
+    assert torch.allclose(gc, c.grad, rtol=0, atol=1e-12)
+    assert torch.allclose(db, beta.grad, rtol=0, atol=1e-10) and torch.allclose(dg, gamma.grad, rtol=0, atol=1e-10)
+    assert bool((a1 >= db.abs()).all()) and bool((a2 >= dg.abs()).all())
+    assert bool((dg != db).any()) and bool((gc != 0).any())
+
+
+@pytest.mark.parametrize("two", [False, True])
+@pytest.mark.parametrize("byp", [False, True])
+def test_tail_bwd_frozen_ref_equals_autograd_through_eval_mode_batch_norm(byp, two):
+    """relu(relu(bn2(c2)) + shortcut), shortcut = bnpass(cb) or x, both sites frozen; the gate is the forward output's sign,
+    handed over as the mask bits the forward kernel would have stored"""
+    N, H, W, C = 2, 9, 11, 8
+    c2 = operands(N, C, H, W, 91, density=0.7, zero_tiles=0).requires_grad_(True)
+    sc = operands(N, C, H, W, 92, density=0.7, zero_tiles=0, exp=-1).requires_grad_(True)
+    go = operands(N, C, H, W, 93, density=0.6, zero_tiles=0, exp=-1)
+    go2 = operands(N, C, H, W, 94, density=0.6, zero_tiles=0, exp=-1) if two else None
+    mean2, var2, g2, b2, eps = _frozen_site(C, 95)
+    meanb, varb, gb, bb, _ = _frozen_site(C, 96)
+    bn2 = F.batch_norm(nchw(c2), mean2, var2, g2, b2, False, 0.0, eps)
+    sh = F.batch_norm(nchw(sc), meanb, varb, gb, bb, False, 0.0, eps) if byp else nchw(sc)
+    out = F.relu(F.relu(bn2) + sh)
+    out.backward(nchw(go + go2 if two else go))
+    i2, ib = 1.0 / torch.sqrt(var2 + eps), 1.0 / torch.sqrt(varb + eps)
+    s2, sb = g2.detach() * i2, gb.detach() * ib
+    positive = nhwc(out.detach()) > 0
+    bits = kref.mask_pack(positive, 8)
+    g_c2, g_sc, sums2, sumsb = kref.tail_bwd_frozen_ref(go, go2, kref.mask_unpack(bits, positive.shape, 8), c2.detach(), s2, b2.detach(),
+                                                        mean2, i2, sc.detach() if byp else None, sb if byp else None,
+                                                        meanb if byp else None, ib if byp else None)
+    assert torch.allclose(g_c2, c2.grad, rtol=0, atol=1e-12) and torch.allclose(g_sc, sc.grad, rtol=0, atol=1e-12)
+    (db2, a1), (dg2, a2) = sums2
+    assert torch.allclose(db2, b2.grad, rtol=0, atol=1e-10) and torch.allclose(dg2, g2.grad, rtol=0, atol=1e-10)
+    assert bool((a1 >= db2.abs()).all()) and bool((a2 >= dg2.abs()).all())
+    if byp:
+        (dbb, _), (dgb, _) = sumsb
+        assert torch.allclose(dbb, bb.grad, rtol=0, atol=1e-10) and torch.allclose(dgb, gb.grad, rtol=0, atol=1e-10)
+        assert bool((g_sc != go + go2 if two else g_sc != go).any())          # scale_b is in it
+    else:
+        assert sumsb is None and gb.grad is None
+
+
+def test_fault_frozen_dgamma_from_the_centred_input_or_an_unscaled_shortcut_is_caught():
+    """two slips a one-pass kernel can make without touching its sibling: sum g_y*(c - mean) in place of sum g_y*xhat, and a
+    bypass block's g_sc stored without scale_b"""
+    N, H, W, C = 2, 32, 32, 16
+    dt = torch.bfloat16
+    go = kref.exact_operands((N, H, W, C), dt, seed=131, density=0.5, zero_tiles=0.2, exp=-1)
+    c2 = kref.exact_operands((N, H, W, C), dt, seed=132, density=0.6, zero_tiles=0.2)
+    cb = kref.exact_operands((N, H, W, C), dt, seed=133, density=0.6, zero_tiles=0.2)
+    positive = kref.exact_operands((N, H, W, C), dt, seed=134, density=0.5, zero_tiles=0) > 0
+    m2, s2, t2, i2 = _vectors(_site(C, 135))
+    mb, sb, _, ib = _vectors(_site(C, 136))
+    assert bool((i2 != 1).any()) and bool((sb != 1).any())
+    g_c2, g_sc, [(db, a1), (dg, a2)], _ = kref.tail_bwd_frozen_ref(go, None, positive, c2, s2, t2, m2, i2, cb, sb, mb, ib)
+    kref.assert_sums_exact(dg, dg, a2, 0.25, "reference itself")
+    gz, gy2, _, _ = kref.tail_bwd_ref(go, None, positive, c2, s2, t2, m2, i2, cb, mb, ib)
+    wrong = (gy2 * (c2.double() - m2)).reshape(-1, C).sum(0)
+    with pytest.raises(AssertionError, match="channel"):
+        kref.assert_sums_exact(wrong, dg, a2, 0.25, "centred input")
+    kref.assert_exact(kref.round_to(g_sc, dt), g_sc, dt, g_sc.abs(), 2.0 ** -5, "reference itself")
+    with pytest.raises(AssertionError, match="differ"):
+        kref.assert_exact(kref.round_to(gz, dt), g_sc, dt, g_sc.abs(), 2.0 ** -5, "unscaled shortcut")
+
+
 def test_bn_finalize_ref_equals_batch_norm_training_statistics():
     N, H, W, C = 3, 8, 8, 6
     x = operands(N, C, H, W, 85, density=0.9, zero_tiles=0)

@@ -2,7 +2,8 @@
 tests/kref.py on exact operands (see kref's docstring): bit for bit where the budget holds, within a stated bound
 where it cannot.
 
-The four legs (the bench's headline train step, its ASPP leg, the inference leg, the fp32 train step) run once with
+The legs (the bench's headline train step, its ASPP leg, the inference leg, the fp32 train step, and three small steps through the
+frozen-BatchNorm schedule: every site frozen on the U-ResNet and on ASPP_ResNet, and a train-mode step with two frozen sites) run once with
 ops.conv / ops.conv_phases / ops.wgrad wrapped: every call is recorded -- tensor views (shape, strides, how they
 share storage), taps, flags, and the kernel variant that ran.  Each distinct call is then replayed on fresh exact
 operands, in buffers of the same layout and aliasing whose every element outside the views holds a NaN sentinel:
@@ -428,7 +429,7 @@ def _print_table(rows, capsys, title):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# the four legs
+# the legs
 # ------------------------------------------------------------------------------------------------------------------
 def _train_pass(model, x, lab, wgt):
     from ubresnet_amd.training.pixelwise_nllloss import PixelWiseNLLLoss
@@ -449,7 +450,22 @@ def _leg(name):
         m.compute_dtype = torch.float16
         x = torch.from_numpy(synthetic.make_batch(30, 512, 832, 5000)[0]).cuda()
         return lambda: _no_grad(m, x)
-    if name == "aspp":
+    if name in FROZEN_LEGS:
+        # small steps through the frozen-BatchNorm schedule: every site frozen (model.eval()), or two sites of a train-mode model,
+        # each leaving one block tail with sites in different modes (the mixed cases of test_gpu_frozen_bn.py, both at once)
+        if name == "frozen-aspp":
+            m = ASPP_ResNet(num_classes=3, in_channels=3, inplanes=16, showsizes=False).cuda().eval()
+            dt, (B, H, W, planes) = torch.bfloat16, (1, 64, 96, 3)
+        else:
+            m = UResNet(num_classes=3, input_channels=1, inplanes=16).cuda()
+            dt, (B, H, W, planes) = torch.bfloat16, (2, 128, 128, 1)
+            if name == "frozen":
+                m.eval()
+            else:
+                m.train()
+                m.enc_layer2.res1.bnpass.eval()
+                m.dec_layer3.res.res1.bn2.eval()
+    elif name == "aspp":
         m = ASPP_ResNet(num_classes=3, in_channels=3, inplanes=16, showsizes=False).cuda().train()
         dt, (B, H, W, planes) = torch.bfloat16, (16, 512, 832, 3)
     else:
@@ -466,12 +482,14 @@ def _no_grad(m, x):
     torch.cuda.synchronize()
 
 
+FROZEN_LEGS = ("frozen", "frozen-aspp", "mixed")
+
 # the kernel-variant switches are read once per process; with any of them set, other variants run than the ones named here
 _SWITCHED = any(os.environ.get(k) for k in ("UBR_WGRAD_PC", "UBR_CONV_PC", "UBR_CONV_THIN"))
 HEADLINE_VARIANTS = ("wgrad_kernel<bf16_t, 2, 4, 9, true, false, true>", "conv_pc_kernel", "conv_thin_kernel")
 
 
-@pytest.mark.parametrize("leg", ["headline", "aspp", "infer", "fp32"])
+@pytest.mark.parametrize("leg", ["headline", "aspp", "infer", "fp32", "frozen", "frozen-aspp", "mixed"])
 def test_every_launch_of_the_leg_matches_the_fp64_reference(leg, monkeypatch, capsys):
     monkeypatch.setattr(plan, "ENABLED", False)
     t0 = time.perf_counter()

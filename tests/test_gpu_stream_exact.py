@@ -3,11 +3,12 @@ and backward, BatchNorm backward, max-pool, channel sums, stem expansion, log-so
 shape, strides and aliasing, against the float64 references of tests/kref.py on exact operands: bit for bit (only
 logsoftmax_bwd, which calls expf, is held to a derived bound).
 
-The four legs of test_gpu_kernels_exact.py run once with the operators wrapped; each distinct call is replayed in
+The legs of test_gpu_kernels_exact.py run once with the operators wrapped; each distinct call is replayed in
 NaN-guarded buffers of the recorded layout, and nothing outside the output views may change (the bytes beyond C in each
 pixel of a sliced view included).  EXTRA_CASES are shapes the legs do not produce (odd max-pool extents, ties on a sliced
-view, non-power-of-two unit counts, a partial last trip under the workgroup cap) and a dozen of the captured ones as plain
-cases.  A table row is printed per case."""
+view, non-power-of-two unit counts, a partial last trip under the workgroup cap, every flush form / template switch / partial
+trip of the one-pass frozen-BatchNorm kernels, the masked two-pass fallback) and a dozen of the captured ones as plain
+cases.  The frozen and mixed legs also assert WHICH kernels the step takes.  A table row is printed per case."""
 import inspect
 import time
 
@@ -36,17 +37,22 @@ VIEWS = {
     "block_tail_bwd_apply": ("go", "go2", "out", "c2", "cb", "g_c2", "g_sc"),
     "block_tail_bwd_apply_fin": ("go", "go2", "c2", "cb", "g_c2", "g_sc"),
     "bn_bwd_reduce": ("ga", "ga2", "c"), "bn_bwd_apply": ("ga", "ga2", "c", "gc"), "bn_bwd_apply_fin": ("ga", "ga2", "c", "gc"),
+    "block_tail_bwd_frozen": ("go", "go2", "c2", "cb", "g_c2", "g_sc"), "bn_bwd_frozen": ("ga", "ga2", "c", "gc"),
     "maxpool_fwd": ("x", "pooled", "xcopy"), "maxpool_bwd": ("x", "g_pooled", "g_extra", "gx"),
     "channel_sum": ("g",), "stem_expand": ("out",), "logsoftmax_bwd": ("g_logits",),
     "pixelwise_nll_fwd": (), "pixelwise_nll_bwd": (),
 }
 OUT_VIEWS = {"block_tail_fwd": ("out",), "block_tail_fwd_fin": ("out",), "block_tail_bwd_apply": ("g_c2", "g_sc"),
              "block_tail_bwd_apply_fin": ("g_c2", "g_sc"), "bn_bwd_apply": ("gc",), "bn_bwd_apply_fin": ("gc",),
+             "block_tail_bwd_frozen": ("g_c2", "g_sc"), "bn_bwd_frozen": ("gc",),
              "maxpool_fwd": ("pooled", "xcopy"), "maxpool_bwd": ("gx",), "stem_expand": ("out",), "logsoftmax_bwd": ("g_logits",)}
 # what the headline bf16 train step must keep calling (ubresnet_amd/engine.py: fused finalizes, masked tails, saved arg-max)
 HEADLINE_OPS = ("block_tail_fwd_fin", "block_tail_bwd_reduce", "block_tail_bwd_apply_fin", "bn_bwd_reduce", "bn_bwd_apply_fin",
                 "maxpool_fwd", "maxpool_bwd", "channel_sum", "stem_expand", "logsoftmax_bwd", "pixelwise_nll_fwd", "pixelwise_nll_bwd")
 HEADLINE_SLICED = ("block_tail_fwd_fin", "block_tail_bwd_apply_fin", "maxpool_fwd")
+# a step whose BatchNorm sites are all frozen takes the one-pass kernels at every site, and no two-pass kernel anywhere
+FROZEN_OPS = ("bn_bwd_frozen", "block_tail_bwd_frozen")
+TWO_PASS_OPS = ("bn_bwd_reduce", "bn_bwd_apply", "bn_bwd_apply_fin", "block_tail_bwd_reduce", "block_tail_bwd_apply", "block_tail_bwd_apply_fin")
 
 if torch.cuda.is_available():
     _SIGS = {n: inspect.signature(getattr(ops, n)) for n in VIEWS}
@@ -402,6 +408,64 @@ def replay_bn_bwd(a, op):
     return "exact", kref.pick_blocks(npix, CU, 2048, 4)
 
 
+def replay_tail_bwd_frozen(a, op):
+    """ubr_block_tail_bwd_frozen: both data gradients and both pairs of sums in one walk; the mask is an input"""
+    B = Buffers(_tvs(a, op))
+    c2v = B.view(a["c2"])
+    npix, C, cpu, CU = _geom(c2v)
+    dt = c2v.dtype
+    go = _fill(B.view(a["go"]), -1)
+    go2 = _fill(B.view(a["go2"]), -1) if a["go2"] is not None else None
+    c2 = _fill(c2v, 0, 0.6)
+    byp = a["cb"] is not None
+    cb = _fill(B.view(a["cb"]), 0, 0.6) if byp else None
+    mask = Guard(npix * CU, torch.uint8, 0)
+    mask.t.copy_(torch.randint(0, 256, (npix * CU,), dtype=torch.uint8, device=DEV, generator=torch.Generator(device=DEV).manual_seed(_next_seed())))
+    m2, s2, t2, i2 = _bn_vectors(C)
+    mb, sb, _, ib = _bn_vectors(C) if byp else (None,) * 4
+    g_c2, g_sc, sums2, sumsb = kref.tail_bwd_frozen_ref(go, go2, kref.mask_unpack(mask.t, c2v.shape, cpu), c2, s2, t2, m2, i2, cb, sb, mb, ib)
+    V = lambda n: B.view(a[n]) if a.get(n) is not None else None
+    r2, init2 = _red_guard(2 * C)
+    rb, initb = _red_guard(2 * C) if byp else (None, None)
+    snap = _begin(B, a, op, [g for g in (mask, r2, rb) if g])
+    _ORIG[op](V("go"), V("go2"), mask.t, c2v, s2, t2, m2, i2, r2.t, V("cb"), sb, mb, ib, rb.t if byp else None, V("g_c2"), V("g_sc"))
+    torch.cuda.synchronize()
+    kref.assert_exact(V("g_c2"), g_c2, dt, g_c2.abs(), 2.0 ** -5, op + " g_c2")
+    if a.get("g_sc") is not None:
+        kref.assert_exact(V("g_sc"), g_sc, dt, g_sc.abs(), 2.0 ** -5, op + " g_sc")
+    else:
+        assert not byp, "a bypass block always writes g_cb"
+    _check_red(r2, init2, RS, sums2, (0.5, 0.25), op + " (bn2)")
+    if byp:
+        _check_red(rb, initb, RS, sumsb, (0.5, 0.25), op + " (bnpass)")
+    mask.check(op + " (mask)", written=False)
+    B.check_sentinel(snap, op)           # (with g_sc = None nothing but g_c2 and the stripes may have changed)
+    return "exact", kref.pick_blocks(npix, CU, 512, 8)
+
+
+def replay_bn_bwd_frozen(a, op):
+    """ubr_bn_bwd_frozen: with `red` the data gradient and the sums in one walk; without, the data gradient alone"""
+    B = Buffers(_tvs(a, op))
+    cv = B.view(a["c"])
+    npix, C, cpu, CU = _geom(cv)
+    dt = cv.dtype
+    ga = _fill(B.view(a["ga"]), -1)
+    ga2 = _fill(B.view(a["ga2"]), -1) if a["ga2"] is not None else None
+    c = _fill(cv, 0, 0.6)
+    mean, scale, shift, invstd = _bn_vectors(C)
+    gc, dbeta, dgamma = kref.bn_bwd_frozen_ref(ga, ga2, c, scale, shift, mean, invstd, a["relu"])
+    V = lambda n: B.view(a[n]) if a.get(n) is not None else None
+    r, init = _red_guard(2 * C) if a["red"] is not None else (None, None)
+    snap = _begin(B, a, op, [r] if r else [])
+    _ORIG[op](V("ga"), V("ga2"), cv, scale, shift, mean, invstd, a["relu"], r.t if r else None, V("gc"))
+    torch.cuda.synchronize()
+    kref.assert_exact(V("gc"), gc, dt, gc.abs(), 2.0 ** -5, op)
+    if r:
+        _check_red(r, init, RS, [dbeta, dgamma], (0.5, 0.25), op)
+    B.check_sentinel(snap, op)           # (pure apply: nothing but gc may have changed)
+    return "exact", kref.pick_blocks(npix, CU, 512, 8) if r else kref.pick_blocks(npix, CU, 2048, 4)
+
+
 def _pool_xf(a, C):
     if a["xf"] is None:
         return None, None
@@ -553,6 +617,7 @@ def replay_nll_bwd(a, op):
 REPLAY = {"block_tail_fwd": replay_tail_fwd, "block_tail_fwd_fin": replay_tail_fwd,
           "block_tail_bwd_reduce": replay_tail_bwd, "block_tail_bwd_apply": replay_tail_bwd, "block_tail_bwd_apply_fin": replay_tail_bwd,
           "bn_bwd_reduce": replay_bn_bwd, "bn_bwd_apply": replay_bn_bwd, "bn_bwd_apply_fin": replay_bn_bwd,
+          "block_tail_bwd_frozen": replay_tail_bwd_frozen, "bn_bwd_frozen": replay_bn_bwd_frozen,
           "maxpool_fwd": replay_maxpool_fwd, "maxpool_bwd": replay_maxpool_bwd, "channel_sum": replay_channel_sum,
           "stem_expand": replay_stem_expand, "logsoftmax_bwd": replay_logsoftmax_bwd,
           "pixelwise_nll_fwd": replay_nll_fwd, "pixelwise_nll_bwd": replay_nll_bwd}
@@ -583,6 +648,8 @@ def _flags(rec):
             f.append("%s=%s" % (k, int(a[k])))
     if a.get("xf") is not None:
         f.append("lo=%s" % ("0" if all(v == 0 for v in a["xf"][1]) else "mixed"))
+    if rec["op"] == "bn_bwd_frozen" and a.get("red") is None:
+        f.append("pure-apply")
     return ",".join(f)
 
 
@@ -607,7 +674,32 @@ def _print_table(rows, capsys, title):
             print("  %-9s %-25s %-40s %-44s wgs=%-5d %-8s %5.2fs" % (leg, op, shp, fl, wgs, res, sec))
 
 
-@pytest.mark.parametrize("leg", ["headline", "aspp", "infer", "fp32"])
+def _sliced(rec):
+    return any(v.stride[2] > v.shape[3] for v in _tvs(rec["a"], rec["op"]))
+
+
+def _assert_frozen_schedule(leg, recs):
+    """which kernels a frozen / mixed-mode step must take (ubresnet_amd/engine.py: Engine._bn_bwd, Engine.block_bwd): a fall back to
+    the two-pass kernels computes the same gradients and would only show as lost time"""
+    used = {r["op"] for r in recs}
+    if leg in ("frozen", "frozen-aspp"):
+        for op in FROZEN_OPS:
+            assert op in used, "the %s step no longer calls ops.%s" % (leg, op)
+        two = sorted(used & set(TWO_PASS_OPS))
+        assert not two, "the %s step fell back to the two-pass kernels: %s" % (leg, ", ".join(two))
+        if leg == "frozen":
+            assert any(r["op"] == "block_tail_bwd_frozen" and r["a"]["cb"] is None and r["a"]["g_sc"] is None for r in recs), \
+                "no identity tail of the frozen step leaves its skip gradient to conv1's data gradient (g_sc = None)"
+        else:
+            assert any(r["op"] in FROZEN_OPS and _sliced(r) for r in recs), \
+                "the frozen ASPP step no longer passes a channel slice (pixel stride > C) to a one-pass kernel"
+    if leg == "mixed":
+        assert any(r["op"] == "block_tail_bwd_apply" and r["a"]["relu_mask"] is not None for r in recs), \
+            "a tail with sites in different modes no longer takes the masked two-pass fallback (ops.block_tail_bwd_apply)"
+        assert "block_tail_bwd_apply_fin" in used, "the all-train tails of the mixed step no longer fuse their finalizes"
+
+
+@pytest.mark.parametrize("leg", ["headline", "aspp", "infer", "fp32", "frozen", "frozen-aspp", "mixed"])
 def test_every_streaming_launch_of_the_leg_matches_the_fp64_reference(leg, monkeypatch, capsys):
     monkeypatch.setattr(plan, "ENABLED", False)
     t0 = time.perf_counter()
@@ -624,6 +716,7 @@ def test_every_streaming_launch_of_the_leg_matches_the_fp64_reference(leg, monke
         for op in HEADLINE_SLICED:
             assert any(r["op"] == op and any(v.stride[2] > v.shape[3] for v in _tvs(r["a"], op)) for r in recs), \
                 "the headline step no longer passes a channel slice (pixel stride > C) to ops.%s" % op
+    _assert_frozen_schedule(leg, recs)
     rows, fails = run_cases(leg, recs)
     _print_table(rows, capsys, "%s (%d launches captured, %.1fs)" % (leg, len(cap.calls), time.perf_counter() - t0))
     assert len(rows) == len(recs)
@@ -685,6 +778,17 @@ def _bn_bwd(kind, shape, dt=BF, relu=True, ga_ps=None, ga_off=0, c_ps=None, c_of
     return _case("bn_bwd_" + kind, **a)
 
 
+def _tail_frozen(shape, dt=BF, byp=True, go2_ps=None, go2_off=0, g_sc=True, gc2_ps=None, gc2_off=0):
+    return _case("block_tail_bwd_frozen", go=_v(shape, dt), go2=_v(shape, dt, go2_ps, go2_off) if go2_ps else None, relu_mask=True,
+                 c2=_v(shape, dt), red2=True, cb=_v(shape, dt) if byp else None, red_b=True if byp else None,
+                 g_c2=_v(shape, dt, gc2_ps, gc2_off), g_sc=_v(shape, dt) if (g_sc or byp) else None)
+
+
+def _bn_frozen(shape, dt=BF, relu=True, ga2=False, red=True, ga_ps=None, ga_off=0, c_ps=None, c_off=0):
+    return _case("bn_bwd_frozen", ga=_v(shape, dt, ga_ps, ga_off), ga2=_v(shape, dt) if ga2 else None, c=_v(shape, dt, c_ps, c_off),
+                 relu=relu, red=True if red else None, gc=_v(shape, dt))
+
+
 def _pool(bwd, shape, stride, dt=BF, xf=True, argmax=False, slice_ps=None, slice_off=0, extra=True, xcopy=False):
     N, H, W, C = shape
     oshape = (N, kref.pool_out(H, stride), kref.pool_out(W, stride), C)
@@ -697,6 +801,61 @@ def _pool(bwd, shape, stride, dt=BF, xf=True, argmax=False, slice_ps=None, slice
 
 
 PARTIAL = (2, 1000, 721, 16)      # 1 442 000 pixels: with the grid capped, the second trip is partial, and only for some threads
+# The one-pass kernels of frozen sites walk trips of four pixels per thread (UNR = 4), pixel u of a trip at p + u * pstep.
+# 316 683 pixels x 32 bf16 channels = 1 266 732 units: pick_blocks(npix, 4, 512, 8) wants 619 workgroups and is capped at 512, so
+# pstep = 512 * 256 / 4 = 32 768 and a trip covers 131 072 pixels: two full trips, then 54 539 pixels = 32 768 + 21 771 -- in the
+# third trip pixel 0 of the unroll is full, pixel 1 is partial (only for the threads below 21 771 * 4), pixels 2 and 3 are empty.
+# With 64 channels and no sums (pure apply), pick_blocks(npix, 8, 2048, 4) wants 2475 and is capped at 2048: pstep = 65 536, a trip
+# covers 262 144 pixels, and the second trip (54 539 pixels) is partial in its first pixel.
+PARTIAL_FROZEN = (3, 333, 317, 32)
+PARTIAL_FROZEN_APPLY = (3, 333, 317, 64)
+SWITCH = (2, 64, 64, 32)          # 8192 pixels: 16 workgroups with sums (32 in fp32), 32 for pure apply (64 in fp32): whole trips only
+# (shape, type) per form of the sums flush (red_flush_mode / flush_sums_pow2 / flush_sums in csrc/ubr_elem.hip); workgroups with
+# sums = pick_blocks(npix, CU, 512, 8); no trip is partial at these sizes (the flush is what differs)
+FLUSH_FORMS = [("C16", (4, 32, 32, 16), BF),           # CU 2: register butterfly over five lane bits; 4 workgroups
+               ("C80", (4, 32, 32, 80), BF),           # CU 10: not a power of two, below a wave: fp64 LDS atomics; 20 workgroups (a multiple of 5)
+               ("C96", (4, 32, 32, 96), BF),           # CU 12: the same; 24 workgroups (a multiple of 3)
+               ("C512", (16, 16, 16, 512), BF),        # CU 64: one unit per lane, no butterfly; 128 workgroups
+               ("C512-f32", (4, 16, 16, 512), F32),    # CU 128: a wave covers half the units: the per-wave rows are zeroed first; 64 workgroups
+               ("C768", (4, 16, 16, 768), BF)]         # CU 96: >= 64 and not a power of two, routed to the row flush by rule; 48 workgroups
+
+
+def _frozen_cases():
+    """the one-pass backward of frozen BatchNorm sites (ubr_block_tail_bwd_frozen, ubr_bn_bwd_frozen) at the smallest shapes that
+    still take each of its paths, and the two-pass paths that only a frozen or mixed-mode step reaches"""
+    c = []
+    # every form of the sums flush, through both one-pass kernels
+    for nm, shp, dt in FLUSH_FORMS:
+        c += [("frozen-tail-" + nm, _tail_frozen(shp, dt)), ("frozen-bn-" + nm, _bn_frozen(shp, dt))]
+    # CU = 96 through the two-pass reduce kernels, which share the rule
+    c += [("bn-reduce-C768", _bn_bwd("reduce", FLUSH_FORMS[-1][1])), ("tail-reduce-C768", _tail_bwd("reduce", FLUSH_FORMS[-1][1]))]
+    # a last trip that is partial for only some of the four unrolled pixels, under the workgroup cap (see PARTIAL_FROZEN)
+    c += [("frozen-tail-partial", _tail_frozen(PARTIAL_FROZEN, go2_ps=64, go2_off=32)),
+          ("frozen-bn-partial", _bn_frozen(PARTIAL_FROZEN, ga2=True)),
+          ("frozen-bn-partial-pure-apply", _bn_frozen(PARTIAL_FROZEN_APPLY, red=False))]
+    # the template switches, in all three element types
+    for tn, dt in (("f32", F32), ("bf16", BF), ("f16", torch.float16)):
+        for byp in (True, False):
+            for two in (False, True):
+                c.append(("frozen-tail-%s-%s%s" % (tn, "bypass" if byp else "identity", "-go2" if two else ""),
+                          _tail_frozen(SWITCH, dt, byp=byp, go2_ps=32 if two else None)))
+        c.append(("frozen-tail-%s-identity-lazy" % tn, _tail_frozen(SWITCH, dt, byp=False, g_sc=False)))
+        for relu in (True, False):
+            for two in (False, True):
+                for red in (True, False):
+                    c.append(("frozen-bn-%s%s%s%s" % (tn, "-relu" if relu else "", "-ga2" if two else "", "" if red else "-pure-apply"),
+                              _bn_frozen(SWITCH, dt, relu=relu, ga2=two, red=red)))
+    # channel slices: ga and c as channels 32..48 of 80-channel buffers (the ASPP concat layout); a tail whose g_c2 is channels
+    # 32..64 of a 64-channel buffer (a byte written beyond C lands in the sentinel or in the next pixel's other half)
+    c += [("frozen-bn-slice80", _bn_frozen((4, 32, 32, 16), ga_ps=80, ga_off=32, c_ps=80, c_off=32)),
+          ("frozen-bn-slice80-pure-apply", _bn_frozen((4, 32, 32, 16), ga_ps=80, ga_off=32, c_ps=80, c_off=32, red=False)),
+          ("frozen-tail-gc2-slice64", _tail_frozen(SWITCH, gc2_ps=64, gc2_off=32)),
+          ("frozen-tail-identity-lazy-gc2-slice64", _tail_frozen(SWITCH, byp=False, g_sc=False, gc2_ps=64, gc2_off=32))]
+    # the two-pass fallback of a tail with sites in different modes: the masked apply pass with k1 / k2 from standalone finalizes
+    c += [("tail-apply-masked-bypass", _tail_bwd("apply", SWITCH, mask=True)),
+          ("tail-apply-masked-identity", _tail_bwd("apply", SWITCH, byp=False, mask=True)),
+          ("tail-apply-masked-partial", _tail_bwd("apply", PARTIAL_FROZEN, mask=True))]
+    return c
 
 
 def _extra_cases():
@@ -719,6 +878,7 @@ def _extra_cases():
           ("partial-tail-apply", _tail_bwd("apply_fin", PARTIAL, go2_ps=32, go2_off=16)), ("partial-tail-apply-out", _tail_bwd("apply", PARTIAL, mask=False)),
           ("partial-bn-reduce", _bn_bwd("reduce", PARTIAL, ga2=True)), ("partial-bn-apply", _bn_bwd("apply", PARTIAL)),
           ("partial-channel-sum", _case("channel_sum", g=_v(PARTIAL, BF, 32, 16)))]
+    c += _frozen_cases()
     # captured shapes of the headline / ASPP / fp32 legs
     c += [("tail-fwd-16x256x256x32", _tail_fwd((16, 256, 256, 32), ps=64, off=32)),
           ("tail-fwd-identity-16x256x256x16", _tail_fwd((16, 256, 256, 16), byp=False)),
