@@ -903,3 +903,95 @@ def stitch_tiles_ref(scores, desc, out):
                     break
                 out[p, :, r0 + y, c0 + x] = scores[t, :, y, x]
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# edge values of the storage types (self-test in tests/test_cpu_kref.py)
+# ------------------------------------------------------------------------------------------------------------------
+# exact_operands() never puts a kernel's store on a rounding tie, past the largest finite value of the storage type, on a
+# subnormal, a signed zero, an infinity or a NaN.  edge_table() lists such fp32 values by CLASS, built from bit patterns:
+# the midpoint of two neighbours of T is the fp64 mean of the two (exact in fp32: T has at most 11 significant bits), its
+# fp32 neighbours are the bit pattern +- 1.  Every class comes in both signs.  The reference rounding is torch's .to(T):
+# round to nearest even, subnormals kept, NaN stays NaN.
+FLT_MAX_BITS = 0x7f7fffff
+_T_INFO = {      # (bit patterns b of T whose midpoint with b + 1 is listed: even b, odd b; largest finite; largest subnormal; smallest normal)
+    torch.bfloat16: ((0x3f80, 0x2f82, 0x4a7e, 0x0002, 0x7f00), (0x3f81, 0x2f83, 0x4a7f, 0x0003, 0x7f01), 0x7f7f, 0x007f, 0x0080),
+    torch.float16: ((0x3c00, 0x1402, 0x6bfe, 0x0002, 0x7800), (0x3c01, 0x1403, 0x6bff, 0x0003, 0x7801), 0x7bff, 0x03ff, 0x0400),
+}
+NAN_CLASSES = ("nan", "nan_low_payload")
+
+
+def _from_bits32(b):
+    return torch.tensor([x - (1 << 32) if x >= (1 << 31) else x for x in b], dtype=torch.int64).to(torch.int32).view(torch.float32)
+
+
+def _t_value(b, dtype):
+    """the fp32 value of bit pattern b of the 16-bit type"""
+    return float(torch.tensor([b], dtype=torch.int32).to(torch.int16).view(dtype).float())
+
+
+def _bits_of(x):
+    return int(torch.tensor([x], dtype=torch.float32).view(torch.int32)) & 0xffffffff
+
+
+def edge_table(dtype):
+    """[(class name, fp32 bit pattern)] of the edge values of storage type `dtype`, positive sign first, then every entry
+    again with the sign bit set (names prefixed '-')"""
+    rows = [("f32_subnormal_min", 0x00000001), ("f32_subnormal", 0x00012345), ("f32_subnormal_max", 0x007fffff),
+            ("zero", 0x00000000), ("inf", 0x7f800000), ("nan", 0x7fc00000), ("flt_max", FLT_MAX_BITS)]
+    if dtype != torch.float32:
+        even, odd, tmax, submax, normmin = _T_INFO[dtype]
+        for nm, bs in (("tie_even", even), ("tie_odd", odd)):
+            for b in bs:
+                mid = (torch.tensor(_t_value(b, dtype), dtype=torch.float64) + _t_value(b + 1, dtype)) / 2
+                assert float(mid.float().double()) == float(mid)
+                mb = _bits_of(float(mid))
+                rows += [(nm, mb), (nm + "_above", mb + 1), (nm + "_below", mb - 1)]
+        top = _t_value(tmax, dtype)
+        ovf = _bits_of(top + (top - _t_value(tmax - 1, dtype)) / 2)           # largest finite + half a T-ulp
+        smin = _t_value(1, dtype)
+        rows += [("t_max", _bits_of(top)), ("overflow_tie", ovf), ("overflow_below", ovf - 1),
+                 ("t_subnormal_min", _bits_of(smin)), ("t_subnormal_half", _bits_of(smin / 2)), ("t_subnormal_half_above", _bits_of(smin / 2) + 1),
+                 ("t_subnormal_max", _bits_of(_t_value(submax, dtype))), ("t_normal_min", _bits_of(_t_value(normmin, dtype))),
+                 # a NaN whose payload lies in the low 16 bits only: truncation, or adding 0x7fff before it, gives infinity
+                 ("nan_low_payload", 0x7f800001)]
+    return rows + [("-" + n, b | 0x80000000) for n, b in rows]
+
+
+def edge_values(dtype, classes=None, exclude=()):
+    """fp32 tensor of the edge values of `dtype` (edge_table order); classes / exclude filter by class name without the sign"""
+    rows = [(n, b) for n, b in edge_table(dtype) if (classes is None or n.lstrip("-") in classes) and n.lstrip("-") not in exclude]
+    return _from_bits32([b for _, b in rows])
+
+
+def tie_bases(dtype):
+    """{class: T bit patterns b whose midpoint with b + 1 the table lists} (for the self-test: neighbours from bit patterns)"""
+    return {"tie_even": _T_INFO[dtype][0], "tie_odd": _T_INFO[dtype][1]}
+
+
+def edge_names(dtype, classes=None, exclude=()):
+    return [n for n, _ in edge_table(dtype) if (classes is None or n.lstrip("-") in classes) and n.lstrip("-") not in exclude]
+
+
+def assert_bits(got, expected, zero_sign=True, what=""):
+    """equal bit patterns element for element: +0 != -0 (unless zero_sign is False, for a formula that leaves the sign of a zero
+    open), any NaN matches any NaN and nothing else"""
+    assert got.shape == expected.shape and got.dtype == expected.dtype, "%s: %s %s vs %s %s" % (what, tuple(got.shape), got.dtype, tuple(expected.shape), expected.dtype)
+    e = expected.to(got.device)
+    if got.is_floating_point():
+        gn, en = torch.isnan(got), torch.isnan(e)
+        same = bits(got) == bits(e)
+        if not zero_sign:
+            same = same | ((got == 0) & (e == 0))
+        bad = ~((same & ~gn & ~en) | (gn & en))
+    else:
+        bad = got != e
+    if bool(bad.any()):
+        idx = tuple(bad.nonzero()[0].tolist())
+        if got.is_floating_point():
+            gb, eb = int(bits(got)[idx]), int(bits(e)[idx])
+        else:
+            gb, eb = int(got[idx]), int(e[idx])
+        m = (1 << (8 * got.element_size())) - 1
+        raise AssertionError("%s: %d of %d elements differ in bits; first at %s: got %r (0x%x), expected %r (0x%x)"
+                             % (what, int(bad.sum()), bad.numel(), idx, float(got[idx]), gb & m, float(e[idx]), eb & m))

@@ -760,3 +760,126 @@ def test_tile_refs_crop_with_zero_fill_and_stitch_only_inside_keep_windows():
     scores = np.stack([crop[0][None], crop[1][None]])
     kref.stitch_tiles_ref(scores, [(1, 3, 4, 0, 4, 0, 6), (0, 0, 0, 1, 3, 2, 2)], out)
     assert np.array_equal(out[1, 0, 3:5, 4:7], view[1, 3:5, 4:7]) and int(np.isnan(out).sum()) == out.size - 6
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# edge-value table (kref.edge_table / edge_values / assert_bits)
+# ------------------------------------------------------------------------------------------------------------------
+def _t_from_bits(b, dt):
+    """fp64 value of bit pattern b of the 16-bit type (no rounding involved: widening is exact)"""
+    return float(torch.tensor([b], dtype=torch.int32).to(torch.int16).view(dt).double())
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+def test_edge_table_holds_what_its_class_names_say(dt):
+    names = kref.edge_names(dt)
+    v = kref.edge_values(dt)
+    assert len(names) == v.numel() and v.dtype == torch.float32
+    r = v.to(dt)                                   # torch's conversion: RNE, the reference
+    fi = torch.finfo(dt)
+    seen = set()
+    for i, nm in enumerate(names):
+        neg = nm.startswith("-")
+        base = nm.lstrip("-")
+        seen.add(base)
+        x, rx = v[i:i + 1], r[i:i + 1]
+        assert bool(torch.signbit(x)) == neg, nm
+        if base in kref.NAN_CLASSES:
+            assert bool(torch.isnan(x)) and bool(torch.isnan(rx)), nm
+            if base == "nan_low_payload":
+                b = int(x.view(torch.int32)) & 0x7fffffff
+                assert b >> 16 == 0x7f80 and b & 0xffff, nm            # truncation gives infinity
+                assert ((b + 0x7fff) >> 16) == 0x7f80, nm
+            continue
+        mag, rmag = abs(float(x)), abs(float(rx))
+        if base.startswith("tie_"):
+            # neighbours from the T bit patterns b and b + 1, independent of the conversion under reference
+            kind = "tie_even" if base.startswith("tie_even") else "tie_odd"
+            seq = [j for j, n in enumerate(names) if n == ("-" if neg else "") + base]
+            b = kref.tie_bases(dt)[kind][seq.index(i)]
+            lo, hi = _t_from_bits(b, dt), _t_from_bits(b + 1, dt)
+            assert (b & 1) == (0 if kind == "tie_even" else 1) and 0 < lo < hi, nm
+            if base == kind:
+                assert hi - mag == mag - lo > 0, nm                        # both neighbours equidistant, in fp64
+                assert rmag == (lo if kind == "tie_even" else hi), nm       # RNE: the neighbour with the even last bit
+            else:
+                tie = float((x.abs().view(torch.int32) + (-1 if base.endswith("above") else 1)).view(torch.float32))
+                assert hi - tie == tie - lo and (mag > tie) == base.endswith("above"), nm
+                assert rmag == (hi if base.endswith("above") else lo), nm
+        elif base == "t_max":
+            assert mag == fi.max and rmag == fi.max, nm
+        elif base == "overflow_tie":
+            assert mag == fi.max + (fi.max - float(torch.nextafter(torch.tensor(fi.max, dtype=dt), torch.tensor(0., dtype=dt)))) / 2 and rmag == float("inf"), nm
+        elif base == "overflow_below":
+            assert rmag == fi.max and mag > fi.max, nm
+        elif base == "flt_max":
+            assert mag == torch.finfo(torch.float32).max and rmag == float("inf"), nm
+        elif base == "t_subnormal_min":
+            assert mag == fi.smallest_normal * fi.eps and rmag == mag, nm
+        elif base == "t_subnormal_half":
+            assert mag == fi.smallest_normal * fi.eps / 2 and rmag == 0.0 and bool(torch.signbit(rx)) == neg, nm
+        elif base == "t_subnormal_half_above":
+            assert rmag == fi.smallest_normal * fi.eps and mag < rmag, nm
+        elif base == "t_subnormal_max":
+            assert mag == fi.smallest_normal * (1 - fi.eps) and rmag == mag, nm
+        elif base == "t_normal_min":
+            assert mag == fi.smallest_normal and rmag == mag, nm
+        elif base.startswith("f32_subnormal"):
+            assert 0 < mag < torch.finfo(torch.float32).smallest_normal, nm
+        elif base == "zero":
+            assert mag == 0 and rmag == 0 and bool(torch.signbit(rx)) == neg, nm
+        elif base == "inf":
+            assert mag == float("inf") and rmag == float("inf"), nm
+        else:
+            raise AssertionError("unknown class " + nm)
+    assert {"tie_even", "tie_odd", "tie_even_above", "tie_odd_below", "t_max", "overflow_tie", "overflow_below", "flt_max", "t_subnormal_min",
+            "t_subnormal_half", "t_subnormal_half_above", "t_subnormal_max", "t_normal_min", "f32_subnormal", "zero", "inf", "nan",
+            "nan_low_payload"} <= seen
+    # ties at several exponents, a value that rounds to 0 although it is > 0, one that rounds to the largest finite
+    assert len({torch.frexp(v[i])[1].item() for i, n in enumerate(names) if n == "tie_even"}) >= 4
+    assert any(float(v[i]) > 0 and float(r[i]) == 0 for i in range(len(names)))
+
+
+def test_edge_table_float32_and_filters():
+    names = kref.edge_names(torch.float32)
+    v = kref.edge_values(torch.float32)
+    tiny, big = 2.0 ** -149, float(torch.finfo(torch.float32).max)
+    want = {"f32_subnormal_min": tiny, "f32_subnormal": 0x12345 * tiny, "f32_subnormal_max": 2.0 ** -126 - tiny, "zero": 0.0,
+            "inf": float("inf"), "flt_max": big, "nan": None}
+    assert {n.lstrip("-") for n in names} == set(want) and len(names) == 2 * len(want)
+    for i, n in enumerate(names):
+        w = want[n.lstrip("-")]
+        assert bool(torch.signbit(v[i])) == n.startswith("-"), n
+        assert bool(torch.isnan(v[i])) if w is None else abs(float(v[i].double())) == w, n
+    assert big == (2.0 - 2.0 ** -23) * 2.0 ** 127
+    v = kref.edge_values(torch.float32, exclude=kref.NAN_CLASSES)
+    assert not bool(torch.isnan(v).any()) and v.numel() == len(names) - 2
+    fin = kref.edge_values(torch.float16, exclude=kref.NAN_CLASSES + ("inf", "flt_max", "overflow_tie"))
+    assert bool(torch.isfinite(fin.to(torch.float16)).all())
+    # the ties reach from the subnormal range to the top binade of either type
+    for dt in (torch.bfloat16, torch.float16):
+        t = kref.edge_values(dt, classes=("tie_even",)).abs()
+        fi = torch.finfo(dt)
+        assert float(t.min()) < fi.smallest_normal and float(t.max()) > fi.max / 2
+
+
+def test_assert_bits_tells_signed_zeros_and_nans():
+    for dt in (torch.float32, torch.bfloat16, torch.float16):
+        a = torch.tensor([0.0, -0.0, float("nan"), float("inf"), 1.0]).to(dt)
+        kref.assert_bits(a, a.clone())
+        nan2 = a.clone()
+        nan2[2] = -a[2]                                   # another NaN bit pattern
+        kref.assert_bits(a, nan2)
+        z = a.clone()
+        z[1] = 0.0
+        with pytest.raises(AssertionError, match="differ in bits"):
+            kref.assert_bits(a, z)
+        kref.assert_bits(a, z, zero_sign=False)
+        for j, val in ((2, float("inf")), (3, float("nan")), (4, 1.0 + 2.0 ** -7)):
+            b = a.clone()
+            b[j] = val
+            with pytest.raises(AssertionError, match="differ in bits"):
+                kref.assert_bits(a, b, zero_sign=False)
+    kref.assert_bits(torch.tensor([1, 2], dtype=torch.uint8), torch.tensor([1, 2], dtype=torch.uint8))
+    with pytest.raises(AssertionError):
+        kref.assert_bits(torch.tensor([1, 2], dtype=torch.uint8), torch.tensor([1, 3], dtype=torch.uint8))

@@ -841,16 +841,19 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const PoolK k) {
     float m[CPU];
     int am[CPU];
 #pragma unroll
-    for (int e = 0; e < CPU; ++e) { m[e] = -FLT_MAX; am[e] = -1; }
+    // (-inf, not -FLT_MAX: a window whose taps are all -inf pools to -inf in fp32 as well)
+    for (int e = 0; e < CPU; ++e) { m[e] = -INFINITY; am[e] = -1; }
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
       float v[CPU];
       unpack4<T>(raw[t], v);
       if constexpr (XF) ubr_bnrelu<CPU>(v, sb, sc, sh, lo);
       if constexpr (AMAX) {
+        // strict >: first maximum wins (ATen).  A NaN tap is skipped, as fmaxf skips it in the form without arg-max: taken as a
+        // window's first tap it is replaced by the next one (m != m), later it never compares greater.
 #pragma unroll
         for (int e = 0; e < CPU; ++e)
-          if (ok[t] && (am[e] < 0 || v[e] > m[e])) { m[e] = v[e]; am[e] = t; }   // strict >: first maximum wins (ATen)
+          if (ok[t] && (am[e] < 0 || v[e] > m[e] || m[e] != m[e])) { m[e] = v[e]; am[e] = t; }
       } else {
 #pragma unroll
         for (int e = 0; e < CPU; ++e) m[e] = ok[t] ? fmaxf(m[e], v[e]) : m[e];
@@ -865,6 +868,10 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const PoolK k) {
       }
     }
     {
+      if constexpr (AMAX) {     // a window of nothing but NaN: -inf, what the fmaxf chain of the other form leaves
+#pragma unroll
+        for (int e = 0; e < CPU; ++e) m[e] = m[e] != m[e] ? -INFINITY : m[e];
+      }
       const uint4 pk = ET<T>::pack(m);
       __builtin_amdgcn_raw_buffer_store_b128(ubr_u4{pk.x, pk.y, pk.z, pk.w}, pr, (int)(pu * (unsigned)k.p_ps * ESZ + (unsigned)ix.c * 16u), 0, 0);
     }
