@@ -239,7 +239,7 @@ int ubr_wgrad_reduce_batched(const ubr_wgrad_reduce_item* items_host, int nitems
 int ubr_stem_forward(int dtype, const float* x_nchw, int N, int Cin, int H, int W,
                      const float* weight /*[Cout][Cin][7][7]*/, const float* bias, int Cout,
                      ubr_tensor y, double* stats, void* stream);
-int ubr_stem_wgrad(int dtype, const float* x_nchw, int N, int Cin, int H, int W, ubr_tensor g, int Cout,
+int ubr_stem_wgrad(int dtype, const float* x_nchw, int N, int Cin, int H, int W, ubr_tensor g, int Cout /* 16 or 32 */,
                    float* partial /*workspace*/, int64_t partial_bytes, float* dweight, float* dbias,
                    int accumulate, void* stream);
 int64_t ubr_stem_wgrad_workspace(int N, int Cin, int H, int W, int Cout);
@@ -486,6 +486,13 @@ int ubr_tape_set_label(ubr_tape* t, int label);
 /* replay with timing events around every launch on its own stream; synchronises the tape's streams.  ms[i], label[i] per
    node (label -2: fork / mark node); cap = room in both arrays (>= ubr_tape_size) */
 int ubr_tape_replay_timed(const ubr_tape* t, int nstreams, void* const* streams, float* ms, int32_t* label, int cap);
+
+/* Launch log (tests): ubr_launch_log(on) clears the process-wide set of launched kernel symbols and switches recording on or off;
+ * while on, every kernel this library launches adds its symbol, as the HIP runtime names it (tape replays re-issue recorded
+ * closures and add nothing).  ubr_launch_log_read copies the distinct names, newline-separated and NUL-terminated, into buf
+ * (truncated to n bytes) and returns the size a complete copy needs, the terminator included. */
+int ubr_launch_log(int on);
+int ubr_launch_log_read(char* buf, int n);
 
 const char* ubr_last_error(void);
 int ubr_version(void);

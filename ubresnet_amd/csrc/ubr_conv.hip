@@ -1877,6 +1877,7 @@ int try_thin(const ConvK& c, dim3 grid, hipStream_t st, int* rc) {
   static const bool thin_on = [] { const char* e = getenv("UBR_CONV_THIN"); return !e || atoi(e) != 0; }();
   const int esz = 16 / ET<T>::CPU;
   if (!thin_on || c.nblk != 1 || c.S != 1 || (c.UPB != 2 && c.UPB != 4)) return 0;
+  if constexpr (FW == 8) { if (c.UPB == 4) return 0; }    // no 4-unit form on the 16x32-pixel tile: its halo never fits the register slots (below)
   const int nph = (int)grid.z;
   int steps_tot = c.steps, nunits_tot = c.nunits;
   if (nph > 1) {
@@ -2003,11 +2004,21 @@ int try_thin(const ConvK& c, dim3 grid, hipStream_t st, int* rc) {
       return 0;
     }
   }
-  if (ext == 1) *rc = c.UPB == 2 ? launch_thin<T, FW, NT, TWF, 2, false, false, false, 1>(k, g, lds, st) : launch_thin<T, FW, NT, TWF, 4, false, false, false, 1>(k, g, lds, st);
-  else if (ext == 2) *rc = c.UPB == 2 ? launch_thin<T, FW, NT, TWF, 2, false, false, false, 2>(k, g, lds, st) : launch_thin<T, FW, NT, TWF, 4, false, false, false, 2>(k, g, lds, st);
-  else if (c.UPB == 2) *rc = xf ? launch_thin<T, FW, NT, TWF, 2, true>(k, g, lds, st) : launch_thin<T, FW, NT, TWF, 2, false>(k, g, lds, st);
-  else *rc = xf ? launch_thin<T, FW, NT, TWF, 4, true>(k, g, lds, st) : launch_thin<T, FW, NT, TWF, 4, false>(k, g, lds, st);
-  return 1;
+  if (c.UPB == 2) {
+    if (ext == 1) *rc = launch_thin<T, FW, NT, TWF, 2, false, false, false, 1>(k, g, lds, st);
+    else if (ext == 2) *rc = launch_thin<T, FW, NT, TWF, 2, false, false, false, 2>(k, g, lds, st);
+    else *rc = xf ? launch_thin<T, FW, NT, TWF, 2, true>(k, g, lds, st) : launch_thin<T, FW, NT, TWF, 2, false>(k, g, lds, st);
+    return 1;
+  }
+  // 4-unit blocks exist on the 8-row tiles only: on the 16x32-pixel tile even a one-tap halo, 16 * 32 * 4 items, is beyond the
+  // 256 * 6 register slots checked above, so no descriptor reaches this point with FW == 8 and those kernels are not compiled
+  if constexpr (FW != 8) {
+    if (ext == 1) *rc = launch_thin<T, FW, NT, TWF, 4, false, false, false, 1>(k, g, lds, st);
+    else if (ext == 2) *rc = launch_thin<T, FW, NT, TWF, 4, false, false, false, 2>(k, g, lds, st);
+    else *rc = xf ? launch_thin<T, FW, NT, TWF, 4, true>(k, g, lds, st) : launch_thin<T, FW, NT, TWF, 4, false>(k, g, lds, st);
+    return 1;
+  }
+  return 0;
 }
 
 // the cin-block pipeline exists for the 64-cout tiles, when a block's items fit its register slots

@@ -356,7 +356,8 @@ extern "C" int ubr_stem_wgrad(int dtype, const float* x_nchw, int N, int Cin, in
   UBR_CHECK(ubr_dtype_ok(dtype), "ubr_stem_wgrad: bad dtype");
   UBR_CHECK(x_nchw && g.p && partial && dweight, "ubr_stem_wgrad: null pointer");
   UBR_CHECK(N > 0 && H > 0 && W > 0 && Cin >= 1 && Cin <= 4, "ubr_stem_wgrad: bad extents");
-  UBR_CHECK(Cout == 16 || Cout == 32 || Cout == 64, "ubr_stem_wgrad: Cout=%d must be 16, 32 or 64", Cout);
+  // (64 output channels would need 256 * 64 floats of LDS for the partial sums alone, the whole 64 KiB this launch may ask for)
+  UBR_CHECK(Cout == 16 || Cout == 32, "ubr_stem_wgrad: Cout=%d must be 16 or 32", Cout);
   UBR_CHECK(partial_bytes >= ubr_stem_wgrad_workspace(N, Cin, H, W, Cout), "ubr_stem_wgrad: workspace too small");
   const int esz = ubr_esize(dtype);
   UBR_CHECK(ubr_aligned16(g.p) && (g.sx * esz) % 16 == 0 && (g.sy * esz) % 16 == 0 && (g.sn * esz) % 16 == 0 && g.sx >= Cout,
@@ -369,7 +370,7 @@ extern "C" int ubr_stem_wgrad(int dtype, const float* x_nchw, int N, int Cin, in
 #define UBR_SW(CO) UBR_DT_SWITCH(dtype, ubr_launch((stem_wgrad_kernel<TT, CO>), dim3(nwg), dim3(256), lds, st, x_nchw, N, Cin, H, W, \
     (const char*)g.p, (long)g.sn * esz, (long)g.sy * esz, (long)g.sx * esz, partial, tiles_x, tiles_y, ntiles))
   if (lds > 64 * 1024) { ubr_set_error("ubr_stem_wgrad: LDS too large"); return UBR_EINVAL; }
-  if (Cout == 16) { UBR_SW(16); } else if (Cout == 32) { UBR_SW(32); } else { UBR_SW(64); }
+  if (Cout == 16) { UBR_SW(16); } else { UBR_SW(32); }
 #undef UBR_SW
   UBR_LAUNCH_CHECK("ubr_stem_wgrad");
   const int nw = Cout * Cin * 49;

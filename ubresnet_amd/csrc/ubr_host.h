@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <atomic>
 #include <functional>
 #include <tuple>
 #include <type_traits>
@@ -67,9 +68,15 @@ struct ubr_tape {
 };
 ubr_tape* ubr_tape_current();                // the tape recording on this thread (nullptr: none); ubr_tape.hip
 
+// Launch log (include/ubresnet_hip.h, ubr_launch_log): while switched on, ubr_launch adds the symbol of every kernel it launches to a
+// process-wide set (ubr_tape.hip).  Off, the cost is one relaxed load.  Tape replays re-issue closures and are not logged.
+extern std::atomic<int> g_ubr_launch_log_on;
+void ubr_launch_log_add(const void* fn, hipStream_t st);
+
 template <typename... KA, typename... A>
 static inline void ubr_launch(void (*fn)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A&&... a) {
   fn<<<grid, block, lds, st>>>(a...);
+  if (g_ubr_launch_log_on.load(std::memory_order_relaxed)) ubr_launch_log_add(reinterpret_cast<const void*>(fn), st);
   ubr_tape* t = ubr_tape_current();
   if (t != nullptr && t->recording && t->paused == 0) {
     std::tuple<std::decay_t<KA>...> args(a...);

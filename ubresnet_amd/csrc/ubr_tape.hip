@@ -6,9 +6,43 @@
 // validated and tile configurations chosen once, at record time; a replay is a tight loop of hipLaunchKernel calls with
 // the fork/join structure of the two-stream backward expressed as event nodes.
 #include "ubr_host.h"
+#include <mutex>
+#include <set>
+#include <string>
+#include <string.h>
 
 static thread_local ubr_tape* g_tape = nullptr;
 ubr_tape* ubr_tape_current() { return g_tape; }
+
+// launch log: the distinct kernel symbols ubr_launch has issued since ubr_launch_log(1), process-wide
+std::atomic<int> g_ubr_launch_log_on{0};
+static std::mutex g_log_mu;
+static std::set<std::string> g_log_names;
+
+void ubr_launch_log_add(const void* fn, hipStream_t st) {
+  const char* nm = hipKernelNameRefByPtr(fn, st);
+  std::lock_guard<std::mutex> lk(g_log_mu);
+  g_log_names.insert(nm != nullptr ? nm : "?");
+}
+
+extern "C" int ubr_launch_log(int on) {
+  std::lock_guard<std::mutex> lk(g_log_mu);
+  g_log_names.clear();
+  g_ubr_launch_log_on.store(on ? 1 : 0, std::memory_order_relaxed);
+  return UBR_OK;
+}
+
+extern "C" int ubr_launch_log_read(char* buf, int n) {
+  std::lock_guard<std::mutex> lk(g_log_mu);
+  std::string all;
+  for (const auto& s : g_log_names) { all += s; all += '\n'; }
+  if (buf != nullptr && n > 0) {
+    const size_t m = all.size() < (size_t)(n - 1) ? all.size() : (size_t)(n - 1);
+    memcpy(buf, all.data(), m);
+    buf[m] = 0;
+  }
+  return (int)all.size() + 1;
+}
 
 extern "C" ubr_tape* ubr_tape_create(void) { return new ubr_tape(); }
 
