@@ -1,9 +1,10 @@
-"""Build libubresnet_hip.so (all HIP kernels + the C ABI) with hipcc for gfx950, in-tree.
+"""Build libubresnet_hip.so (all HIP kernels of the network + the C ABI) and libubresnet_post.so (event products of
+whole-view inference, a self-contained library of its own) with hipcc for gfx950, in-tree.
 
     python -m ubresnet_amd.build [--force]
 
-The shared library has NO PyTorch dependency: it is plain HIP behind include/ubresnet_hip.h.
-Objects are compiled in parallel, one per translation unit.
+The shared libraries have NO PyTorch dependency: they are plain HIP behind include/ubresnet_hip.h and
+include/ubresnet_post.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
 """
 import os
 import subprocess
@@ -15,6 +16,10 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libubresnet_hip.so")
 SOURCES = ["ubr_conv.hip", "ubr_aspp.hip", "ubr_wgrad.hip", "ubr_elem.hip", "ubr_head.hip", "ubr_tape.hip"]
 HEADERS = ["ubr_common.h", "ubr_host.h", os.path.join("..", "..", "include", "ubresnet_hip.h")]
+# the second library: not linked against the first; source_hash() covers the network sources only
+POST_OUT = os.path.join(HERE, "libubresnet_post.so")
+POST_SOURCES = ["ubr_post.hip"]
+POST_HEADERS = [os.path.join("..", "..", "include", "ubresnet_post.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=off"]
@@ -38,14 +43,20 @@ def _newer(target, deps):
 
 
 def build(force=False, verbose=True):
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS]
-    objs, jobs = [], []
-    for s in SOURCES:
-        src = os.path.join(CSRC, s)
-        obj = os.path.join(CSRC, s.replace(".hip", ".o"))
-        objs.append(obj)
-        if force or not _newer(obj, [src] + hdrs):
-            jobs.append([HIPCC] + FLAGS + ["-c", src, "-o", obj])
+    """compile what is out of date and link both libraries; -> path of the main library"""
+    libs = [(OUT, SOURCES, HEADERS), (POST_OUT, POST_SOURCES, POST_HEADERS)]
+    jobs, links = [], []
+    for out, sources, headers in libs:
+        hdrs = [os.path.join(CSRC, h) for h in headers]
+        objs, stale = [], False
+        for s in sources:
+            src = os.path.join(CSRC, s)
+            obj = os.path.join(CSRC, s.replace(".hip", ".o"))
+            objs.append(obj)
+            if force or not _newer(obj, [src] + hdrs):
+                jobs.append([HIPCC] + FLAGS + ["-c", src, "-o", obj])
+                stale = True
+        links.append((out, objs, stale))
 
     def run(cmd):
         if verbose:
@@ -61,12 +72,13 @@ def build(force=False, verbose=True):
                     raise RuntimeError("hipcc failed: " + " ".join(cmd))
                 if verbose and r.stderr.strip():
                     sys.stderr.write(r.stderr)
-    if jobs or force or not _newer(OUT, objs):
-        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT] + objs
-        cmd, r = run(cmd)
-        if r.returncode != 0:
-            sys.stderr.write(r.stdout + r.stderr)
-            raise RuntimeError("link failed")
+    for out, objs, stale in links:
+        if stale or force or not _newer(out, objs):
+            cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs
+            cmd, r = run(cmd)
+            if r.returncode != 0:
+                sys.stderr.write(r.stdout + r.stderr)
+                raise RuntimeError("link failed")
     return OUT
 
 

@@ -13,15 +13,55 @@ Mirrors the inference side of the reference:
     (rows {0,496}, cols {0,656,1312,1968,2624} for a 1008 x 3456 view).
     Crop and stitch are HIP kernels; the per-batch forward is captured once in a hipGraph and
     replayed (fixed shapes), tiles are independent so multi-GPU inference is replicas only.
+  * event products (``output="products"``): what the downstream chain keeps of the dense scores -- a class per pixel, its
+    probability and per-plane class counts, only where the wire signal is above threshold (tf/compare_caffe_to_tf.py:17,81-89,
+    ADC_THRESHOLD = 10.0) -- written by one fused kernel in place of the stitch (include/ubresnet_post.h).
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib as L
+from . import _post as PL
+
+
+class Products(NamedTuple):
+    """event products (ubp_stitch_products): `label` uint8 (fill_label where the pixel is not lit), `confidence` float16
+    (exp of the winning log-probability, +0 where not lit), `counts` int64 pixels per class among the lit ones"""
+    label: torch.Tensor
+    confidence: torch.Tensor
+    counts: torch.Tensor
+
+
+def _check_output(output):
+    if output not in ("scores", "products"):
+        raise ValueError("output must be 'scores' or 'products' (got %r)" % (output,))
+
+
+def _check_cover(tiles, P, rows, cols):
+    """the products path allocates label / confidence uninitialised: every pixel must lie in exactly one keep window"""
+    cover = torch.zeros((P, rows, cols), dtype=torch.uint8)
+    for (p, r0, c0, kr0, kr1, kc0, kc1) in tiles:
+        cover[p, r0 + kr0:min(r0 + kr1, rows), c0 + kc0:min(c0 + kc1, cols)] += 1
+    if int(cover.min()) != 1 or int(cover.max()) != 1:
+        raise ValueError("the keep windows of the tiling do not partition the %d x %d x %d view" % (P, rows, cols))
+
+
+def _desc7(tiles):
+    flat = [v for t in tiles for v in t]
+    return (C.c_int32 * len(flat))(*flat)
+
+
+def _stitch_products(logp, nclass, th, tw, tiles, adc, vplanes, adc_threshold, fill_label, prod: Products, P, rows, cols):
+    """one ubp_stitch_products launch on the current stream; `adc` is the float32 view the lit test reads (None: all lit)"""
+    use_adc = adc is not None and adc_threshold is not None
+    PL.check(PL.lib().ubp_stitch_products(logp.data_ptr(), nclass, th, tw, _desc7(tiles), len(tiles),
+                                          adc.data_ptr() if use_adc else None, vplanes, float(adc_threshold) if use_adc else 0.0,
+                                          prod.label.data_ptr(), prod.confidence.data_ptr(), prod.counts.data_ptr(),
+                                          fill_label, P, rows, cols, L.stream_ptr()), "stitch_products")
 
 
 def load_model(checkpointfile: Optional[str], device, num_classes: int = 4, inplanes: int = 16, input_channels: int = 1,
@@ -62,13 +102,36 @@ def save_checkpoint(state: dict, is_best: bool, p: int, filename: str = "checkpo
 
 
 @torch.no_grad()
-def segment_crops(model, adc: torch.Tensor, batch: int = 4) -> torch.Tensor:
-    """eval forward over pre-cropped images [n,C,H,W] in batches (deploy/run_ubresnet_precropped.py:115-182)"""
+def segment_crops(model, adc: torch.Tensor, batch: int = 4, output: str = "scores", adc_threshold: Optional[float] = 10.0,
+                  fill_label: int = 255):
+    """eval forward over pre-cropped images [n,C,H,W] in batches (deploy/run_ubresnet_precropped.py:115-182).
+    output="products": Products of [n,H,W] / [n,H,W] / [n,classes] instead of the scores; every image is one whole-image tile
+    of ubp_stitch_products and is lit where any of its channels is above `adc_threshold` (None: everywhere)."""
+    _check_output(output)
     model.eval()
-    outs = []
-    for i in range(0, adc.shape[0], batch):
-        outs.append(model(adc[i:i + batch]))
-    return torch.cat(outs, 0)
+    if output == "scores":
+        outs = []
+        for i in range(0, adc.shape[0], batch):
+            outs.append(model(adc[i:i + batch]))
+        return torch.cat(outs, 0)
+    L.require_cuda(adc, "adc")
+    if adc.dtype != torch.float32 or adc.dim() != 4:
+        raise RuntimeError("segment_crops: expected float32 [n,C,H,W], got %s %s" % (adc.dtype, tuple(adc.shape)))
+    adc = adc.contiguous()
+    n, cin, H, W = adc.shape
+    nclass = model.conv11.out_channels
+    prod = Products(torch.empty((n, H, W), dtype=torch.uint8, device=adc.device),
+                    torch.empty((n, H, W), dtype=torch.float16, device=adc.device),
+                    torch.zeros((n, nclass), dtype=torch.int64, device=adc.device))
+    for i in range(0, n, batch):
+        logp = model(adc[i:i + batch]).contiguous()
+        if logp.dtype != torch.float32:
+            raise RuntimeError("segment_crops: the model must return float32 log-probabilities (got %s)" % logp.dtype)
+        for j in range(0, logp.shape[0], PL.MAX_TILES):
+            m = min(PL.MAX_TILES, logp.shape[0] - j)
+            tiles = [(i + j + q, 0, 0, 0, H, 0, W) for q in range(m)]
+            _stitch_products(logp[j:j + m], nclass, H, W, tiles, adc, cin, adc_threshold, fill_label, prod, n, H, W)
+    return prod
 
 
 def regular_tiling(rows: int, cols: int, th: int = 512, tw: int = 832) -> Tuple[List[int], List[int]]:
@@ -120,13 +183,21 @@ class WholeViewSegmenter:
                                  dtype=torch.float16)
         scores = seg(view)          # view [planes,1,rows,cols] float32 on the GPU -> [planes,C,rows,cols]
 
+    With output="products" the call returns Products instead -- label and confidence [planes,rows,cols], counts [planes,C] --
+    and no [planes,C,rows,cols] buffer exists: one ubp_stitch_products launch per chunk of tiles takes the place of the stitch,
+    with the input view as the ADC of the lit test (`adc_threshold`, None = every pixel lit; unlit pixels get `fill_label`).
+
     A model whose first conv takes one channel (UResNet, deploy/run_ubresnet_wholeview.py) sees every plane's tiles on their
     own.  A model that takes `planes` channels (ASPP_ResNet, the three planes stacked as channels) sees one stacked tile per
-    position, and the result is one class-score map per event, [C,rows,cols].
+    position, and the result is one class-score map per event, [C,rows,cols] (products: [rows,cols] and [C]; a pixel is lit if
+    any plane is).
     """
 
     def __init__(self, model, rows: int, cols: int, planes: int = 3, tile=(512, 832), batch: int = 10,
-                 dtype: torch.dtype = torch.float16, use_graph: bool = True):
+                 dtype: torch.dtype = torch.float16, use_graph: bool = True, output: str = "scores",
+                 adc_threshold: Optional[float] = 10.0, fill_label: int = 255):
+        _check_output(output)
+        self.output, self.adc_threshold, self.fill_label = output, adc_threshold, fill_label
         self.model, self.rows, self.cols, self.planes = model, rows, cols, planes
         self.th, self.tw = tile
         if self.th % 32 or self.tw % 32:
@@ -142,6 +213,8 @@ class WholeViewSegmenter:
         if batch * cin > L.MAX_TILES:
             raise ValueError("batch * planes must be <= %d tile descriptors (UBR_MAX_TILES)" % L.MAX_TILES)
         self.nclass = model.conv11.out_channels
+        if output == "products":
+            _check_cover(self.tiles, 1 if self.stacked else planes, rows, cols)
         self._graph = None
         self._static_in = None
         self._static_out = None
@@ -152,8 +225,7 @@ class WholeViewSegmenter:
         return len(self.tiles)
 
     def _desc(self, tiles):
-        flat = [v for t in tiles for v in t]
-        return (C.c_int32 * len(flat))(*flat)
+        return _desc7(tiles)
 
     def _forward_batch(self, x):
         old = getattr(self.model, "compute_dtype", None)
@@ -188,7 +260,7 @@ class WholeViewSegmenter:
                 self._graph = g
 
     @torch.no_grad()
-    def __call__(self, view: torch.Tensor) -> torch.Tensor:
+    def __call__(self, view: torch.Tensor):
         L.require_cuda(view, "view")
         if view.dtype != torch.float32 or tuple(view.shape) != (self.planes, 1, self.rows, self.cols):
             raise RuntimeError("WholeViewSegmenter: expected float32 [%d,1,%d,%d], got %s %s"
@@ -196,7 +268,13 @@ class WholeViewSegmenter:
         view = view.contiguous()
         self._ensure_graph(view.device)
         oplanes = 1 if self.stacked else self.planes
-        out = torch.empty((oplanes, self.nclass, self.rows, self.cols), dtype=torch.float32, device=view.device)
+        products = self.output == "products"
+        if products:                     # label / confidence uninitialised: the tiling covers the view
+            out = Products(torch.empty((oplanes, self.rows, self.cols), dtype=torch.uint8, device=view.device),
+                           torch.empty((oplanes, self.rows, self.cols), dtype=torch.float16, device=view.device),
+                           torch.zeros((oplanes, self.nclass), dtype=torch.int64, device=view.device))
+        else:
+            out = torch.empty((oplanes, self.nclass, self.rows, self.cols), dtype=torch.float32, device=view.device)
         lib = L.lib()
         for i in range(0, len(self.tiles), self.batch):
             chunk = self.tiles[i:i + self.batch]
@@ -211,6 +289,12 @@ class WholeViewSegmenter:
                 scores = self._static_out
             else:
                 scores = self._forward_batch(self._static_in)
+            if products:
+                _stitch_products(scores, self.nclass, self.th, self.tw, chunk, view, self.planes if self.stacked else 1,
+                                 self.adc_threshold, self.fill_label, out, oplanes, self.rows, self.cols)
+                continue
             L.check(lib.ubr_stitch_tiles(scores.data_ptr(), self.nclass, self.th, self.tw, desc, n, out.data_ptr(),
                                          oplanes, self.rows, self.cols, L.stream_ptr()), "stitch_tiles")
+        if products:
+            return Products(*(t[0] for t in out)) if self.stacked else out
         return out[0] if self.stacked else out
