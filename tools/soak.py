@@ -2,18 +2,17 @@ import sys, os, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ubresnet_amd.models.ub_uresnet import UResNet
 from ubresnet_amd.training.pixelwise_nllloss import PixelWiseNLLLoss
+from ubresnet_amd.training import epoch
 from ubresnet_amd.optim import FlatAdam
-from ubresnet_amd import synthetic, metrics
+from ubresnet_amd.staging import BatchStager
+from ubresnet_amd import synthetic
 dev = torch.device("cuda:0"); torch.manual_seed(0)
-model = UResNet(num_classes=3, input_channels=1, inplanes=16).to(dev); model.compute_dtype = torch.bfloat16; model.train()
+model = UResNet(num_classes=3, input_channels=1, inplanes=16).to(dev); model.compute_dtype = torch.bfloat16
 crit = PixelWiseNLLLoss(); opt = FlatAdam(model, lr=1e-3, weight_decay=1e-4)
-ld = synthetic.SyntheticLArCVDataset(height=512, width=512, tag="train", nentries=64); ld.start(16)
-st = synthetic.DeviceStager(ld, 16, 512, 512, tag="train")
-t0 = time.perf_counter(); losses = []
-for i in range(300):
-    x, lab, wgt = st.next()
-    out = model.forward(x); loss = crit.forward(out, lab, wgt); opt.zero_grad(); loss.backward(); opt.step()
-    if i % 50 == 0 or i == 299:
-        losses.append(round(loss.item(), 4))
-        print(i, losses[-1], "mem GB %.2f" % (torch.cuda.max_memory_allocated() / 2**30), "acc", [round(a, 1) for a in metrics.accuracy(out.detach(), lab)], flush=True)
+ld = synthetic.SyntheticLArCVDataset(height=512, width=512, tag="train", nentries=64, cache=64); ld.start(16)
+t0 = time.perf_counter()
+with BatchStager(ld, 16, 512, 512, tag="train") as st:
+    for ep in range(6):
+        loss, acc = epoch.train(st, model, crit, opt, 50, iiter=ep, print_freq=25)
+        print(ep, round(loss, 4), "mem GB %.2f" % (torch.cuda.max_memory_allocated() / 2**30), "acc[1] %.1f" % acc, st.stage_times(), flush=True)
 torch.cuda.synchronize(); print("300 steps in %.1f s; finite params: %s" % (time.perf_counter() - t0, all(torch.isfinite(p).all().item() for p in model.parameters())))

@@ -1,10 +1,11 @@
-"""Build libubresnet_hip.so (all HIP kernels of the network + the C ABI) and libubresnet_post.so (event products of
-whole-view inference, a self-contained library of its own) with hipcc for gfx950, in-tree.
+"""Build libubresnet_hip.so (all HIP kernels of the network + the C ABI), libubresnet_post.so (event products of
+whole-view inference) and libubresnet_data.so (device-side batch preparation of the loader), the latter two self-contained
+libraries of their own, with hipcc for gfx950, in-tree.
 
     python -m ubresnet_amd.build [--force]
 
-The shared libraries have NO PyTorch dependency: they are plain HIP behind include/ubresnet_hip.h and
-include/ubresnet_post.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
+The shared libraries have NO PyTorch dependency: they are plain HIP behind include/ubresnet_hip.h,
+include/ubresnet_post.h and include/ubresnet_data.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
 """
 import os
 import subprocess
@@ -20,6 +21,10 @@ HEADERS = ["ubr_common.h", "ubr_host.h", os.path.join("..", "..", "include", "ub
 POST_OUT = os.path.join(HERE, "libubresnet_post.so")
 POST_SOURCES = ["ubr_post.hip"]
 POST_HEADERS = [os.path.join("..", "..", "include", "ubresnet_post.h")]
+# the third library: like the second, it links against neither of the others
+DATA_OUT = os.path.join(HERE, "libubresnet_data.so")
+DATA_SOURCES = ["ubr_data.hip"]
+DATA_HEADERS = [os.path.join("..", "..", "include", "ubresnet_data.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=off"]
@@ -43,8 +48,9 @@ def _newer(target, deps):
 
 
 def build(force=False, verbose=True):
-    """compile what is out of date and link both libraries; -> path of the main library"""
-    libs = [(OUT, SOURCES, HEADERS), (POST_OUT, POST_SOURCES, POST_HEADERS)]
+    """compile what is out of date and link the three libraries; -> path of the main library"""
+    libs = [(OUT, SOURCES, HEADERS), (POST_OUT, POST_SOURCES, POST_HEADERS),
+            (DATA_OUT, DATA_SOURCES, DATA_HEADERS)]
     jobs, links = [], []
     for out, sources, headers in libs:
         hdrs = [os.path.join(CSRC, h) for h in headers]

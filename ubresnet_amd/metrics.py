@@ -22,7 +22,12 @@ def confusion_matrix(output: torch.Tensor, target: torch.Tensor) -> torch.Tensor
 
 def accuracy(output: torch.Tensor, target: torch.Tensor):
     """Same return value as the reference's accuracy(): per-class recall in percent, then the total."""
-    cm = confusion_matrix(output, target).cpu().double()   # the single host sync
+    return accuracy_from_confusion(confusion_matrix(output, target).cpu())   # the single host sync
+
+
+def accuracy_from_confusion(cm: torch.Tensor):
+    """accuracy()'s list from a [C,C] confusion matrix already on the host (the epoch loop reads many of them back at once)"""
+    cm = cm.double()
     res = []
     for c in range(cm.shape[0]):
         n = cm[c].sum().item()

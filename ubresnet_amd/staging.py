@@ -1,0 +1,325 @@
+"""Threaded staging of loader batches: producer threads fill pinned slots, the device prepares the batch.
+
+The reference's loader runs two filler threads over two batch buffers (training/ubresnet_train.cfg:1-29,
+training/larcv1_interface.py:36-66) and ``prep_data`` (training/train_ubresnet2018_wlarcv2.py:576-615) then converts the
+labels on the host, inside the step.  ``BatchStager`` keeps the host's share of a batch to one loader call and one memcpy
+per array, both off the training thread:
+
+    loader = SyntheticLArCVDataset(512, 512, tag="train"); loader.start(16)
+    with BatchStager(loader, 16, 512, 512, tag="train") as stager:
+        adc, label, weight = stager.next()          # [B,P,H,W] float32, [B,H,W] int64, [B,H,W] float32 on the device
+
+* ``threads`` producers each take a free slot, then -- under one lock, because a loader is not thread-safe and batch order
+  must not depend on timing -- call ``loader[0]`` and take the batch's sequence number.  Outside the lock they copy the flat
+  float32 arrays as they are into the slot, ``[image | label wire | weight]`` in one packed (pinned) buffer.  Nothing is
+  converted on the host.
+* The thread that calls ``next()`` makes every GPU call: for the batch after the one it returns it issues, on a copy stream,
+  ONE host-to-device copy of the packed slot, ``ubd_prep_batch`` (libubresnet_data.so: float labels -> int64, the optional
+  ADC threshold, all-ones weights when the wire carries none) and an event.  A producer waits for that event before it
+  refills the slot; that is the only GPU call a producer makes.
+* Batches arrive in sequence order.  The returned tensors are fresh device memory per batch (``adc`` and ``weight`` are views
+  of the packed device copy) and stay valid for as long as the caller holds them.
+* No wait is unbounded: ``next()`` raises ``RuntimeError("Batch Loader timed out")`` (the reference's wording,
+  larcv1_interface.py) after ``timeout`` seconds; an exception in a producer is re-raised by the ``next()`` whose batch it
+  hit; ``close()`` stops and joins the (daemon) threads.
+
+``device=None`` runs the host half alone (``pin=False`` then needs no GPU at all): ``next()`` returns a ``HostBatch`` of numpy
+views of the slot, which stay valid until the following ``next()``, ``skip()`` or ``close()`` releases the slot.
+"""
+from __future__ import annotations
+
+import collections
+import threading
+import time
+
+import numpy as np
+
+__all__ = ["BatchStager", "HostBatch"]
+
+HostBatch = collections.namedtuple("HostBatch", ["seq", "image", "label_wire", "weight"])
+
+
+class _Slot(object):
+    __slots__ = ("index", "tensor", "array", "event", "has_weight")
+
+    def __init__(self, index, nfloats, pin):
+        self.index = index
+        self.tensor = None
+        if pin:
+            import torch
+            self.tensor = torch.empty(nfloats, dtype=torch.float32).pin_memory()
+            self.array = self.tensor.numpy()
+        else:
+            self.array = np.empty(nfloats, dtype=np.float32)
+        self.event = None              # recorded behind the last host-to-device copy that read this slot
+        self.has_weight = True
+
+
+class BatchStager(object):
+    def __init__(self, loader, batchsize, height, width, planes=1, tag="train", device="cuda", threads=2, slots=None,
+                 label_offset=0, adc_threshold=None, timeout=60.0, pin=True):
+        if threads < 1:
+            raise ValueError("BatchStager: threads must be >= 1")
+        self.loader, self.tag = loader, tag
+        self.shape = (int(batchsize), int(planes), int(height), int(width))
+        b, p, h, w = self.shape
+        self.npix = b * h * w
+        self.label_offset = int(label_offset)
+        self.adc_threshold = None if adc_threshold is None else float(adc_threshold)
+        self.timeout = float(timeout)
+        nslots = int(slots) if slots is not None else int(threads) + 1
+        if nslots < 1:
+            raise ValueError("BatchStager: slots must be >= 1")
+        self.device = None
+        if device is not None:
+            import torch
+            from . import _data
+            self._torch, self._data = torch, _data
+            self.device = torch.device(device)
+            if self.device.type != "cuda":
+                raise RuntimeError("BatchStager: the device stage needs a ROCm device (got %s); device=None runs the host half alone" % (self.device,))
+            if self.device.index is None:
+                self.device = torch.device("cuda", torch.cuda.current_device())
+            _data.lib()                                    # a missing library is an error now, not at the first batch
+            self.stream = torch.cuda.Stream(device=self.device)
+        self._slots = [_Slot(i, (p + 2) * self.npix, pin) for i in range(nslots)]
+        self._free = collections.deque(self._slots)
+        self._ready = {}                                   # sequence number -> filled slot, or the exception that batch hit
+        self._cond = threading.Condition()                 # guards _free, _ready, _stop, the stage times
+        self._loader_lock = threading.Lock()               # guards the loader and _seq
+        self._seq = 0                                      # next sequence number a producer takes
+        self._want = 0                                     # next sequence number the consumer takes
+        self._stop = False                                 # close(): every producer ends where it stands
+        self._halt = False                                 # a batch failed: no producer begins another one
+        self._closed = False
+        self._held = None                                  # host mode: the slot whose views the caller holds
+        self._inflight = None                              # device mode: (tensors, event) of the staged batch, or an exception
+        self._times = {"loader": [0.0, 0], "fill": [0.0, 0], "wait_slot": [0.0, 0]}
+        self._nthreads = int(threads)
+        self._threads = []
+
+    # ---- producers -------------------------------------------------------------------------------------------------------
+    def _start(self):
+        if not self._threads:
+            for i in range(self._nthreads):
+                t = threading.Thread(target=self._produce, name="BatchStager-%d" % i, daemon=True)
+                self._threads.append(t)
+                t.start()
+
+    def _note(self, what, dt):
+        with self._cond:
+            acc = self._times[what]
+            acc[0] += dt
+            acc[1] += 1
+
+    def _produce(self):
+        while True:
+            t0 = time.perf_counter()
+            with self._cond:
+                while not self._free and not (self._stop or self._halt):
+                    self._cond.wait(0.1)
+                if self._stop or self._halt:
+                    return
+                slot = self._free.popleft()
+            self._note("wait_slot", time.perf_counter() - t0)
+            seq = None
+            try:
+                with self._loader_lock:
+                    if self._stop or self._halt:
+                        return
+                    seq = self._seq
+                    self._seq += 1
+                    t0 = time.perf_counter()
+                    try:
+                        data = self.loader[0]
+                    except BaseException:
+                        self._halt = True                  # still under the lock: no producer calls the loader after this
+                        raise
+                    self._note("loader", time.perf_counter() - t0)
+                t0 = time.perf_counter()
+                if not self._wait_copied(slot):
+                    return
+                self._fill(slot, data)
+                self._note("fill", time.perf_counter() - t0)
+                result = slot
+            except BaseException as e:                     # delivered to the next() that asks for this batch
+                if seq is None:
+                    return
+                result = e
+            with self._cond:
+                self._ready[seq] = result
+                if not isinstance(result, _Slot):
+                    self._halt = True                      # batches already under way are still delivered, no new one is begun
+                self._cond.notify_all()
+            if not isinstance(result, _Slot):
+                return
+
+    def _wait_copied(self, slot):
+        """the host-to-device copy that last read this slot is done (the one GPU call of a producer); False: stopped"""
+        ev, slot.event = slot.event, None
+        if ev is None:
+            return True
+        deadline = time.monotonic() + self.timeout
+        while not ev.query():
+            if self._stop:
+                return False
+            if time.monotonic() > deadline:
+                raise RuntimeError("Batch Loader timed out")
+            time.sleep(0.0002)
+        return True
+
+    def _fill(self, slot, data):
+        b, p, h, w = self.shape
+        n = self.npix
+        parts = [("source_%s" % self.tag, 0, p * n), ("label_%s" % self.tag, p * n, n)]
+        key = "weight_%s" % self.tag
+        slot.has_weight = key in data
+        if slot.has_weight:
+            parts.append((key, (p + 1) * n, n))
+        for name, lo, cnt in parts:
+            a = data[name]
+            if a.dtype != np.float32 or a.size != cnt:
+                raise ValueError("BatchStager: %s is %s[%d], expected float32[%d]" % (name, a.dtype, a.size, cnt))
+            np.copyto(slot.array[lo:lo + cnt], a.reshape(-1))
+
+    # ---- consumer --------------------------------------------------------------------------------------------------------
+    def _take(self):
+        """-> the filled slot of the next batch in sequence order; raises what that batch hit, or the timeout"""
+        if self._closed:
+            raise RuntimeError("BatchStager is closed")
+        self._start()
+        seq = self._want
+        deadline = time.monotonic() + self.timeout
+        with self._cond:
+            while seq not in self._ready:
+                left = deadline - time.monotonic()
+                if left <= 0:
+                    break
+                self._cond.wait(min(left, 0.1))
+            got = self._ready.pop(seq, None)
+        if got is None:
+            self.close()
+            raise RuntimeError("Batch Loader timed out")
+        if not isinstance(got, _Slot):
+            self.close()
+            raise got
+        self._want = seq + 1
+        return got
+
+    def _release(self, slot):
+        with self._cond:
+            self._free.append(slot)
+            self._cond.notify_all()
+
+    def _issue(self):
+        """stage the next batch in sequence order on the copy stream; an exception becomes the staged batch"""
+        torch = self._torch
+        b, p, h, w = self.shape
+        n = self.npix
+        try:
+            slot = self._take()
+        except BaseException as e:
+            self._inflight = e
+            return
+        with torch.cuda.stream(self.stream):
+            packed = torch.empty((p + 2) * n, dtype=torch.float32, device=self.device)
+            label = torch.empty((b, h, w), dtype=torch.int64, device=self.device)
+            m = (p + 2) * n if slot.has_weight else (p + 1) * n
+            packed[:m].copy_(slot.tensor[:m] if slot.tensor is not None else torch.from_numpy(slot.array[:m]),
+                             non_blocking=slot.tensor is not None)
+            base = packed.data_ptr()
+            self._data.prep_batch(base + 4 * p * n, label.data_ptr(), n, self.label_offset, image=base, planes=p, hw=h * w,
+                                  threshold=self.adc_threshold, weight_fill=None if slot.has_weight else base + 4 * (p + 1) * n,
+                                  stream=self.stream.cuda_stream)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        slot.event = ev
+        self._release(slot)
+        self._inflight = ((packed[:p * n].view(b, p, h, w), label, packed[(p + 1) * n:].view(b, h, w)), ev)
+
+    def _staged(self):
+        """take the staged batch; what it hit while it was staged is raised by the call it belongs to"""
+        staged, self._inflight = self._inflight, None
+        if isinstance(staged, BaseException):
+            self.close()
+            raise staged
+        return staged
+
+    def next(self):
+        if isinstance(self._inflight, BaseException):
+            self._staged()
+        if self._closed:
+            raise RuntimeError("BatchStager is closed")
+        if self.device is None:
+            if self._held is not None:
+                self._release(self._held)
+                self._held = None
+            seq = self._want
+            slot = self._held = self._take()
+            b, p, h, w = self.shape
+            n = self.npix
+            a = slot.array
+            return HostBatch(seq, a[:p * n].reshape(b, p, h, w), a[p * n:(p + 1) * n].reshape(b, h, w),
+                             a[(p + 1) * n:].reshape(b, h, w) if slot.has_weight else None)
+        if self._inflight is None:
+            self._issue()
+        dev, ev = self._staged()
+        cur = self._torch.cuda.current_stream(self.device)
+        cur.wait_event(ev)
+        for t in dev:
+            t.record_stream(cur)
+        self._issue()
+        return dev
+
+    def skip(self, nbatches):
+        """advance the loader by `nbatches` batches without staging them on the device (resume from a checkpoint)"""
+        nbatches = int(nbatches)
+        if self._closed:
+            raise RuntimeError("BatchStager is closed")
+        if nbatches > 0 and self._inflight is not None:     # the staged batch is the first one skipped
+            self._staged()
+            nbatches -= 1
+        if not self._threads:                               # nothing fetched yet: the loader alone moves, no slot is filled
+            with self._loader_lock:
+                for _ in range(nbatches):
+                    self.loader[0]
+                    self._seq += 1
+                self._want = self._seq
+            return
+        if self._held is not None:
+            self._release(self._held)
+            self._held = None
+        for _ in range(nbatches):
+            self._release(self._take())
+
+    def stage_times(self):
+        """mean host milliseconds per batch of the producers' stages: {"loader", "fill", "wait_slot"} -> (mean ms, count)"""
+        with self._cond:
+            return {k: (1e3 * s / c if c else 0.0, c) for k, (s, c) in self._times.items()}
+
+    def close(self):
+        """stop and join the producers; idempotent.  A producer stuck inside the loader is left behind (it is a daemon)."""
+        self._closed = True
+        with self._cond:
+            self._stop = True
+            self._cond.notify_all()
+        deadline = time.monotonic() + 1.0
+        me = threading.current_thread()
+        for t in self._threads:
+            if t is not me:
+                t.join(max(0.0, deadline - time.monotonic()))
+        self._held = None
+        self._inflight = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1,0 +1,160 @@
+"""The reference's epoch loops over a batch stager: ``train`` (training/train_ubresnet2018_wlarcv2.py:298-397), ``validate``
+(:399-471, repaired: as checked in it reads undefined names) and ``AverageMeter`` (:482-497).
+
+    with BatchStager(loader, 16, 512, 512, tag="train") as stager:
+        for epoch in range(start, epochs):
+            loss, acc = train(stager, model, criterion, optimizer, nbatches, iiter=epoch)
+
+The meters are the reference's -- the average over the epoch of per-batch values, a batch's accuracies as
+``metrics.accuracy`` defines them -- but the loop does not stop the host at every step as ``loss.data.item()`` and
+``accuracy()`` do there (:353-355): each batch's loss and C x C confusion matrix go into a row of device buffers allocated
+once per epoch, and the rows are read back at every ``print_freq``-th batch and at the end.  No TensorBoard writer.
+"""
+from __future__ import annotations
+
+import time
+
+import torch
+
+from ubresnet_amd import metrics, ops
+
+__all__ = ["AverageMeter", "train", "validate"]
+
+
+class AverageMeter(object):
+    """Computes and stores the average and current value"""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.val = 0
+        self.avg = 0
+        self.sum = 0
+        self.count = 0
+
+    def update(self, val, n=1):
+        self.val = val
+        self.sum += val * n
+        self.count += n
+        self.avg = self.sum / self.count
+
+
+class _EpochRecord(object):
+    """per-batch loss and confusion matrix in device rows; drain() moves the rows not yet read into the meters, in order"""
+
+    def __init__(self, nbatches, nclasses):
+        self.nbatches, self.nclasses = int(nbatches), int(nclasses)
+        self.loss = self.cm = None
+        self.read = 0
+        self.losses = AverageMeter()
+        self.acc_list = [AverageMeter() for _ in range(self.nclasses + 1)]      # last accuracy is for total
+
+    def put(self, i, loss, pred, label):
+        C = pred.shape[1]
+        if C != self.nclasses:
+            raise ValueError("epoch: the model scores %d classes, nclasses=%d" % (C, self.nclasses))
+        if self.loss is None:
+            self.loss = torch.empty(self.nbatches, dtype=torch.float32, device=pred.device)
+            self.cm = torch.empty((self.nbatches, C * C), dtype=torch.int64, device=pred.device)
+            ops.zero_(self.cm)
+        pred, label = pred.detach(), label.detach()
+        if pred.dtype != torch.float32 or label.dtype != torch.int64:
+            raise RuntimeError("epoch: expected float32 scores and int64 labels")
+        self.loss[i:i + 1].copy_(loss.detach().reshape(1))
+        ops.confusion(pred.contiguous(), label.contiguous(), self.cm[i])
+
+    def drain(self, upto):
+        if self.loss is None or upto <= self.read:
+            return
+        C = self.nclasses
+        loss = self.loss[self.read:upto].cpu()                                   # the host waits here, and only here
+        cm = self.cm[self.read:upto].cpu()
+        for j in range(upto - self.read):
+            acc_values = metrics.accuracy_from_confusion(cm[j].view(C, C))
+            self.losses.update(loss[j].item())
+            for iacc, acc in enumerate(self.acc_list):
+                acc.update(acc_values[iacc])
+        self.read = upto
+
+
+def _flush(criterion):
+    flush = getattr(criterion, "flush", None)
+    if flush is not None:
+        flush()             # PixelWiseNLLLoss reports a bad label one call late: raise for the last batches too
+
+
+def train(stager, model, criterion, optimizer, nbatches, iiter=0, nclasses=3, print_freq=10, reducer=None, log=print):
+    """one epoch of `nbatches` train steps fed by `stager.next()`; -> (losses.avg, acc_list[1].avg) as the reference (:396)"""
+    batch_time, data_time = AverageMeter(), AverageMeter()
+    rec = _EpochRecord(nbatches, nclasses)
+
+    # switch to train mode
+    model.train()
+
+    for i in range(0, nbatches):
+        batchstart = time.time()
+        adc_t, label_t, weight_t = stager.next()
+        data_time.update(time.time() - batchstart)
+
+        # compute output
+        pred_t = model.forward(adc_t)
+        loss = criterion.forward(pred_t, label_t, weight_t)
+
+        # compute gradient and do the optimizer step
+        optimizer.zero_grad()
+        loss.backward()
+        if reducer is not None:
+            reducer.finish()
+        optimizer.step()
+
+        rec.put(i, loss, pred_t, label_t)
+        batch_time.update(time.time() - batchstart)           # host time: the device runs behind it between two read-backs
+
+        if i % print_freq == 0:
+            rec.drain(i + 1)
+            log("Train Iter: [%d][%d/%d]  Batch %.3f (%.3f)  Data %.3f (%.3f)\t || \tLoss %.3f (%.3f)\tAcc[total] %.3f (%.3f)" % (
+                iiter, i, nbatches, batch_time.val, batch_time.avg, data_time.val, data_time.avg,
+                rec.losses.val, rec.losses.avg, rec.acc_list[-1].val, rec.acc_list[1].avg))
+
+    rec.drain(nbatches)
+    _flush(criterion)
+    log("Train Iter [%d] Ave: Batch %.3f  Data %.3f ||  Loss %.3f Acc[Total] %.3f" % (
+        iiter, batch_time.avg, data_time.avg, rec.losses.avg, rec.acc_list[-1].avg))
+    return rec.losses.avg, rec.acc_list[1].avg
+
+
+def validate(stager, model, criterion, nbatches, iiter=0, nclasses=3, print_freq=10, log=print):
+    """`nbatches` batches of `stager.next()` through the model in eval mode, without gradients (the folded inference schedule);
+    -> float(acc_list[-1].avg), the average total accuracy in percent (:471)"""
+    batch_time, load_data = AverageMeter(), AverageMeter()
+    rec = _EpochRecord(nbatches, nclasses)
+
+    # switch to evaluate mode
+    model.eval()
+
+    with torch.no_grad():
+        for i in range(0, nbatches):
+            batchstart = time.time()
+            adc_t, label_t, weight_t = stager.next()
+            load_data.update(time.time() - batchstart)
+
+            # compute output
+            pred_t = model.forward(adc_t)
+            loss_t = criterion.forward(pred_t, label_t, weight_t)
+
+            rec.put(i, loss_t, pred_t, label_t)
+            batch_time.update(time.time() - batchstart)
+
+            if i % print_freq == 0:
+                rec.drain(i + 1)
+                log("Valid: [%d/%d]\tTime %.3f (%.3f)\tLoss %.3f (%.3f)\tAcc[Total] %.3f (%.3f)" % (
+                    i, nbatches, batch_time.val, batch_time.avg, rec.losses.val, rec.losses.avg,
+                    rec.acc_list[-1].val, rec.acc_list[-1].avg))
+
+    rec.drain(nbatches)
+    _flush(criterion)
+    log("Valid Iter %d sum: Batch %.3f\tData %.3f || Loss %.3f\tAcc[Total] %.3f" % (
+        iiter, batch_time.avg, load_data.avg, rec.losses.avg, rec.acc_list[-1].avg))
+    log("Test:Result* Acc[Total] %.3f\tLoss %.3f" % (rec.acc_list[-1].avg, rec.losses.avg))
+    return float(rec.acc_list[-1].avg)
