@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The bf16 16 x 1 x 512 x 512 UResNet train step fed five ways, alternated in one process: ms per step, wall clock.
+"""The bf16 16 x 1 x 512 x 512 UResNet train step fed six ways, alternated in one process: ms per step, wall clock.
 
     python tools/loaderprobe.py [--steps N] [--reps R] [--out FILE]
 
@@ -8,12 +8,14 @@
   (c) batch-1     staging.BatchStager, threads=1
   (d) batch-2     staging.BatchStager, threads=2
   (e) epoch       leg (d) driven by training.epoch.train (adds the per-batch confusion matrix and the read-backs)
+  (f) augment     leg (d) with augment=Augment(): uba_augment_batch in place of ubd_prep_batch behind the same copy
 
 The loader is SyntheticLArCVDataset with cache >= nentries, filled before anything is timed: the crop generator is a stand-in
 for the real input, its cost is kept out.  A leg runs `--steps` steps between two device synchronisations; median and spread
 (max - min) over `--reps` alternating repetitions.  The legs run in a child process under a time limit; a failure ends the run.
 For the BatchStager legs the producers' mean host time per batch is printed per stage: loader call (under the lock), slot
 fill (wait for the slot's last copy + memcpy into the pinned slot), wait for a free slot (idle: the consumer is the bottleneck).
+Leg (f) passes if its median is within the combined spread of legs (d) and (f) of leg (d)'s, measured in the same run.
 """
 import argparse
 import os
@@ -34,6 +36,7 @@ def legs(a, say):
     import torch
     torch.set_num_threads(8)
     from ubresnet_amd import synthetic
+    from ubresnet_amd.augment import Augment
     from ubresnet_amd.models.ub_uresnet import UResNet
     from ubresnet_amd.optim import FlatAdam
     from ubresnet_amd.staging import BatchStager
@@ -64,7 +67,8 @@ def legs(a, say):
     resident = tuple(torch.from_numpy(t).to(dev) for t in synthetic.make_batch(B, H, W, 1000))
     old = synthetic.DeviceStager(loader(), B, H, W, tag="train")
     st = {1: BatchStager(loader(), B, H, W, tag="train", threads=1), 2: BatchStager(loader(), B, H, W, tag="train", threads=2),
-          "e": BatchStager(loader(), B, H, W, tag="train", threads=2)}
+          "e": BatchStager(loader(), B, H, W, tag="train", threads=2),
+          "f": BatchStager(loader(), B, H, W, tag="train", threads=2, augment=Augment())}
 
     def run(leg, n):
         torch.cuda.synchronize()
@@ -75,8 +79,8 @@ def legs(a, say):
         elif leg == "b":
             for _ in range(n):
                 step(*old.next())
-        elif leg in ("c", "d"):
-            s = st[1 if leg == "c" else 2]
+        elif leg in ("c", "d", "f"):
+            s = st[{"c": 1, "d": 2, "f": "f"}[leg]]
             for _ in range(n):
                 step(*s.next())
         else:
@@ -85,7 +89,7 @@ def legs(a, say):
         return (time.perf_counter() - t0) * 1e3 / n
 
     names = {"a": "resident batch", "b": "DeviceStager", "c": "BatchStager threads=1", "d": "BatchStager threads=2",
-             "e": "epoch.train over (d)"}
+             "e": "epoch.train over (d)", "f": "(d) with Augment()"}
     for leg in names:
         run(leg, 4)                        # warm-up: kernel selection, pinned slots, allocator
     runs = {leg: [] for leg in names}
@@ -105,7 +109,7 @@ def legs(a, say):
             % (leg, name, med[leg], max(r) - min(r), med[leg] / med["a"], " ".join("%.2f" % x for x in r)))
     say("# producers' host time per batch, mean ms (batches): loader call | slot fill | wait for a free slot")
     stage = {}
-    for leg, key in (("c", 1), ("d", 2), ("e", "e")):
+    for leg, key in (("c", 1), ("d", 2), ("e", "e"), ("f", "f")):
         t = stage[leg] = st[key].stage_times()
         say("(%s) loader %.2f (%d) | fill %.2f (%d) | wait_slot %.2f (%d)" % (
             leg, t["loader"][0], t["loader"][1], t["fill"][0], t["fill"][1], t["wait_slot"][0], t["wait_slot"][1]))
@@ -122,6 +126,17 @@ def legs(a, say):
             say("target (%s) <= %.2f x (a): MISSED at x%.3f (%.2f ms over the %.2f ms step); producers need max(loader, (loader + fill) / 2) = "
                 "%.2f ms per batch: %s bounds the loop" % (leg, TARGET, ratio, med[leg] - med["a"], med["a"], bound,
                                                           "the loader call" if t["loader"][0] >= serial / 2.0 else "the slot fill"))
+
+
+    spread = {leg: max(runs[leg]) - min(runs[leg]) for leg in ("d", "f")}
+    delta, allowed = med["f"] - med["d"], spread["d"] + spread["f"]
+    if abs(delta) <= allowed:
+        say("augment (f) against (d): %+.2f ms, within the two legs' combined spread of %.2f ms: PASSED" % (delta, allowed))
+    else:
+        t = stage["f"]
+        say("augment (f) against (d): %+.2f ms, outside the two legs' combined spread of %.2f ms: %s; producers of (f): loader %.2f | "
+            "fill %.2f | wait_slot %.2f ms per batch" % (delta, allowed, "FASTER" if delta < 0 else "MISSED", t["loader"][0], t["fill"][0],
+                                                         t["wait_slot"][0]))
 
 
 def main():

@@ -1,11 +1,11 @@
 """Build libubresnet_hip.so (all HIP kernels of the network + the C ABI), libubresnet_post.so (event products of
-whole-view inference) and libubresnet_data.so (device-side batch preparation of the loader), the latter two self-contained
-libraries of their own, with hipcc for gfx950, in-tree.
+whole-view inference), libubresnet_data.so (device-side batch preparation of the loader) and libubresnet_aug.so (device-side
+augmentation of training batches), the latter three self-contained libraries of their own, with hipcc for gfx950, in-tree.
 
     python -m ubresnet_amd.build [--force]
 
 The shared libraries have NO PyTorch dependency: they are plain HIP behind include/ubresnet_hip.h,
-include/ubresnet_post.h and include/ubresnet_data.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
+include/ubresnet_post.h, include/ubresnet_data.h and include/ubresnet_aug.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
 """
 import os
 import subprocess
@@ -25,6 +25,10 @@ POST_HEADERS = [os.path.join("..", "..", "include", "ubresnet_post.h")]
 DATA_OUT = os.path.join(HERE, "libubresnet_data.so")
 DATA_SOURCES = ["ubr_data.hip"]
 DATA_HEADERS = [os.path.join("..", "..", "include", "ubresnet_data.h")]
+# the fourth library: it links against none of the others either
+AUG_OUT = os.path.join(HERE, "libubresnet_aug.so")
+AUG_SOURCES = ["ubr_aug.hip"]
+AUG_HEADERS = [os.path.join("..", "..", "include", "ubresnet_aug.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=off"]
@@ -48,9 +52,9 @@ def _newer(target, deps):
 
 
 def build(force=False, verbose=True):
-    """compile what is out of date and link the three libraries; -> path of the main library"""
+    """compile what is out of date and link the four libraries; -> path of the main library"""
     libs = [(OUT, SOURCES, HEADERS), (POST_OUT, POST_SOURCES, POST_HEADERS),
-            (DATA_OUT, DATA_SOURCES, DATA_HEADERS)]
+            (DATA_OUT, DATA_SOURCES, DATA_HEADERS), (AUG_OUT, AUG_SOURCES, AUG_HEADERS)]
     jobs, links = [], []
     for out, sources, headers in libs:
         hdrs = [os.path.join(CSRC, h) for h in headers]

@@ -25,8 +25,10 @@ def accuracy(output: torch.Tensor, target: torch.Tensor):
     return accuracy_from_confusion(confusion_matrix(output, target).cpu())   # the single host sync
 
 
-def accuracy_from_confusion(cm: torch.Tensor):
-    """accuracy()'s list from a [C,C] confusion matrix already on the host (the epoch loop reads many of them back at once)"""
+def accuracy_from_confusion(cm: torch.Tensor, track_shower: bool = False):
+    """accuracy()'s list from a [C,C] confusion matrix already on the host (the epoch loop reads many of them back at once).
+    `track_shower` appends the fifth figure of the LArCV1 drivers' accuracy() (training/train_ubresnet2018_wlarcv1.py:584):
+    the correct pixels of classes 1 and 2 over the pixels of classes 1 and 2, in percent; 0.0 where there are none."""
     cm = cm.double()
     res = []
     for c in range(cm.shape[0]):
@@ -34,6 +36,11 @@ def accuracy_from_confusion(cm: torch.Tensor):
         res.append(100.0 * cm[c, c].item() / n if n > 0 else 0.0)
     tot = cm.sum().item()
     res.append(100.0 * cm.diag().sum().item() / tot if tot > 0 else 0.0)
+    if track_shower:
+        if cm.shape[0] < 3:
+            raise ValueError("accuracy_from_confusion: track_shower needs classes 1 and 2")
+        n = (cm[1].sum() + cm[2].sum()).item()
+        res.append(100.0 * (cm[1, 1] + cm[2, 2]).item() / n if n > 0 else 0.0)
     return res
 
 

@@ -23,8 +23,17 @@ per array, both off the training thread:
   larcv1_interface.py) after ``timeout`` seconds; an exception in a producer is re-raised by the ``next()`` whose batch it
   hit; ``close()`` stops and joins the (daemon) threads.
 
+``augment=Augment(...)`` (ubresnet_amd/augment.py) pads, flips and crops every image of a training batch on the device, with
+its label and weight: behind the same one copy the consumer launches ``uba_augment_batch`` (libubresnet_aug.so) INSTEAD of
+``ubd_prep_batch`` -- it does the label conversion and the threshold as well -- with ``augment.params(seq, B)``, `seq` the
+batch's sequence number.  Still one copy, one launch and one event per batch; the three tensors are fresh allocations and the
+packed device copy is dropped behind the launch (it was allocated and used on the copy stream only).  What a batch looks like
+depends on ``(augment.seed, seq)`` alone, so neither thread timing nor ``skip(n)`` changes it.  A validation stager takes no
+``augment``.
+
 ``device=None`` runs the host half alone (``pin=False`` then needs no GPU at all): ``next()`` returns a ``HostBatch`` of numpy
-views of the slot, which stay valid until the following ``next()``, ``skip()`` or ``close()`` releases the slot.
+views of the slot, which stay valid until the following ``next()``, ``skip()`` or ``close()`` releases the slot.  Nothing is
+augmented there: ``stager.augment.params(batch.seq, B)`` gives the caller the batch's parameters.
 """
 from __future__ import annotations
 
@@ -57,7 +66,7 @@ class _Slot(object):
 
 class BatchStager(object):
     def __init__(self, loader, batchsize, height, width, planes=1, tag="train", device="cuda", threads=2, slots=None,
-                 label_offset=0, adc_threshold=None, timeout=60.0, pin=True):
+                 label_offset=0, adc_threshold=None, timeout=60.0, pin=True, augment=None):
         if threads < 1:
             raise ValueError("BatchStager: threads must be >= 1")
         self.loader, self.tag = loader, tag
@@ -67,6 +76,7 @@ class BatchStager(object):
         self.label_offset = int(label_offset)
         self.adc_threshold = None if adc_threshold is None else float(adc_threshold)
         self.timeout = float(timeout)
+        self.augment = augment
         nslots = int(slots) if slots is not None else int(threads) + 1
         if nslots < 1:
             raise ValueError("BatchStager: slots must be >= 1")
@@ -81,6 +91,12 @@ class BatchStager(object):
             if self.device.index is None:
                 self.device = torch.device("cuda", torch.cuda.current_device())
             _data.lib()                                    # a missing library is an error now, not at the first batch
+            if augment is not None:
+                from . import _aug
+                self._aug = _aug
+                _aug.lib()
+                if b > _aug.MAX_BATCH:
+                    raise ValueError("BatchStager: augment takes at most %d images per batch (got %d)" % (_aug.MAX_BATCH, b))
             self.stream = torch.cuda.Stream(device=self.device)
         self._slots = [_Slot(i, (p + 2) * self.npix, pin) for i in range(nslots)]
         self._free = collections.deque(self._slots)
@@ -221,6 +237,9 @@ class BatchStager(object):
         except BaseException as e:
             self._inflight = e
             return
+        if self.augment is not None:
+            self._issue_augmented(slot, self._want - 1)
+            return
         with torch.cuda.stream(self.stream):
             packed = torch.empty((p + 2) * n, dtype=torch.float32, device=self.device)
             label = torch.empty((b, h, w), dtype=torch.int64, device=self.device)
@@ -236,6 +255,32 @@ class BatchStager(object):
         slot.event = ev
         self._release(slot)
         self._inflight = ((packed[:p * n].view(b, p, h, w), label, packed[(p + 1) * n:].view(b, h, w)), ev)
+
+    def _issue_augmented(self, slot, seq):
+        """_issue with an Augment: the same copy, then uba_augment_batch out of the packed copy into three fresh tensors"""
+        torch = self._torch
+        b, p, h, w = self.shape
+        n = self.npix
+        aug = self.augment
+        with torch.cuda.stream(self.stream):
+            packed = torch.empty((p + 2) * n, dtype=torch.float32, device=self.device)
+            adc = torch.empty((b, p, h, w), dtype=torch.float32, device=self.device)
+            label = torch.empty((b, h, w), dtype=torch.int64, device=self.device)
+            weight = torch.empty((b, h, w), dtype=torch.float32, device=self.device)
+            m = (p + 2) * n if slot.has_weight else (p + 1) * n
+            packed[:m].copy_(slot.tensor[:m] if slot.tensor is not None else torch.from_numpy(slot.array[:m]),
+                             non_blocking=slot.tensor is not None)
+            base = packed.data_ptr()
+            self._aug.augment_batch(base, base + 4 * p * n, base + 4 * (p + 1) * n if slot.has_weight else None,
+                                    adc.data_ptr(), label.data_ptr(), weight.data_ptr(), self.shape, aug.pad,
+                                    aug.params(seq, b), label_offset=self.label_offset, threshold=self.adc_threshold,
+                                    pad_label=aug.pad_label, pad_weight=aug.pad_weight, stream=self.stream.cuda_stream)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        del packed                                          # allocated and used on the copy stream only: its reuse is ordered
+        slot.event = ev
+        self._release(slot)
+        self._inflight = ((adc, label, weight), ev)
 
     def _staged(self):
         """take the staged batch; what it hit while it was staged is raised by the call it belongs to"""

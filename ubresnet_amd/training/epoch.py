@@ -9,6 +9,10 @@ The meters are the reference's -- the average over the epoch of per-batch values
 ``metrics.accuracy`` defines them -- but the loop does not stop the host at every step as ``loss.data.item()`` and
 ``accuracy()`` do there (:353-355): each batch's loss and C x C confusion matrix go into a row of device buffers allocated
 once per epoch, and the rows are read back at every ``print_freq``-th batch and at the end.  No TensorBoard writer.
+
+``track_shower=True`` keeps one more meter, the fifth figure of the LArCV1 drivers' ``accuracy()``
+(training/train_ubresnet2018_wlarcv1.py:584: classes 1 and 2 together), appends it to the log lines and to what is returned:
+``train`` -> (loss, acc[1], track/shower), ``validate`` -> (total, track/shower).
 """
 from __future__ import annotations
 
@@ -43,8 +47,9 @@ class AverageMeter(object):
 class _EpochRecord(object):
     """per-batch loss and confusion matrix in device rows; drain() moves the rows not yet read into the meters, in order"""
 
-    def __init__(self, nbatches, nclasses):
+    def __init__(self, nbatches, nclasses, track_shower=False):
         self.nbatches, self.nclasses = int(nbatches), int(nclasses)
+        self.track_shower = AverageMeter() if track_shower else None            # the fifth meter, apart from acc_list
         self.loss = self.cm = None
         self.read = 0
         self.losses = AverageMeter()
@@ -64,6 +69,11 @@ class _EpochRecord(object):
         self.loss[i:i + 1].copy_(loss.detach().reshape(1))
         ops.confusion(pred.contiguous(), label.contiguous(), self.cm[i])
 
+    def tail(self):
+        """what track_shower adds to a log line"""
+        ts = self.track_shower
+        return "" if ts is None else "\tAcc[trk/shr] %.3f (%.3f)" % (ts.val, ts.avg)
+
     def drain(self, upto):
         if self.loss is None or upto <= self.read:
             return
@@ -71,10 +81,12 @@ class _EpochRecord(object):
         loss = self.loss[self.read:upto].cpu()                                   # the host waits here, and only here
         cm = self.cm[self.read:upto].cpu()
         for j in range(upto - self.read):
-            acc_values = metrics.accuracy_from_confusion(cm[j].view(C, C))
+            acc_values = metrics.accuracy_from_confusion(cm[j].view(C, C), track_shower=self.track_shower is not None)
             self.losses.update(loss[j].item())
             for iacc, acc in enumerate(self.acc_list):
                 acc.update(acc_values[iacc])
+            if self.track_shower is not None:
+                self.track_shower.update(acc_values[C + 1])
         self.read = upto
 
 
@@ -84,10 +96,12 @@ def _flush(criterion):
         flush()             # PixelWiseNLLLoss reports a bad label one call late: raise for the last batches too
 
 
-def train(stager, model, criterion, optimizer, nbatches, iiter=0, nclasses=3, print_freq=10, reducer=None, log=print):
-    """one epoch of `nbatches` train steps fed by `stager.next()`; -> (losses.avg, acc_list[1].avg) as the reference (:396)"""
+def train(stager, model, criterion, optimizer, nbatches, iiter=0, nclasses=3, print_freq=10, reducer=None, log=print,
+          track_shower=False):
+    """one epoch of `nbatches` train steps fed by `stager.next()`; -> (losses.avg, acc_list[1].avg) as the reference (:396),
+    with `track_shower` -> (losses.avg, acc_list[1].avg, track/shower avg)"""
     batch_time, data_time = AverageMeter(), AverageMeter()
-    rec = _EpochRecord(nbatches, nclasses)
+    rec = _EpochRecord(nbatches, nclasses, track_shower)
 
     # switch to train mode
     model.train()
@@ -115,20 +129,22 @@ def train(stager, model, criterion, optimizer, nbatches, iiter=0, nclasses=3, pr
             rec.drain(i + 1)
             log("Train Iter: [%d][%d/%d]  Batch %.3f (%.3f)  Data %.3f (%.3f)\t || \tLoss %.3f (%.3f)\tAcc[total] %.3f (%.3f)" % (
                 iiter, i, nbatches, batch_time.val, batch_time.avg, data_time.val, data_time.avg,
-                rec.losses.val, rec.losses.avg, rec.acc_list[-1].val, rec.acc_list[1].avg))
+                rec.losses.val, rec.losses.avg, rec.acc_list[-1].val, rec.acc_list[1].avg) + rec.tail())
 
     rec.drain(nbatches)
     _flush(criterion)
     log("Train Iter [%d] Ave: Batch %.3f  Data %.3f ||  Loss %.3f Acc[Total] %.3f" % (
-        iiter, batch_time.avg, data_time.avg, rec.losses.avg, rec.acc_list[-1].avg))
+        iiter, batch_time.avg, data_time.avg, rec.losses.avg, rec.acc_list[-1].avg) + rec.tail())
+    if track_shower:
+        return rec.losses.avg, rec.acc_list[1].avg, rec.track_shower.avg
     return rec.losses.avg, rec.acc_list[1].avg
 
 
-def validate(stager, model, criterion, nbatches, iiter=0, nclasses=3, print_freq=10, log=print):
+def validate(stager, model, criterion, nbatches, iiter=0, nclasses=3, print_freq=10, log=print, track_shower=False):
     """`nbatches` batches of `stager.next()` through the model in eval mode, without gradients (the folded inference schedule);
-    -> float(acc_list[-1].avg), the average total accuracy in percent (:471)"""
+    -> float(acc_list[-1].avg), the average total accuracy in percent (:471), with `track_shower` -> (that, track/shower avg)"""
     batch_time, load_data = AverageMeter(), AverageMeter()
-    rec = _EpochRecord(nbatches, nclasses)
+    rec = _EpochRecord(nbatches, nclasses, track_shower)
 
     # switch to evaluate mode
     model.eval()
@@ -150,11 +166,13 @@ def validate(stager, model, criterion, nbatches, iiter=0, nclasses=3, print_freq
                 rec.drain(i + 1)
                 log("Valid: [%d/%d]\tTime %.3f (%.3f)\tLoss %.3f (%.3f)\tAcc[Total] %.3f (%.3f)" % (
                     i, nbatches, batch_time.val, batch_time.avg, rec.losses.val, rec.losses.avg,
-                    rec.acc_list[-1].val, rec.acc_list[-1].avg))
+                    rec.acc_list[-1].val, rec.acc_list[-1].avg) + rec.tail())
 
     rec.drain(nbatches)
     _flush(criterion)
     log("Valid Iter %d sum: Batch %.3f\tData %.3f || Loss %.3f\tAcc[Total] %.3f" % (
         iiter, batch_time.avg, load_data.avg, rec.losses.avg, rec.acc_list[-1].avg))
-    log("Test:Result* Acc[Total] %.3f\tLoss %.3f" % (rec.acc_list[-1].avg, rec.losses.avg))
+    log("Test:Result* Acc[Total] %.3f\tLoss %.3f" % (rec.acc_list[-1].avg, rec.losses.avg) + rec.tail())
+    if track_shower:
+        return float(rec.acc_list[-1].avg), float(rec.track_shower.avg)
     return float(rec.acc_list[-1].avg)
