@@ -40,7 +40,7 @@ extern "C" {
 #define UBR_STAT_SLOTS 32
 /* The BatchNorm-backward / block-tail reduce passes launch at most 1024 workgroups and use only the first UBR_RED_SLOTS
  * stripes of their buffer (the others stay zero, so ubr_bn_bwd_finalize still sums all of them): the apply passes with the
- * finalize fused (ubr_*_apply_fin) re-sum the stripes in every workgroup, and 8 stripes keep that to 128 B per channel. */
+ * finalize fused (UBR_PASS_APPLY_FIN) re-sum the stripes in every workgroup, and 8 stripes keep that to 128 B per channel. */
 #define UBR_RED_SLOTS 8
 
 /* Strided NHWC view: element (n,y,x,c) lives at p + n*sn + y*sy + x*sx + c (strides in elements). */
@@ -102,14 +102,14 @@ typedef struct {
                               * this is the whole BasicBlock tail (models/common_layers.py:47-56) */
   int32_t pad_;
   /* Training, data-gradient convs (both optional; zero-initialise the descriptor):
-   * addend_mask -- the addend is gated by the ReLU bit mask of a block tail (ubr_block_tail_fwd_masked: one byte per output
+   * addend_mask -- the addend is gated by the ReLU bit mask of a block tail (ubr_block_tail_fwd_desc.relu_mask: one byte per output
    *   pixel and 16-byte channel unit, [N*OH*OW][Cout / channels-per-unit], bit e = channel e of the unit):
    *   out = conv + addend * bit.  This re-forms the skip gradient g_out*[out>0] of an identity block from g_out and the mask, so
-   *   the tail's backward need not write it (ubr_block_tail_bwd_apply_fin with g_sc == NULL).
+   *   the tail's backward need not write it (ubr_block_tail_bwd, UBR_PASS_APPLY_FIN with g_sc absent).
    * bnb_c -- BatchNorm-backward sums in the epilogue: `stats` then receives, per output channel, sum g_y and sum g_y*xhat of
-   *   a = max(bn(c), 0)  (g = this conv's output rounded to the storage type, exactly what a separate ubr_bn_bwd_reduce over
+   *   a = max(bn(c), 0)  (g = this conv's output rounded to the storage type, exactly what a separate UBR_PASS_REDUCE over
    *   the stored tensor reads; g_y = g*[bn(c) > 0]; xhat = (c - mean)*invstd) instead of the output's own statistics: the
-   *   reduce pass of ubr_bn_bwd_* for one extra read of c.  c is a view of the OUTPUT grid.  Stripes: UBR_RED_SLOTS. */
+   *   reduce pass of ubr_bn_bwd for one extra read of c.  c is a view of the OUTPUT grid.  Stripes: UBR_RED_SLOTS. */
   const uint8_t* addend_mask;
   ubr_tensor bnb_c;
   const float *bnb_mean, *bnb_scale, *bnb_shift, *bnb_invstd;
@@ -123,7 +123,7 @@ typedef struct {
   int32_t pad3_;
   int64_t phase_yoff[4], phase_aoff[4];
   int32_t stats_slots;       /* stripes of `stats` to use: 0 = UBR_STAT_SLOTS; UBR_RED_SLOTS when the consumer sums them itself
-                              * (ubr_block_tail_fwd_fin).  bnb_c always uses UBR_RED_SLOTS. */
+                              * (ubr_block_tail_fwd with fin2).  bnb_c always uses UBR_RED_SLOTS. */
   int32_t pad2_;
 } ubr_conv_desc;
 
@@ -263,57 +263,57 @@ int ubr_bn_eval_affine(const float* gamma, const float* beta, const float* runni
                        const float* running_var, float eps, int C, float* scale, float* shift,
                        float* mean, float* invstd, void* stream);
 
-/* Backward of  a = max(bn(c), lo)  given g_a (sum of up to two tensors):
- *   pass 1 (reduce): red[c] += sum g_y, red[C+c] += sum g_y*xhat      (g_y = g_a * [bn(c) > lo])
- *   finalize       : dgamma, dbeta, and the per-channel constants of pass 2
- *   pass 2 (apply) : g_c = scale * (g_y - k1 - xhat*k2)
- * relu = 0 drops the mask (BatchNorm with no ReLU, e.g. bnpass, models/common_layers.py:50-51). */
-int ubr_bn_bwd_reduce(int dtype, int64_t npix, int C, const void* ga, int64_t ga_ps, const void* ga2, int64_t ga2_ps,
-                      const void* c, int64_t c_ps, const float* scale, const float* shift, const float* mean,
-                      const float* invstd, int relu, double* red, void* stream);
-int ubr_bn_bwd_finalize(const double* red, double count, const float* scale /*gamma*invstd*/, const float* invstd,
-                        int C, float* dgamma, float* dbeta, int accumulate, float* k1, float* k2, void* stream);
-int ubr_bn_bwd_apply(int dtype, int64_t npix, int C, const void* ga, int64_t ga_ps, const void* ga2, int64_t ga2_ps,
-                     const void* c, int64_t c_ps, const float* scale, const float* shift, const float* mean,
-                     const float* invstd, int relu, const float* k1, const float* k2,
-                     void* gc, int64_t gc_ps, void* stream);
+/* NHWC tensor seen as [npix][ps]: base pointer and pixel stride in elements; p NULL = absent.  A tensor that is present is
+ * 16-byte aligned, ps >= C with ps * element size a multiple of 16, and npix * ps * element size < 2 GiB (32-bit buffer offsets). */
+typedef struct { void* p; int64_t ps; } ubr_pix;
 
-/* pass 2 with the finalize fused: every workgroup forms k1 = sum(g_y)/count, k2 = sum(g_y*xhat)/count from the reduce pass's
- * stripes itself and workgroup 0 writes dgamma / dbeta (either may be NULL) -- one launch less on the dependent chain.
- * Needs 8*C bytes of LDS (C <= 8192). */
-int ubr_bn_bwd_apply_fin(int dtype, int64_t npix, int C, const void* ga, int64_t ga_ps, const void* ga2, int64_t ga2_ps,
-                         const void* c, int64_t c_ps, const float* scale, const float* shift, const float* mean,
-                         const float* invstd, int relu, const double* red, double count, float* dgamma, float* dbeta,
-                         void* gc, int64_t gc_ps, void* stream);
+/* Backward of  a = max(bn(c), lo)  given g_a (sum of up to two tensors), as passes over the tensors:
+ *   finalize (ubr_bn_bwd_finalize, between REDUCE and APPLY): dgamma, dbeta, and the per-channel constants k1, k2 of APPLY
+ * Every fp64 buffer `red` is [UBR_STAT_SLOTS][2*C] (sum g_y | sum g_y*xhat) of which UBR_RED_SLOTS stripes are used. */
+#define UBR_PASS_REDUCE 0      /* red[c] += sum g_y, red[C+c] += sum g_y*xhat      (g_y = g_a * [bn(c) > lo]) */
+#define UBR_PASS_APPLY 1       /* g_c = scale * (g_y - k1 - xhat*k2) */
+#define UBR_PASS_APPLY_FIN 2   /* APPLY with the finalize fused: every workgroup forms k1 = sum(g_y)/count, k2 = sum(g_y*xhat)/count
+                                * from the reduce pass's stripes itself and workgroup 0 writes dgamma / dbeta -- one launch less on
+                                * the dependent chain */
+#define UBR_PASS_FROZEN 3      /* frozen BatchNorm (module in eval mode, running statistics): mean / invstd are constants, so
+                                *   g_c = scale * g_y,  dgamma = sum g_y*xhat,  dbeta = sum g_y
+                                * and the data gradient waits for no reduction: reduce and apply are ONE pass, which reads every
+                                * operand once, writes the data gradient(s) and adds the sums into the same striped buffers as
+                                * REDUCE.  Per element the arithmetic is that of APPLY with k1 = k2 = 0.
+                                * ubr_bn_bwd_finalize_frozen then gives dgamma / dbeta, off the dependent chain */
+
+/* One BatchNorm site; C floats each; what a pass does not use is NULL. */
+typedef struct {
+  const float *scale, *shift, *mean, *invstd;   /* gamma*invstd, beta, mean, invstd: every pass */
+  const float *k1, *k2;                         /* APPLY: both */
+  double* red;                                  /* REDUCE, FROZEN: added to; APPLY_FIN: read */
+  float *dgamma, *dbeta;                        /* APPLY_FIN: written; either may be NULL */
+} ubr_bn_site;
+
+int ubr_bn_bwd_finalize(const double* red, double count, int C, float* dgamma, float* dbeta, int accumulate,
+                        float* k1, float* k2, void* stream);
+
+/* A single site.  ga2: optional second gradient tensor; gc: the data gradient (every pass but REDUCE).
+ * relu = 0 drops the mask (BatchNorm with no ReLU, e.g. bnpass, models/common_layers.py:50-51).
+ * FROZEN: bn.red may be NULL (the conv that produced `ga` already reduced, ubr_conv_desc.bnb_c): pure apply.
+ * LDS: APPLY_FIN needs 8*C bytes (C <= 8192); REDUCE and FROZEN with bn.red 16*C (32*C where the unit count allows the register
+ * flush), for FROZEN at most 64 KiB. */
+typedef struct {
+  int32_t dtype, pass, relu, C;
+  int64_t npix;
+  double count;                /* APPLY_FIN: elements per channel, >= 1 */
+  ubr_pix ga, ga2, c, gc;
+  ubr_bn_site bn;
+} ubr_bn_bwd_desc;
+int ubr_bn_bwd(const ubr_bn_bwd_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * BasicBlock tail (models/common_layers.py:47-56):
  *   out = relu( relu(bn2(c2)) + shortcut ),  shortcut = bnpass(cb)  or  x
- * forward; backward pass 1 (all per-channel reductions of both BatchNorms) and pass 2
+ * forward; backward REDUCE (all per-channel reductions of both BatchNorms) and APPLY
  * (g_c2, and g_cb or the identity-skip gradient g_skip = g_out*[out>0]).
  * ---------------------------------------------------------------------------------------- */
-int ubr_block_tail_fwd(int dtype, int64_t npix, int C, const void* c2, int64_t c2_ps, const float* mean2,
-                       const float* scale2, const float* shift2, const void* sc, int64_t sc_ps, const float* mean_b,
-                       const float* scale_b, const float* shift_b /*NULL => identity shortcut*/,
-                       void* out, int64_t out_ps, void* stream);
-int ubr_block_tail_bwd_reduce(int dtype, int64_t npix, int C, const void* go, int64_t go_ps, const void* go2, int64_t go2_ps,
-                              const void* out, int64_t out_ps, const void* c2, int64_t c2_ps,
-                              const float* scale2, const float* shift2, const float* mean2, const float* invstd2,
-                              const void* cb, int64_t cb_ps, const float* mean_b, const float* invstd_b,
-                              double* red2, double* red_b, void* stream);
-int ubr_block_tail_bwd_apply(int dtype, int64_t npix, int C, const void* go, int64_t go_ps, const void* go2, int64_t go2_ps,
-                             const void* out, int64_t out_ps, const void* c2, int64_t c2_ps,
-                             const float* scale2, const float* shift2, const float* mean2, const float* invstd2,
-                             const float* k1_2, const float* k2_2,
-                             const void* cb, int64_t cb_ps, const float* scale_b, const float* mean_b, const float* invstd_b,
-                             const float* k1_b, const float* k2_b,
-                             void* g_c2, int64_t g_c2_ps, void* g_sc, int64_t g_sc_ps, void* stream);
-
-/* Forward with the train-mode BatchNorm finalize(s) fused: the convs that produced c2 (and cb) accumulated their statistics with
- * UBR_RED_SLOTS stripes (ubr_conv_desc.stats_slots); every workgroup forms mean / scale from them, workgroup 0 writes the
- * site's vectors (for the backward pass), the running statistics and the batch counter -- ubr_bn_finalize's arithmetic, without
- * its launches on the dependent chain.  momentum < 0 = cumulative averaging (nn.BatchNorm2d(momentum=None)).  bn_b NULL =
- * identity shortcut.  relu_mask may be NULL.  Needs 12*C (24*C) bytes of LDS. */
+/* train-mode BatchNorm finalize of one site, fused into the forward below */
 typedef struct {
   const double* stats;             /* [UBR_STAT_SLOTS][2*C] of which the first UBR_RED_SLOTS stripes are used */
   const float *gamma, *beta;
@@ -321,63 +321,54 @@ typedef struct {
   float momentum, eps;
   float *scale, *shift, *mean, *invstd;                                 /* outputs, C floats each */
 } ubr_bn_fwd_fin;
-int ubr_block_tail_fwd_fin(int dtype, int64_t npix, int C, const void* c2, int64_t c2_ps, const ubr_bn_fwd_fin* bn2,
-                           const void* sc, int64_t sc_ps, const ubr_bn_fwd_fin* bn_b, double count,
-                           void* out, int64_t out_ps, uint8_t* relu_mask, void* stream);
 
-/* The same three with the final ReLU's mask kept as bits: `relu_mask` holds one byte per pixel and 16-byte channel unit
- * ([npix][C / channels-per-unit], bit e = "stored output of channel e of the unit is > 0").  The forward writes it beside
- * `out`; the two backward passes read it instead of `out` -- 1 byte per unit instead of 16, i.e. two of the eight tensor passes
- * of a block tail's backward (autograd keeps the whole output for threshold_backward; reference models/common_layers.py:56). */
-int ubr_block_tail_fwd_masked(int dtype, int64_t npix, int C, const void* c2, int64_t c2_ps, const float* mean2,
-                              const float* scale2, const float* shift2, const void* sc, int64_t sc_ps, const float* mean_b,
-                              const float* scale_b, const float* shift_b, void* out, int64_t out_ps, uint8_t* relu_mask, void* stream);
-int ubr_block_tail_bwd_reduce_masked(int dtype, int64_t npix, int C, const void* go, int64_t go_ps, const void* go2, int64_t go2_ps,
-                                     const uint8_t* relu_mask, const void* c2, int64_t c2_ps,
-                                     const float* scale2, const float* shift2, const float* mean2, const float* invstd2,
-                                     const void* cb, int64_t cb_ps, const float* mean_b, const float* invstd_b,
-                                     double* red2, double* red_b, void* stream);
-int ubr_block_tail_bwd_apply_masked(int dtype, int64_t npix, int C, const void* go, int64_t go_ps, const void* go2, int64_t go2_ps,
-                                    const uint8_t* relu_mask, const void* c2, int64_t c2_ps,
-                                    const float* scale2, const float* shift2, const float* mean2, const float* invstd2,
-                                    const float* k1_2, const float* k2_2,
-                                    const void* cb, int64_t cb_ps, const float* scale_b, const float* mean_b, const float* invstd_b,
-                                    const float* k1_b, const float* k2_b,
-                                    void* g_c2, int64_t g_c2_ps, void* g_sc, int64_t g_sc_ps, void* stream);
+/* Forward, in exactly one of two forms.
+ * Plain (fin2 == NULL, fin_b == NULL): the six vectors of ubr_bn_finalize / ubr_bn_eval_affine; mean_b, scale_b, shift_b all NULL
+ *   = identity shortcut.
+ * Fused finalize (fin2 != NULL, the six vectors NULL): the convs that produced c2 (and cb) accumulated their statistics with
+ *   UBR_RED_SLOTS stripes (ubr_conv_desc.stats_slots); every workgroup forms mean / scale from them, workgroup 0 writes the
+ *   site's vectors (for the backward pass), the running statistics and the batch counter -- ubr_bn_finalize's arithmetic, without
+ *   its launches on the dependent chain.  momentum < 0 = cumulative averaging (nn.BatchNorm2d(momentum=None)).  fin_b NULL =
+ *   identity shortcut.  Needs 12*C (24*C with fin_b) bytes of LDS; 24*C <= 64 KiB is required of both.
+ * relu_mask (optional) keeps the final ReLU's mask as bits: one byte per pixel and 16-byte channel unit
+ * ([npix][C / channels-per-unit], bit e = "stored output of channel e of the unit is > 0"), written beside `out`; the backward
+ * passes read it instead of `out` -- 1 byte per unit instead of 16, i.e. two of the eight tensor passes of a block tail's
+ * backward (autograd keeps the whole output for threshold_backward; reference models/common_layers.py:56). */
+typedef struct {
+  int32_t dtype, C;
+  int64_t npix;
+  double count;                /* fused-finalize form: elements per channel, >= 1 */
+  ubr_pix c2, sc, out;         /* sc: cb on a bypass block, the block input x on an identity block */
+  uint8_t* relu_mask;
+  const float *mean2, *scale2, *shift2, *mean_b, *scale_b, *shift_b;
+  const ubr_bn_fwd_fin *fin2, *fin_b;
+} ubr_block_tail_fwd_desc;
+int ubr_block_tail_fwd(const ubr_block_tail_fwd_desc* d, void* stream);
 
-/* masked apply pass with both finalizes fused (see ubr_bn_bwd_apply_fin); red2 / red_b are the reduce pass's buffers.
- * On an identity block (cb == NULL) g_sc may be NULL: the skip gradient g_out*[out>0] is then not written, and the
- * consumer re-forms it from g_out and the mask (ubr_conv_desc.addend_mask). */
-int ubr_block_tail_bwd_apply_fin(int dtype, int64_t npix, int C, const void* go, int64_t go_ps, const void* go2, int64_t go2_ps,
-                                 const uint8_t* relu_mask, const void* c2, int64_t c2_ps,
-                                 const float* scale2, const float* shift2, const float* mean2, const float* invstd2,
-                                 const double* red2, float* dgamma2, float* dbeta2,
-                                 const void* cb, int64_t cb_ps, const float* scale_b, const float* mean_b, const float* invstd_b,
-                                 const double* red_b, float* dgamma_b, float* dbeta_b, double count,
-                                 void* g_c2, int64_t g_c2_ps, void* g_sc, int64_t g_sc_ps, void* stream);
+/* Backward.  bn2 is the site of c2; bnb that of cb (read only when cb is present: bypass block).
+ *   go, go2      the block output's gradient (go2: optional second tensor)
+ *   out          the block output, the final ReLU's gate when relu_mask is NULL
+ *   relu_mask    the forward's bit mask, read instead of `out`; required for APPLY_FIN and FROZEN; at most 2 GiB
+ *   g_c2, g_sc   data gradients (every pass but REDUCE).  On an identity block (cb absent) g_sc may be absent for APPLY_FIN and
+ *                FROZEN: the skip gradient g_out*[out>0] is then not written, and the consumer re-forms it from g_out and the
+ *                mask (ubr_conv_desc.addend_mask)
+ *   bnb          REDUCE reads mean, invstd; the other passes scale too
+ *   APPLY_FIN    bn2.red / bnb.red are the REDUCE pass's buffers; needs 16*C bytes of LDS (C <= 4096)
+ *   FROZEN       bn2.red / bnb.red are written, not read; needs at most 64 KiB of LDS (as REDUCE: 32*C, or 64*C where the unit
+ *                count allows the register flush).  A block tail whose two sites are in different modes runs REDUCE + APPLY with
+ *                k1 / k2 of the frozen site zero-filled by ubr_bn_bwd_finalize_frozen */
+typedef struct {
+  int32_t dtype, pass, C, pad_;
+  int64_t npix;
+  double count;                /* APPLY_FIN: elements per channel, >= 1 */
+  ubr_pix go, go2, out, c2, cb, g_c2, g_sc;
+  const uint8_t* relu_mask;
+  ubr_bn_site bn2, bnb;
+} ubr_block_tail_bwd_desc;
+int ubr_block_tail_bwd(const ubr_block_tail_bwd_desc* d, void* stream);
 
-/* ------------------------------------------------------------------------------------------
- * Frozen BatchNorm (module in eval mode, running statistics): mean / invstd are constants, so
- *   g_c = scale * g_y,  dgamma = sum g_y*xhat,  dbeta = sum g_y
- * and the data gradient waits for no reduction: reduce and apply are ONE pass.  The kernels below read every operand once,
- * write the data gradient(s) and add the sums into the same striped fp64 buffers as the reduce passes above (UBR_RED_SLOTS
- * stripes of a zeroed [UBR_STAT_SLOTS][2*C] buffer).  Per element the arithmetic is that of the apply passes with
- * k1 = k2 = 0.
- *   ubr_bn_bwd_frozen        : red may be NULL (the conv that produced `ga` already reduced, ubr_conv_desc.bnb_c): pure apply
- *   ubr_block_tail_bwd_frozen: operands of ubr_block_tail_bwd_apply_fin without `count`; red2 / red_b are written, not read;
- *                              g_sc may be NULL on an identity block
- *   ubr_bn_bwd_finalize_frozen: dgamma / dbeta (either may be NULL) from the stripes, off the dependent chain; k1 / k2
- *                              (both or neither) are zero-filled for the two-pass apply kernels, which then compute the
- *                              frozen gradient too (block tails whose two sites are in different modes)
- * ---------------------------------------------------------------------------------------- */
-int ubr_bn_bwd_frozen(int dtype, int64_t npix, int C, const void* ga, int64_t ga_ps, const void* ga2, int64_t ga2_ps,
-                      const void* c, int64_t c_ps, const float* scale, const float* shift, const float* mean,
-                      const float* invstd, int relu, double* red, void* gc, int64_t gc_ps, void* stream);
-int ubr_block_tail_bwd_frozen(int dtype, int64_t npix, int C, const void* go, int64_t go_ps, const void* go2, int64_t go2_ps,
-                              const uint8_t* relu_mask, const void* c2, int64_t c2_ps,
-                              const float* scale2, const float* shift2, const float* mean2, const float* invstd2, double* red2,
-                              const void* cb, int64_t cb_ps, const float* scale_b, const float* mean_b, const float* invstd_b,
-                              double* red_b, void* g_c2, int64_t g_c2_ps, void* g_sc, int64_t g_sc_ps, void* stream);
+/* dgamma / dbeta (either may be NULL) of a frozen site from the stripes, off the dependent chain; k1 / k2 (both or neither)
+ * are zero-filled for the two-pass APPLY kernels, which then compute the frozen gradient too */
 int ubr_bn_bwd_finalize_frozen(const double* red, int C, float* dgamma, float* dbeta, float* k1, float* k2, void* stream);
 
 /* ------------------------------------------------------------------------------------------

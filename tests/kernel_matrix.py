@@ -239,23 +239,23 @@ def _stream_rows():
     for T in DTYPES:
         for byp in (False, True):
             for msk in (False, True):
-                add(T, "tail_fwd_kernel<%s, %s, %s>" % (T, _b(byp), _b(msk)), "ubr_block_tail_fwd_masked" if msk else "ubr_block_tail_fwd",
+                add(T, "tail_fwd_kernel<%s, %s, %s>" % (T, _b(byp), _b(msk)), "ubr_block_tail_fwd",
                     "tail_fwd", shape=SHP, byp=byp, mask=msk)
             for g2 in (False, True):
                 for msk in (False, True):
                     for apply in (False, True):
                         add(T, "tail_bwd_kernel<%s, %s, %s, %s, %s>" % (T, _b(apply), _b(byp), _b(g2), _b(msk)),
-                            "ubr_block_tail_bwd_%s%s" % ("apply" if apply else "reduce", "_masked" if msk else ""),
+                            "ubr_block_tail_bwd",
                             "_tail_bwd", kind="apply" if apply else "reduce", shape=SHP, byp=byp, go2_ps=C2 if g2 else None, go2_off=48 if g2 else 0, mask=msk)
-                add(T, "tail_bwd_frozen_kernel<%s, %s, %s>" % (T, _b(byp), _b(g2)), "ubr_block_tail_bwd_frozen", "_tail_frozen",
+                add(T, "tail_bwd_frozen_kernel<%s, %s, %s>" % (T, _b(byp), _b(g2)), "ubr_block_tail_bwd", "_tail_frozen",
                     shape=SHP, byp=byp, go2_ps=C2 if g2 else None, go2_off=48 if g2 else 0)
         for g2 in (False, True):
             for relu in (False, True):
                 for apply in (False, True):
-                    add(T, "bn_bwd_kernel<%s, %s, %s, %s>" % (T, _b(apply), _b(g2), _b(relu)), "ubr_bn_bwd_apply" if apply else "ubr_bn_bwd_reduce",
+                    add(T, "bn_bwd_kernel<%s, %s, %s, %s>" % (T, _b(apply), _b(g2), _b(relu)), "ubr_bn_bwd",
                         "_bn_bwd", kind="apply" if apply else "reduce", shape=SHP, relu=relu, ga2=g2)
                 for red in (False, True):
-                    add(T, "bn_bwd_frozen_kernel<%s, %s, %s, %s>" % (T, _b(g2), _b(relu), _b(red)), "ubr_bn_bwd_frozen", "_bn_frozen",
+                    add(T, "bn_bwd_frozen_kernel<%s, %s, %s, %s>" % (T, _b(g2), _b(relu), _b(red)), "ubr_bn_bwd", "_bn_frozen",
                         shape=SHP, relu=relu, ga2=g2, red=red)
         add(T, "channel_sum_kernel<%s>" % T, "ubr_channel_sum", "channel_sum", shape=SHP)
         for S in (1, 2):

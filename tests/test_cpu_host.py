@@ -23,7 +23,7 @@ def test_library_exports_every_declared_symbol():
     lib = _lib.lib()
     for s in sorted(declared):
         assert hasattr(lib, s), "libubresnet_hip.so does not export %s" % s
-    assert lib.ubr_version() >= 1
+    assert lib.ubr_version() == 2
 
 
 def test_struct_layouts_match_header():

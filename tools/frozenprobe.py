@@ -2,9 +2,8 @@
 """Frozen-BatchNorm backward: the one-pass kernels against the two launches they replace, and the whole frozen step against
 the train-mode step.  usage: python tools/frozenprobe.py [batch] [out.txt]
 
-Part 1, per block-tail shape of the ip16 network on 512x512 images (bf16): ubr_block_tail_bwd_frozen against
-ubr_block_tail_bwd_reduce_masked + ubr_block_tail_bwd_apply_fin, and ubr_bn_bwd_frozen against ubr_bn_bwd_reduce +
-ubr_bn_bwd_apply_fin; old and new alternate, REPS rounds of ITERS launches each, median and spread (max - min over rounds) per
+Part 1, per block-tail shape of the ip16 network on 512x512 images (bf16): ubr_block_tail_bwd's UBR_PASS_FROZEN against
+its UBR_PASS_REDUCE + UBR_PASS_APPLY_FIN (masked), and the same passes of ubr_bn_bwd; old and new alternate, REPS rounds of ITERS launches each, median and spread (max - min over rounds) per
 launch, achieved bytes/s of the one-pass kernel from its algorithmic bytes.
 Part 2: train step (forward, loss, backward, FlatAdam) in train mode and with every BatchNorm frozen, alternated.
 Event timing, profiler off."""

@@ -96,6 +96,61 @@ class BnFwdFin(C.Structure):
     ]
 
 
+class Pix(C.Structure):
+    """ubr_pix"""
+    _fields_ = [("p", C.c_void_p), ("ps", C.c_int64)]
+
+
+PASS_REDUCE, PASS_APPLY, PASS_APPLY_FIN, PASS_FROZEN = 0, 1, 2, 3      # UBR_PASS_*
+
+
+class BnSite(C.Structure):
+    """ubr_bn_site"""
+    _fields_ = [
+        ("scale", C.c_void_p), ("shift", C.c_void_p), ("mean", C.c_void_p), ("invstd", C.c_void_p),
+        ("k1", C.c_void_p), ("k2", C.c_void_p),
+        ("red", C.c_void_p),
+        ("dgamma", C.c_void_p), ("dbeta", C.c_void_p),
+    ]
+
+
+class BnBwdDesc(C.Structure):
+    """ubr_bn_bwd_desc"""
+    _fields_ = [
+        ("dtype", C.c_int32), ("pass_", C.c_int32), ("relu", C.c_int32), ("C", C.c_int32),
+        ("npix", C.c_int64),
+        ("count", C.c_double),
+        ("ga", Pix), ("ga2", Pix), ("c", Pix), ("gc", Pix),
+        ("bn", BnSite),
+    ]
+
+
+class BlockTailBwdDesc(C.Structure):
+    """ubr_block_tail_bwd_desc"""
+    _fields_ = [
+        ("dtype", C.c_int32), ("pass_", C.c_int32), ("C", C.c_int32), ("pad_", C.c_int32),
+        ("npix", C.c_int64),
+        ("count", C.c_double),
+        ("go", Pix), ("go2", Pix), ("out", Pix), ("c2", Pix), ("cb", Pix), ("g_c2", Pix), ("g_sc", Pix),
+        ("relu_mask", C.c_void_p),
+        ("bn2", BnSite), ("bnb", BnSite),
+    ]
+
+
+class BlockTailFwdDesc(C.Structure):
+    """ubr_block_tail_fwd_desc"""
+    _fields_ = [
+        ("dtype", C.c_int32), ("C", C.c_int32),
+        ("npix", C.c_int64),
+        ("count", C.c_double),
+        ("c2", Pix), ("sc", Pix), ("out", Pix),
+        ("relu_mask", C.c_void_p),
+        ("mean2", C.c_void_p), ("scale2", C.c_void_p), ("shift2", C.c_void_p),
+        ("mean_b", C.c_void_p), ("scale_b", C.c_void_p), ("shift_b", C.c_void_p),
+        ("fin2", C.POINTER(BnFwdFin)), ("fin_b", C.POINTER(BnFwdFin)),
+    ]
+
+
 REDUCE_BATCH = 16         # UBR_REDUCE_BATCH
 
 
@@ -130,11 +185,8 @@ class WgradDesc(C.Structure):
 SYMBOLS = [
     "ubr_conv", "ubr_conv_last_config", "ubr_conv_last_kernel", "ubr_pack_weights", "ubr_pack_weights_batched", "ubr_bn_fold_batched", "ubr_aspp_front", "ubr_wgrad_plan", "ubr_wgrad", "ubr_wgrad_last_config", "ubr_wgrad_last_pc", "ubr_wgrad_reduce", "ubr_wgrad_reduce_batched",
     "ubr_stem_forward", "ubr_stem_wgrad", "ubr_stem_wgrad_workspace", "ubr_stem_expand",
-    "ubr_bn_finalize", "ubr_bn_eval_affine", "ubr_bn_bwd_reduce", "ubr_bn_bwd_finalize", "ubr_bn_bwd_apply",
-    "ubr_block_tail_fwd", "ubr_block_tail_bwd_reduce", "ubr_block_tail_bwd_apply",
-    "ubr_block_tail_fwd_masked", "ubr_block_tail_bwd_reduce_masked", "ubr_block_tail_bwd_apply_masked",
-    "ubr_bn_bwd_apply_fin", "ubr_block_tail_bwd_apply_fin", "ubr_block_tail_fwd_fin",
-    "ubr_bn_bwd_frozen", "ubr_block_tail_bwd_frozen", "ubr_bn_bwd_finalize_frozen",
+    "ubr_bn_finalize", "ubr_bn_eval_affine", "ubr_bn_bwd_finalize", "ubr_bn_bwd_finalize_frozen",
+    "ubr_bn_bwd", "ubr_block_tail_fwd", "ubr_block_tail_bwd",
     "ubr_maxpool_fwd", "ubr_maxpool_bwd",
     "ubr_logsoftmax_bwd", "ubr_pixelwise_nll_fwd", "ubr_pixelwise_nll_bwd", "ubr_confusion",
     "ubr_channel_sum", "ubr_cast_f64_to_f32", "ubr_zero", "ubr_adam_step", "ubr_sgd_step", "ubr_crop_tiles", "ubr_stitch_tiles", "ubr_last_error", "ubr_version",
@@ -174,26 +226,11 @@ def _declare(lib):
     lib.ubr_stem_expand.argtypes = [i32, vp, i32, i32, i32, i32, vp, i64, vp]
     lib.ubr_bn_finalize.argtypes = [vp, f64, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp, vp]
     lib.ubr_bn_eval_affine.argtypes = [vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp]
-    lib.ubr_bn_bwd_reduce.argtypes = [i32, i64, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp, vp]
-    lib.ubr_bn_bwd_finalize.argtypes = [vp, f64, vp, vp, i32, vp, vp, i32, vp, vp, vp]
-    lib.ubr_bn_bwd_apply.argtypes = [i32, i64, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp, i64, vp]
-    lib.ubr_bn_bwd_apply_fin.argtypes = [i32, i64, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp, f64, vp, vp, vp, i64, vp]
-    lib.ubr_block_tail_bwd_apply_fin.argtypes = [i32, i64, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp,
-                                                 vp, i64, vp, vp, vp, vp, vp, vp, f64, vp, i64, vp, i64, vp]
-    lib.ubr_bn_bwd_frozen.argtypes = [i32, i64, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp, vp, i64, vp]
-    lib.ubr_block_tail_bwd_frozen.argtypes = [i32, i64, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp,
-                                              vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp]
+    lib.ubr_bn_bwd_finalize.argtypes = [vp, f64, i32, vp, vp, i32, vp, vp, vp]
     lib.ubr_bn_bwd_finalize_frozen.argtypes = [vp, i32, vp, vp, vp, vp, vp]
-    lib.ubr_block_tail_fwd_fin.argtypes = [i32, i64, i32, vp, i64, C.POINTER(BnFwdFin), vp, i64, C.POINTER(BnFwdFin), f64, vp, i64, vp, vp]
-    lib.ubr_block_tail_fwd.argtypes = [i32, i64, i32, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
-    lib.ubr_block_tail_fwd_masked.argtypes = [i32, i64, i32, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp]
-    lib.ubr_block_tail_bwd_reduce_masked.argtypes = [i32, i64, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
-    lib.ubr_block_tail_bwd_apply_masked.argtypes = [i32, i64, i32, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp,
-                                                    vp, i64, vp, i64, vp]
-    lib.ubr_block_tail_bwd_reduce.argtypes = [i32, i64, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp,
-                                              vp, i64, vp, vp, vp, vp, vp]
-    lib.ubr_block_tail_bwd_apply.argtypes = [i32, i64, i32, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp,
-                                             vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp]
+    lib.ubr_bn_bwd.argtypes = [C.POINTER(BnBwdDesc), vp]
+    lib.ubr_block_tail_fwd.argtypes = [C.POINTER(BlockTailFwdDesc), vp]
+    lib.ubr_block_tail_bwd.argtypes = [C.POINTER(BlockTailBwdDesc), vp]
     lib.ubr_maxpool_fwd.argtypes = [i32, i32, i32, i32, i32, i32, vp, i64, ChanAffine, vp, i64, vp, i64, vp, vp]
     lib.ubr_maxpool_bwd.argtypes = [i32, i32, i32, i32, i32, i32, vp, i64, ChanAffine, vp, i64, vp, i64, vp, i64, vp, vp]
     lib.ubr_logsoftmax_bwd.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, i64, vp]

@@ -198,7 +198,7 @@ template <typename T> __device__ __forceinline__ void unpack4(const ubr_u4& v, f
 // ------------------------------------------------------------------------------------------
 // BasicBlock tail forward
 // ------------------------------------------------------------------------------------------
-// train-mode BatchNorm finalize of one site, fused into its consumer (ubr_block_tail_fwd_fin): the producing conv's striped
+// train-mode BatchNorm finalize of one site, fused into its consumer (ubr_block_tail_fwd with fin2): the producing conv's striped
 // fp64 sums in, the site's vectors out (written by workgroup 0; every workgroup computes its own copy into LDS)
 struct BnFwdFin {
   const double* stats; const float *gamma, *beta;
@@ -1129,20 +1129,48 @@ static int check_nhwc(const char* who, int dtype, int64_t npix, int C, const voi
     if (b2) { constexpr bool B2 = true; UBR_BOOL2(b0, b1, CALL); } else { constexpr bool B2 = false; UBR_BOOL2(b0, b1, CALL); } \
   } while (0)
 
-static int tail_fwd_common(int dtype, int64_t npix, int C, const void* c2, int64_t c2_ps, const float* mean2, const float* scale2,
-                           const float* shift2, const void* sc, int64_t sc_ps, const float* mean_b, const float* scale_b,
-                           const float* shift_b, void* out, int64_t out_ps, uint8_t* relu_mask, void* stream,
-                           const ubr_bn_fwd_fin* fin2 = nullptr, const ubr_bn_fwd_fin* finb = nullptr, double count = 0.0) {
-  UBR_TRY(check_nhwc("ubr_block_tail_fwd(c2)", dtype, npix, C, c2, c2_ps));
-  UBR_TRY(check_nhwc("ubr_block_tail_fwd(sc)", dtype, npix, C, sc, sc_ps));
-  UBR_TRY(check_nhwc("ubr_block_tail_fwd(out)", dtype, npix, C, out, out_ps));
+// Grid limits of the reduce / apply passes, the stripes in use and the flush form: the defaults, or what ubr_tune_set chose
+struct PassTune { int red_iters = 8, red_blocks = 512, app_blocks = 2048; };
+static PassTune pass_tune(int* nslots, int* flush) {
+  PassTune t;
+  *nslots = UBR_RED_SLOTS;
+#ifdef UBR_TUNE
+  if (g_tune_red_iters) t.red_iters = g_tune_red_iters;
+  if (g_tune_red_blocks) t.red_blocks = g_tune_red_blocks;
+  if (g_tune_app_blocks) t.app_blocks = g_tune_app_blocks;
+  if (g_tune_slots) *nslots = g_tune_slots;
+  if (!g_tune_flush) *flush = 0;
+#endif
+  return t;
+}
+
+// "entry(pass)" for the error texts of a backward entry point; rejects a pass out of range
+static int pass_who(const char* entry, int pass, char (&who)[48]) {
+  static const char* const names[] = {"reduce", "apply", "apply_fin", "frozen"};
+  UBR_CHECK(pass >= UBR_PASS_REDUCE && pass <= UBR_PASS_FROZEN, "%s: bad pass %d", entry, pass);
+  snprintf(who, sizeof who, "%s(%s)", entry, names[pass]);
+  return UBR_OK;
+}
+
+static bool site_consts(const ubr_bn_site& s) { return s.scale && s.shift && s.mean && s.invstd; }
+
+extern "C" int ubr_block_tail_fwd(const ubr_block_tail_fwd_desc* d, void* stream) {
+  const char* who = "ubr_block_tail_fwd";
+  UBR_CHECK(d != nullptr, "%s: null descriptor", who);
+  const int C = d->C;
+  UBR_TRY(check_nhwc("ubr_block_tail_fwd(c2)", d->dtype, d->npix, C, d->c2.p, d->c2.ps));
+  UBR_TRY(check_nhwc("ubr_block_tail_fwd(sc)", d->dtype, d->npix, C, d->sc.p, d->sc.ps));
+  UBR_TRY(check_nhwc("ubr_block_tail_fwd(out)", d->dtype, d->npix, C, d->out.p, d->out.ps));
   TailF k{};
-  k.npix = npix; k.CU = C / ubr_cpu(dtype); k.C = C;
-  k.c2 = c2; k.sc = sc; k.out = out; k.c2_ps = c2_ps; k.sc_ps = sc_ps; k.out_ps = out_ps;
-  k.relu_mask = relu_mask;
+  k.npix = d->npix; k.CU = C / ubr_cpu(d->dtype); k.C = C;
+  k.c2 = d->c2.p; k.sc = d->sc.p; k.out = d->out.p; k.c2_ps = d->c2.ps; k.sc_ps = d->sc.ps; k.out_ps = d->out.ps;
+  k.relu_mask = d->relu_mask;
+  const bool plain = d->mean2 || d->scale2 || d->shift2 || d->mean_b || d->scale_b || d->shift_b;
+  const bool fused = d->fin2 != nullptr;
+  UBR_CHECK(fused ? !plain : d->fin_b == nullptr, "%s: give the six vectors or fin2 (and fin_b), not both", who);
   bool byp;
   size_t lds = 0;
-  if (fin2 != nullptr) {
+  if (fused) {
     auto conv = [](const ubr_bn_fwd_fin* f, BnFwdFin* o) {
       o->stats = f->stats; o->gamma = f->gamma; o->beta = f->beta; o->rmean = f->running_mean; o->rvar = f->running_var;
       o->nbt = (long long*)f->num_batches_tracked; o->momentum = f->momentum; o->eps = f->eps;
@@ -1152,289 +1180,114 @@ static int tail_fwd_common(int dtype, int64_t npix, int C, const void* c2, int64
       return f->stats && f->gamma && f->beta && f->scale && f->shift && f->mean && f->invstd && ((f->running_mean == nullptr) == (f->running_var == nullptr)) &&
              (f->momentum >= 0.f || f->num_batches_tracked != nullptr);
     };
-    UBR_CHECK(ok(fin2) && (finb == nullptr || ok(finb)) && count >= 1.0 && (size_t)24 * C <= 65536, "ubr_block_tail_fwd_fin: bad arguments");
-    conv(fin2, &k.f2);
-    if (finb != nullptr) conv(finb, &k.fb);
-    k.count = count; k.nslots = UBR_RED_SLOTS;
-    byp = finb != nullptr;
+    UBR_CHECK(ok(d->fin2) && (d->fin_b == nullptr || ok(d->fin_b)) && d->count >= 1.0 && (size_t)24 * C <= 65536, "%s: bad fused-finalize arguments", who);
+    conv(d->fin2, &k.f2);
+    if (d->fin_b != nullptr) conv(d->fin_b, &k.fb);
+    k.count = d->count; k.nslots = UBR_RED_SLOTS;
+    byp = d->fin_b != nullptr;
     lds = (size_t)(byp ? 24 : 12) * C;
   } else {
-    UBR_CHECK(mean2 && scale2 && shift2 && ((scale_b == nullptr) == (shift_b == nullptr)) && ((scale_b == nullptr) == (mean_b == nullptr)), "ubr_block_tail_fwd: bad affine pointers");
-    k.m2 = mean2; k.s2 = scale2; k.t2 = shift2; k.mb = mean_b; k.sb = scale_b; k.tb = shift_b;
-    byp = scale_b != nullptr;
+    UBR_CHECK(d->mean2 && d->scale2 && d->shift2 && ((d->scale_b == nullptr) == (d->shift_b == nullptr)) && ((d->scale_b == nullptr) == (d->mean_b == nullptr)),
+              "%s: bad affine pointers", who);
+    k.m2 = d->mean2; k.s2 = d->scale2; k.t2 = d->shift2; k.mb = d->mean_b; k.sb = d->scale_b; k.tb = d->shift_b;
+    byp = d->scale_b != nullptr;
   }
-  const int blocks = pick_blocks(npix, k.CU, fin2 != nullptr ? 1024 : 2048, 4);
-  const bool msk = relu_mask != nullptr;
-  UBR_DT_SWITCH(dtype, UBR_BOOL2(byp, msk, ubr_launch((tail_fwd_kernel<TT, B0, B1>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, k)));
-  UBR_LAUNCH_CHECK("ubr_block_tail_fwd");
+  const int blocks = pick_blocks(d->npix, k.CU, fused ? 1024 : 2048, 4);
+  const bool msk = d->relu_mask != nullptr;
+  UBR_DT_SWITCH(d->dtype, UBR_BOOL2(byp, msk, ubr_launch((tail_fwd_kernel<TT, B0, B1>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, k)));
+  UBR_LAUNCH_CHECK(who);
   return UBR_OK;
 }
-extern "C" int ubr_block_tail_fwd(int dtype, int64_t npix, int C, const void* c2, int64_t c2_ps, const float* mean2, const float* scale2,
-                                  const float* shift2, const void* sc, int64_t sc_ps, const float* mean_b, const float* scale_b,
-                                  const float* shift_b, void* out, int64_t out_ps, void* stream) {
-  return tail_fwd_common(dtype, npix, C, c2, c2_ps, mean2, scale2, shift2, sc, sc_ps, mean_b, scale_b, shift_b, out, out_ps, nullptr, stream);
-}
-extern "C" int ubr_block_tail_fwd_masked(int dtype, int64_t npix, int C, const void* c2, int64_t c2_ps, const float* mean2, const float* scale2,
-                                         const float* shift2, const void* sc, int64_t sc_ps, const float* mean_b, const float* scale_b,
-                                         const float* shift_b, void* out, int64_t out_ps, uint8_t* relu_mask, void* stream) {
-  UBR_CHECK(relu_mask != nullptr, "ubr_block_tail_fwd_masked: null mask");
-  return tail_fwd_common(dtype, npix, C, c2, c2_ps, mean2, scale2, shift2, sc, sc_ps, mean_b, scale_b, shift_b, out, out_ps, relu_mask, stream);
-}
 
-struct TailFin { const double *red2, *redb; double count; float *dgamma2, *dbeta2, *dgamma_b, *dbeta_b; };
-
-extern "C" int ubr_block_tail_fwd_fin(int dtype, int64_t npix, int C, const void* c2, int64_t c2_ps, const ubr_bn_fwd_fin* bn2,
-                                      const void* sc, int64_t sc_ps, const ubr_bn_fwd_fin* bn_b, double count,
-                                      void* out, int64_t out_ps, uint8_t* relu_mask, void* stream) {
-  UBR_CHECK(bn2 != nullptr, "ubr_block_tail_fwd_fin: null bn2");
-  return tail_fwd_common(dtype, npix, C, c2, c2_ps, nullptr, nullptr, nullptr, sc, sc_ps, nullptr, nullptr, nullptr, out, out_ps, relu_mask, stream, bn2, bn_b, count);
-}
-
-static int tail_bwd_common(bool apply, int dtype, int64_t npix, int C, const void* go, int64_t go_ps, const void* go2, int64_t go2_ps,
-                           const void* out, int64_t out_ps, const void* c2, int64_t c2_ps,
-                           const float* scale2, const float* shift2, const float* mean2, const float* invstd2,
-                           const float* k1_2, const float* k2_2,
-                           const void* cb, int64_t cb_ps, const float* scale_b, const float* mean_b, const float* invstd_b,
-                           const float* k1_b, const float* k2_b, double* red2, double* red_b,
-                           void* g_c2, int64_t g_c2_ps, void* g_sc, int64_t g_sc_ps, void* stream, const uint8_t* relu_mask = nullptr,
-                           const TailFin* fin = nullptr) {
-  const char* who = apply ? "ubr_block_tail_bwd_apply" : "ubr_block_tail_bwd_reduce";
-  UBR_TRY(check_nhwc(who, dtype, npix, C, go, go_ps));
-  if (go2) UBR_TRY(check_nhwc(who, dtype, npix, C, go2, go2_ps));
-  if (relu_mask == nullptr) UBR_TRY(check_nhwc(who, dtype, npix, C, out, out_ps));
-  UBR_TRY(check_nhwc(who, dtype, npix, C, c2, c2_ps));
-  if (cb) UBR_TRY(check_nhwc(who, dtype, npix, C, cb, cb_ps));
-  UBR_CHECK(scale2 && shift2 && mean2 && invstd2, "%s: null bn2 constants", who);
-  if (cb) UBR_CHECK(mean_b && invstd_b, "%s: null bnpass constants", who);
-  if (relu_mask) UBR_CHECK(npix * (C / ubr_cpu(dtype)) < (int64_t)1 << 31, "%s: mask exceeds 2 GiB", who);
-  if (apply) {
-    UBR_TRY(check_nhwc(who, dtype, npix, C, g_c2, g_c2_ps));
-    if (g_sc != nullptr || cb != nullptr) UBR_TRY(check_nhwc(who, dtype, npix, C, g_sc, g_sc_ps));
-    if (fin == nullptr) UBR_CHECK(k1_2 && k2_2 && (!cb || (k1_b && k2_b)), "%s: null backward constants", who);
-    else UBR_CHECK(fin->red2 && (!cb || fin->redb) && fin->count >= 1.0 && (size_t)16 * C <= 65536, "%s: bad fused-finalize arguments", who);
-    UBR_CHECK(!cb || scale_b, "%s: null bnpass scale", who);
-  } else {
-    UBR_CHECK(red2 && (!cb || red_b), "%s: null reduction buffer", who);
+// FROZEN: the grid and the LDS carve-out of the reduce pass (every workgroup ends with a flush)
+extern "C" int ubr_block_tail_bwd(const ubr_block_tail_bwd_desc* d, void* stream) {
+  UBR_CHECK(d != nullptr, "ubr_block_tail_bwd: null descriptor");
+  char who[48];
+  UBR_TRY(pass_who("ubr_block_tail_bwd", d->pass, who));
+  const int pass = d->pass, dtype = d->dtype, C = d->C;
+  const int64_t npix = d->npix;
+  const ubr_bn_site &s2 = d->bn2, &sb = d->bnb;
+  const bool byp = d->cb.p != nullptr, g2 = d->go2.p != nullptr, msk = d->relu_mask != nullptr;
+  UBR_TRY(check_nhwc(who, dtype, npix, C, d->go.p, d->go.ps));
+  if (g2) UBR_TRY(check_nhwc(who, dtype, npix, C, d->go2.p, d->go2.ps));
+  if (!msk) UBR_TRY(check_nhwc(who, dtype, npix, C, d->out.p, d->out.ps));
+  UBR_TRY(check_nhwc(who, dtype, npix, C, d->c2.p, d->c2.ps));
+  if (byp) UBR_TRY(check_nhwc(who, dtype, npix, C, d->cb.p, d->cb.ps));
+  UBR_CHECK(site_consts(s2), "%s: null bn2 constants", who);
+  if (byp) UBR_CHECK(sb.mean && sb.invstd, "%s: null bnpass constants", who);
+  if (msk) UBR_CHECK(npix * (C / ubr_cpu(dtype)) < (int64_t)1 << 31, "%s: mask exceeds 2 GiB", who);
+  if (pass >= UBR_PASS_APPLY_FIN) UBR_CHECK(msk, "%s: null mask", who);
+  if (pass != UBR_PASS_REDUCE) {
+    UBR_TRY(check_nhwc(who, dtype, npix, C, d->g_c2.p, d->g_c2.ps));
+    if (d->g_sc.p != nullptr || byp) UBR_TRY(check_nhwc(who, dtype, npix, C, d->g_sc.p, d->g_sc.ps));
+    UBR_CHECK(!byp || sb.scale, "%s: null bnpass scale", who);
   }
+  if (pass == UBR_PASS_APPLY) UBR_CHECK(s2.k1 && s2.k2 && (!byp || (sb.k1 && sb.k2)), "%s: null backward constants (k1 and k2, both)", who);
+  else UBR_CHECK(s2.red && (!byp || sb.red), "%s: null reduction buffer", who);
+  if (pass == UBR_PASS_APPLY_FIN) UBR_CHECK(d->count >= 1.0, "%s: count %g < 1", who, d->count);
   TailB k{};
   k.npix = npix; k.C = C; k.CU = C / ubr_cpu(dtype);
-  k.go = go; k.go2 = go2; k.out = out; k.c2 = c2; k.cb = cb;
-  k.go_ps = go_ps; k.go2_ps = go2_ps; k.out_ps = out_ps; k.c2_ps = c2_ps; k.cb_ps = cb_ps;
-  k.s2 = scale2; k.t2 = shift2; k.m2 = mean2; k.i2 = invstd2; k.k1_2 = k1_2; k.k2_2 = k2_2;
-  k.sb = scale_b; k.mb = mean_b; k.ib = invstd_b; k.k1_b = k1_b; k.k2_b = k2_b;
-  k.red2 = red2; k.redb = red_b; k.g_c2 = g_c2; k.g_sc = g_sc; k.g_c2_ps = g_c2_ps; k.g_sc_ps = g_sc_ps;
-  k.relu_mask = relu_mask;
-  k.nslots = UBR_RED_SLOTS;
-  if (fin != nullptr) {
-    k.fin_red2 = fin->red2; k.fin_redb = fin->redb; k.count = fin->count;
-    k.dgamma2 = fin->dgamma2; k.dbeta2 = fin->dbeta2; k.dgamma_b = fin->dgamma_b; k.dbeta_b = fin->dbeta_b;
-  }
-  int red_iters = 8, red_blocks = 512, app_blocks = 2048;
+  k.go = d->go.p; k.go2 = d->go2.p; k.c2 = d->c2.p; k.cb = d->cb.p;
+  k.go_ps = d->go.ps; k.go2_ps = d->go2.ps; k.c2_ps = d->c2.ps; k.cb_ps = d->cb.ps;
+  if (!msk) { k.out = d->out.p; k.out_ps = d->out.ps; }
+  k.s2 = s2.scale; k.t2 = s2.shift; k.m2 = s2.mean; k.i2 = s2.invstd;
+  k.sb = sb.scale; k.mb = sb.mean; k.ib = sb.invstd;
+  k.g_c2 = d->g_c2.p; k.g_sc = d->g_sc.p; k.g_c2_ps = d->g_c2.ps; k.g_sc_ps = d->g_sc.ps;
+  k.relu_mask = d->relu_mask;
+  if (pass == UBR_PASS_APPLY) { k.k1_2 = s2.k1; k.k2_2 = s2.k2; k.k1_b = sb.k1; k.k2_b = sb.k2; }
+  else if (pass == UBR_PASS_APPLY_FIN) {
+    k.fin_red2 = s2.red; k.fin_redb = sb.red; k.count = d->count;
+    k.dgamma2 = s2.dgamma; k.dbeta2 = s2.dbeta; k.dgamma_b = sb.dgamma; k.dbeta_b = sb.dbeta;
+  } else { k.red2 = s2.red; k.redb = sb.red; }
   k.flush = red_flush_mode(k.CU, C, 4);
-#ifdef UBR_TUNE
-  if (g_tune_red_iters) red_iters = g_tune_red_iters;
-  if (g_tune_red_blocks) red_blocks = g_tune_red_blocks;
-  if (g_tune_app_blocks) app_blocks = g_tune_app_blocks;
-  if (g_tune_slots) k.nslots = g_tune_slots;
-  if (!g_tune_flush) k.flush = 0;
-#endif
-  const int blocks = pick_blocks(npix, k.CU, apply ? app_blocks : red_blocks, apply ? 2 : red_iters);
+  const PassTune t = pass_tune(&k.nslots, &k.flush);
+  const bool walk = pass == UBR_PASS_REDUCE || pass == UBR_PASS_FROZEN;     // ends with a flush of the sums
+  const int blocks = walk ? pick_blocks(npix, k.CU, t.red_blocks, t.red_iters) : pick_blocks(npix, k.CU, t.app_blocks, 2);
   // reduce: fp64 atomics need 4 C doubles, the per-wave rows 4 x 4 C floats; apply with the finalize fused: 4 C floats
-  const size_t lds = apply ? (fin != nullptr ? (size_t)16 * C : 0) : (size_t)(k.flush ? 16 : 8) * 4 * C;
-  const bool byp = cb != nullptr, g2 = go2 != nullptr, msk = relu_mask != nullptr;
-  if (apply) { UBR_DT_SWITCH(dtype, UBR_BOOL3(byp, g2, msk, ubr_launch((tail_bwd_kernel<TT, true, B0, B1, B2>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, k))); }
-  else { UBR_DT_SWITCH(dtype, UBR_BOOL3(byp, g2, msk, ubr_launch((tail_bwd_kernel<TT, false, B0, B1, B2>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, k))); }
+  const size_t lds = walk ? (size_t)(k.flush ? 16 : 8) * 4 * C : pass == UBR_PASS_APPLY_FIN ? (size_t)16 * C : 0;
+  if (pass >= UBR_PASS_APPLY_FIN) UBR_CHECK(lds <= 65536, "%s: C = %d needs more than 64 KiB of LDS", who, C);
+  const hipStream_t st = (hipStream_t)stream;
+  if (pass == UBR_PASS_FROZEN) { UBR_DT_SWITCH(dtype, UBR_BOOL2(byp, g2, ubr_launch((tail_bwd_frozen_kernel<TT, B0, B1>), dim3(blocks), dim3(256), lds, st, k))); }
+  else if (pass == UBR_PASS_REDUCE) { UBR_DT_SWITCH(dtype, UBR_BOOL3(byp, g2, msk, ubr_launch((tail_bwd_kernel<TT, false, B0, B1, B2>), dim3(blocks), dim3(256), lds, st, k))); }
+  else { UBR_DT_SWITCH(dtype, UBR_BOOL3(byp, g2, msk, ubr_launch((tail_bwd_kernel<TT, true, B0, B1, B2>), dim3(blocks), dim3(256), lds, st, k))); }
   UBR_LAUNCH_CHECK(who);
   return UBR_OK;
 }
 
-extern "C" int ubr_block_tail_bwd_reduce(int dtype, int64_t npix, int C, const void* go, int64_t go_ps, const void* go2, int64_t go2_ps,
-                                         const void* out, int64_t out_ps, const void* c2, int64_t c2_ps,
-                                         const float* scale2, const float* shift2, const float* mean2, const float* invstd2,
-                                         const void* cb, int64_t cb_ps, const float* mean_b, const float* invstd_b,
-                                         double* red2, double* red_b, void* stream) {
-  return tail_bwd_common(false, dtype, npix, C, go, go_ps, go2, go2_ps, out, out_ps, c2, c2_ps, scale2, shift2, mean2, invstd2,
-                         nullptr, nullptr, cb, cb_ps, nullptr, mean_b, invstd_b, nullptr, nullptr, red2, red_b,
-                         nullptr, 0, nullptr, 0, stream);
-}
-extern "C" int ubr_block_tail_bwd_apply(int dtype, int64_t npix, int C, const void* go, int64_t go_ps, const void* go2, int64_t go2_ps,
-                                        const void* out, int64_t out_ps, const void* c2, int64_t c2_ps,
-                                        const float* scale2, const float* shift2, const float* mean2, const float* invstd2,
-                                        const float* k1_2, const float* k2_2,
-                                        const void* cb, int64_t cb_ps, const float* scale_b, const float* mean_b, const float* invstd_b,
-                                        const float* k1_b, const float* k2_b,
-                                        void* g_c2, int64_t g_c2_ps, void* g_sc, int64_t g_sc_ps, void* stream) {
-  return tail_bwd_common(true, dtype, npix, C, go, go_ps, go2, go2_ps, out, out_ps, c2, c2_ps, scale2, shift2, mean2, invstd2,
-                         k1_2, k2_2, cb, cb_ps, scale_b, mean_b, invstd_b, k1_b, k2_b, nullptr, nullptr,
-                         g_c2, g_c2_ps, g_sc, g_sc_ps, stream);
-}
-// the same two passes reading the forward's ReLU bit mask (ubr_block_tail_fwd_masked) instead of the block output
-extern "C" int ubr_block_tail_bwd_reduce_masked(int dtype, int64_t npix, int C, const void* go, int64_t go_ps, const void* go2, int64_t go2_ps,
-                                                const uint8_t* relu_mask, const void* c2, int64_t c2_ps,
-                                                const float* scale2, const float* shift2, const float* mean2, const float* invstd2,
-                                                const void* cb, int64_t cb_ps, const float* mean_b, const float* invstd_b,
-                                                double* red2, double* red_b, void* stream) {
-  UBR_CHECK(relu_mask != nullptr, "ubr_block_tail_bwd_reduce_masked: null mask");
-  return tail_bwd_common(false, dtype, npix, C, go, go_ps, go2, go2_ps, nullptr, 0, c2, c2_ps, scale2, shift2, mean2, invstd2,
-                         nullptr, nullptr, cb, cb_ps, nullptr, mean_b, invstd_b, nullptr, nullptr, red2, red_b,
-                         nullptr, 0, nullptr, 0, stream, relu_mask);
-}
-extern "C" int ubr_block_tail_bwd_apply_masked(int dtype, int64_t npix, int C, const void* go, int64_t go_ps, const void* go2, int64_t go2_ps,
-                                               const uint8_t* relu_mask, const void* c2, int64_t c2_ps,
-                                               const float* scale2, const float* shift2, const float* mean2, const float* invstd2,
-                                               const float* k1_2, const float* k2_2,
-                                               const void* cb, int64_t cb_ps, const float* scale_b, const float* mean_b, const float* invstd_b,
-                                               const float* k1_b, const float* k2_b,
-                                               void* g_c2, int64_t g_c2_ps, void* g_sc, int64_t g_sc_ps, void* stream) {
-  UBR_CHECK(relu_mask != nullptr, "ubr_block_tail_bwd_apply_masked: null mask");
-  return tail_bwd_common(true, dtype, npix, C, go, go_ps, go2, go2_ps, nullptr, 0, c2, c2_ps, scale2, shift2, mean2, invstd2,
-                         k1_2, k2_2, cb, cb_ps, scale_b, mean_b, invstd_b, k1_b, k2_b, nullptr, nullptr,
-                         g_c2, g_c2_ps, g_sc, g_sc_ps, stream, relu_mask);
-}
-
-struct BnFin { const double* red; double count; float *dgamma, *dbeta; };
-
-static int bn_bwd_common(bool apply, int dtype, int64_t npix, int C, const void* ga, int64_t ga_ps, const void* ga2, int64_t ga2_ps,
-                         const void* c, int64_t c_ps, const float* scale, const float* shift, const float* mean,
-                         const float* invstd, int relu, const float* k1, const float* k2, double* red,
-                         void* gc, int64_t gc_ps, void* stream, const BnFin* fin = nullptr) {
-  const char* who = apply ? "ubr_bn_bwd_apply" : "ubr_bn_bwd_reduce";
-  UBR_TRY(check_nhwc(who, dtype, npix, C, ga, ga_ps));
-  if (ga2) UBR_TRY(check_nhwc(who, dtype, npix, C, ga2, ga2_ps));
-  UBR_TRY(check_nhwc(who, dtype, npix, C, c, c_ps));
-  UBR_CHECK(scale && shift && mean && invstd, "%s: null bn constants", who);
-  if (apply) {
-    UBR_TRY(check_nhwc(who, dtype, npix, C, gc, gc_ps));
-    if (fin == nullptr) UBR_CHECK(k1 && k2, "%s: null k1/k2", who);
-    else UBR_CHECK(fin->red && fin->count >= 1.0 && (size_t)8 * C <= 65536, "%s: bad fused-finalize arguments", who);
-  } else UBR_CHECK(red != nullptr, "%s: null reduction buffer", who);
+// FROZEN with bn.red: the grid and the LDS carve-out of the reduce pass; without: those of the apply pass
+extern "C" int ubr_bn_bwd(const ubr_bn_bwd_desc* d, void* stream) {
+  UBR_CHECK(d != nullptr, "ubr_bn_bwd: null descriptor");
+  char who[48];
+  UBR_TRY(pass_who("ubr_bn_bwd", d->pass, who));
+  const int pass = d->pass, dtype = d->dtype, C = d->C;
+  const int64_t npix = d->npix;
+  const ubr_bn_site& s = d->bn;
+  UBR_TRY(check_nhwc(who, dtype, npix, C, d->ga.p, d->ga.ps));
+  if (d->ga2.p) UBR_TRY(check_nhwc(who, dtype, npix, C, d->ga2.p, d->ga2.ps));
+  UBR_TRY(check_nhwc(who, dtype, npix, C, d->c.p, d->c.ps));
+  UBR_CHECK(site_consts(s), "%s: null bn constants", who);
+  if (pass != UBR_PASS_REDUCE) UBR_TRY(check_nhwc(who, dtype, npix, C, d->gc.p, d->gc.ps));
+  if (pass == UBR_PASS_APPLY) UBR_CHECK(s.k1 && s.k2, "%s: null k1/k2 (both are needed)", who);
+  if (pass == UBR_PASS_REDUCE || pass == UBR_PASS_APPLY_FIN) UBR_CHECK(s.red != nullptr, "%s: null reduction buffer", who);
+  if (pass == UBR_PASS_APPLY_FIN) UBR_CHECK(d->count >= 1.0, "%s: count %g < 1", who, d->count);
   BnB k{};
   k.npix = npix; k.C = C; k.CU = C / ubr_cpu(dtype);
-  k.ga = ga; k.ga2 = ga2; k.c = c; k.ga_ps = ga_ps; k.ga2_ps = ga2_ps; k.c_ps = c_ps;
-  k.scale = scale; k.shift = shift; k.mean = mean; k.invstd = invstd; k.k1 = k1; k.k2 = k2; k.red = red; k.gc = gc; k.gc_ps = gc_ps;
-  k.nslots = UBR_RED_SLOTS;
-  if (fin != nullptr) { k.fin_red = fin->red; k.count = fin->count; k.dgamma = fin->dgamma; k.dbeta = fin->dbeta; }
-  int red_iters = 8, red_blocks = 512, app_blocks = 2048;
+  k.ga = d->ga.p; k.ga2 = d->ga2.p; k.c = d->c.p; k.ga_ps = d->ga.ps; k.ga2_ps = d->ga2.ps; k.c_ps = d->c.ps;
+  k.scale = s.scale; k.shift = s.shift; k.mean = s.mean; k.invstd = s.invstd; k.gc = d->gc.p; k.gc_ps = d->gc.ps;
+  if (pass == UBR_PASS_APPLY) { k.k1 = s.k1; k.k2 = s.k2; }
+  else if (pass == UBR_PASS_APPLY_FIN) { k.fin_red = s.red; k.count = d->count; k.dgamma = s.dgamma; k.dbeta = s.dbeta; }
+  else k.red = s.red;
   k.flush = red_flush_mode(k.CU, C, 2);
-#ifdef UBR_TUNE
-  if (g_tune_red_iters) red_iters = g_tune_red_iters;
-  if (g_tune_red_blocks) red_blocks = g_tune_red_blocks;
-  if (g_tune_app_blocks) app_blocks = g_tune_app_blocks;
-  if (g_tune_slots) k.nslots = g_tune_slots;
-  if (!g_tune_flush) k.flush = 0;
-#endif
-  const int blocks = pick_blocks(npix, k.CU, apply ? app_blocks : red_blocks, apply ? 4 : red_iters);
-  const size_t lds = apply ? (fin != nullptr ? (size_t)8 * C : 0) : (size_t)(k.flush ? 16 : 8) * 2 * C;
-  const bool g2 = ga2 != nullptr, rl = relu != 0;
-  if (apply) { UBR_DT_SWITCH(dtype, UBR_BOOL2(g2, rl, ubr_launch((bn_bwd_kernel<TT, true, B0, B1>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, k))); }
-  else { UBR_DT_SWITCH(dtype, UBR_BOOL2(g2, rl, ubr_launch((bn_bwd_kernel<TT, false, B0, B1>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, k))); }
-  UBR_LAUNCH_CHECK(who);
-  return UBR_OK;
-}
-extern "C" int ubr_bn_bwd_reduce(int dtype, int64_t npix, int C, const void* ga, int64_t ga_ps, const void* ga2, int64_t ga2_ps,
-                                 const void* c, int64_t c_ps, const float* scale, const float* shift, const float* mean,
-                                 const float* invstd, int relu, double* red, void* stream) {
-  return bn_bwd_common(false, dtype, npix, C, ga, ga_ps, ga2, ga2_ps, c, c_ps, scale, shift, mean, invstd, relu, nullptr, nullptr, red, nullptr, 0, stream);
-}
-extern "C" int ubr_bn_bwd_apply(int dtype, int64_t npix, int C, const void* ga, int64_t ga_ps, const void* ga2, int64_t ga2_ps,
-                                const void* c, int64_t c_ps, const float* scale, const float* shift, const float* mean,
-                                const float* invstd, int relu, const float* k1, const float* k2,
-                                void* gc, int64_t gc_ps, void* stream) {
-  return bn_bwd_common(true, dtype, npix, C, ga, ga_ps, ga2, ga2_ps, c, c_ps, scale, shift, mean, invstd, relu, k1, k2, nullptr, gc, gc_ps, stream);
-}
-
-// Apply passes with the finalize fused (no ubr_bn_bwd_finalize launch between reduce and apply): `red` is what the reduce pass
-// accumulated; every workgroup forms k1 / k2 from it, workgroup 0 writes dgamma / dbeta.
-extern "C" int ubr_bn_bwd_apply_fin(int dtype, int64_t npix, int C, const void* ga, int64_t ga_ps, const void* ga2, int64_t ga2_ps,
-                                    const void* c, int64_t c_ps, const float* scale, const float* shift, const float* mean,
-                                    const float* invstd, int relu, const double* red, double count, float* dgamma, float* dbeta,
-                                    void* gc, int64_t gc_ps, void* stream) {
-  const BnFin fin{red, count, dgamma, dbeta};
-  return bn_bwd_common(true, dtype, npix, C, ga, ga_ps, ga2, ga2_ps, c, c_ps, scale, shift, mean, invstd, relu, nullptr, nullptr, nullptr, gc, gc_ps, stream, &fin);
-}
-extern "C" int ubr_block_tail_bwd_apply_fin(int dtype, int64_t npix, int C, const void* go, int64_t go_ps, const void* go2, int64_t go2_ps,
-                                            const uint8_t* relu_mask, const void* c2, int64_t c2_ps,
-                                            const float* scale2, const float* shift2, const float* mean2, const float* invstd2,
-                                            const double* red2, float* dgamma2, float* dbeta2,
-                                            const void* cb, int64_t cb_ps, const float* scale_b, const float* mean_b, const float* invstd_b,
-                                            const double* red_b, float* dgamma_b, float* dbeta_b, double count,
-                                            void* g_c2, int64_t g_c2_ps, void* g_sc, int64_t g_sc_ps, void* stream) {
-  UBR_CHECK(relu_mask != nullptr, "ubr_block_tail_bwd_apply_fin: null mask");
-  const TailFin fin{red2, red_b, count, dgamma2, dbeta2, dgamma_b, dbeta_b};
-  return tail_bwd_common(true, dtype, npix, C, go, go_ps, go2, go2_ps, nullptr, 0, c2, c2_ps, scale2, shift2, mean2, invstd2,
-                         nullptr, nullptr, cb, cb_ps, scale_b, mean_b, invstd_b, nullptr, nullptr, nullptr, nullptr,
-                         g_c2, g_c2_ps, g_sc, g_sc_ps, stream, relu_mask, &fin);
-}
-
-// One-pass backward of frozen sites: the grid and the LDS carve-out of the reduce passes (every workgroup ends with a flush)
-extern "C" int ubr_block_tail_bwd_frozen(int dtype, int64_t npix, int C, const void* go, int64_t go_ps, const void* go2, int64_t go2_ps,
-                                         const uint8_t* relu_mask, const void* c2, int64_t c2_ps,
-                                         const float* scale2, const float* shift2, const float* mean2, const float* invstd2, double* red2,
-                                         const void* cb, int64_t cb_ps, const float* scale_b, const float* mean_b, const float* invstd_b,
-                                         double* red_b, void* g_c2, int64_t g_c2_ps, void* g_sc, int64_t g_sc_ps, void* stream) {
-  const char* who = "ubr_block_tail_bwd_frozen";
-  UBR_TRY(check_nhwc(who, dtype, npix, C, go, go_ps));
-  if (go2) UBR_TRY(check_nhwc(who, dtype, npix, C, go2, go2_ps));
-  UBR_TRY(check_nhwc(who, dtype, npix, C, c2, c2_ps));
-  if (cb) UBR_TRY(check_nhwc(who, dtype, npix, C, cb, cb_ps));
-  UBR_TRY(check_nhwc(who, dtype, npix, C, g_c2, g_c2_ps));
-  if (g_sc != nullptr || cb != nullptr) UBR_TRY(check_nhwc(who, dtype, npix, C, g_sc, g_sc_ps));
-  UBR_CHECK(relu_mask != nullptr && npix * (C / ubr_cpu(dtype)) < (int64_t)1 << 31, "%s: null mask, or mask exceeds 2 GiB", who);
-  UBR_CHECK(scale2 && shift2 && mean2 && invstd2 && red2, "%s: null bn2 constants or reduction buffer", who);
-  if (cb) UBR_CHECK(scale_b && mean_b && invstd_b && red_b, "%s: null bnpass constants or reduction buffer", who);
-  TailB k{};
-  k.npix = npix; k.C = C; k.CU = C / ubr_cpu(dtype);
-  k.go = go; k.go2 = go2; k.c2 = c2; k.cb = cb;
-  k.go_ps = go_ps; k.go2_ps = go2_ps; k.c2_ps = c2_ps; k.cb_ps = cb_ps;
-  k.s2 = scale2; k.t2 = shift2; k.m2 = mean2; k.i2 = invstd2;
-  k.sb = scale_b; k.mb = mean_b; k.ib = invstd_b;
-  k.red2 = red2; k.redb = red_b; k.g_c2 = g_c2; k.g_sc = g_sc; k.g_c2_ps = g_c2_ps; k.g_sc_ps = g_sc_ps;
-  k.relu_mask = relu_mask;
-  k.nslots = UBR_RED_SLOTS;
-  k.flush = red_flush_mode(k.CU, C, 4);
-  int red_iters = 8, red_blocks = 512;
-#ifdef UBR_TUNE
-  if (g_tune_red_iters) red_iters = g_tune_red_iters;
-  if (g_tune_red_blocks) red_blocks = g_tune_red_blocks;
-  if (g_tune_slots) k.nslots = g_tune_slots;
-  if (!g_tune_flush) k.flush = 0;
-#endif
-  const int blocks = pick_blocks(npix, k.CU, red_blocks, red_iters);
-  const size_t lds = (size_t)(k.flush ? 16 : 8) * 4 * C;
-  UBR_CHECK(lds <= 65536, "%s: C = %d needs more than 64 KiB of LDS", who, C);
-  const bool byp = cb != nullptr, g2 = go2 != nullptr;
-  UBR_DT_SWITCH(dtype, UBR_BOOL2(byp, g2, ubr_launch((tail_bwd_frozen_kernel<TT, B0, B1>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, k)));
-  UBR_LAUNCH_CHECK(who);
-  return UBR_OK;
-}
-extern "C" int ubr_bn_bwd_frozen(int dtype, int64_t npix, int C, const void* ga, int64_t ga_ps, const void* ga2, int64_t ga2_ps,
-                                 const void* c, int64_t c_ps, const float* scale, const float* shift, const float* mean,
-                                 const float* invstd, int relu, double* red, void* gc, int64_t gc_ps, void* stream) {
-  const char* who = "ubr_bn_bwd_frozen";
-  UBR_TRY(check_nhwc(who, dtype, npix, C, ga, ga_ps));
-  if (ga2) UBR_TRY(check_nhwc(who, dtype, npix, C, ga2, ga2_ps));
-  UBR_TRY(check_nhwc(who, dtype, npix, C, c, c_ps));
-  UBR_TRY(check_nhwc(who, dtype, npix, C, gc, gc_ps));
-  UBR_CHECK(scale && shift && mean && invstd, "%s: null bn constants", who);
-  BnB k{};
-  k.npix = npix; k.C = C; k.CU = C / ubr_cpu(dtype);
-  k.ga = ga; k.ga2 = ga2; k.c = c; k.ga_ps = ga_ps; k.ga2_ps = ga2_ps; k.c_ps = c_ps;
-  k.scale = scale; k.shift = shift; k.mean = mean; k.invstd = invstd; k.red = red; k.gc = gc; k.gc_ps = gc_ps;
-  k.nslots = UBR_RED_SLOTS;
-  k.flush = red_flush_mode(k.CU, C, 2);
-  int red_iters = 8, red_blocks = 512, app_blocks = 2048;
-#ifdef UBR_TUNE
-  if (g_tune_red_iters) red_iters = g_tune_red_iters;
-  if (g_tune_red_blocks) red_blocks = g_tune_red_blocks;
-  if (g_tune_app_blocks) app_blocks = g_tune_app_blocks;
-  if (g_tune_slots) k.nslots = g_tune_slots;
-  if (!g_tune_flush) k.flush = 0;
-#endif
-  const bool rd = red != nullptr, g2 = ga2 != nullptr, rl = relu != 0;
-  const int blocks = rd ? pick_blocks(npix, k.CU, red_blocks, red_iters) : pick_blocks(npix, k.CU, app_blocks, 4);
-  const size_t lds = rd ? (size_t)(k.flush ? 16 : 8) * 2 * C : 0;
-  UBR_CHECK(lds <= 65536, "%s: C = %d needs more than 64 KiB of LDS", who, C);
-  UBR_DT_SWITCH(dtype, UBR_BOOL3(g2, rl, rd, ubr_launch((bn_bwd_frozen_kernel<TT, B0, B1, B2>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, k)));
+  const PassTune t = pass_tune(&k.nslots, &k.flush);
+  const bool g2 = d->ga2.p != nullptr, rl = d->relu != 0, rd = s.red != nullptr;
+  const bool walk = pass == UBR_PASS_REDUCE || (pass == UBR_PASS_FROZEN && rd);     // ends with a flush of the sums
+  const int blocks = walk ? pick_blocks(npix, k.CU, t.red_blocks, t.red_iters) : pick_blocks(npix, k.CU, t.app_blocks, 4);
+  const size_t lds = walk ? (size_t)(k.flush ? 16 : 8) * 2 * C : pass == UBR_PASS_APPLY_FIN ? (size_t)8 * C : 0;
+  if (pass >= UBR_PASS_APPLY_FIN) UBR_CHECK(lds <= 65536, "%s: C = %d needs more than 64 KiB of LDS", who, C);
+  const hipStream_t st = (hipStream_t)stream;
+  if (pass == UBR_PASS_FROZEN) { UBR_DT_SWITCH(dtype, UBR_BOOL3(g2, rl, rd, ubr_launch((bn_bwd_frozen_kernel<TT, B0, B1, B2>), dim3(blocks), dim3(256), lds, st, k))); }
+  else if (pass == UBR_PASS_REDUCE) { UBR_DT_SWITCH(dtype, UBR_BOOL2(g2, rl, ubr_launch((bn_bwd_kernel<TT, false, B0, B1>), dim3(blocks), dim3(256), lds, st, k))); }
+  else { UBR_DT_SWITCH(dtype, UBR_BOOL2(g2, rl, ubr_launch((bn_bwd_kernel<TT, true, B0, B1>), dim3(blocks), dim3(256), lds, st, k))); }
   UBR_LAUNCH_CHECK(who);
   return UBR_OK;
 }
@@ -1477,9 +1330,8 @@ extern "C" int ubr_bn_eval_affine(const float* gamma, const float* beta, const f
   UBR_LAUNCH_CHECK("ubr_bn_eval_affine");
   return UBR_OK;
 }
-extern "C" int ubr_bn_bwd_finalize(const double* red, double count, const float* scale, const float* invstd,
-                                   int C, float* dgamma, float* dbeta, int accumulate, float* k1, float* k2, void* stream) {
-  (void)scale; (void)invstd;
+extern "C" int ubr_bn_bwd_finalize(const double* red, double count, int C, float* dgamma, float* dbeta, int accumulate,
+                                   float* k1, float* k2, void* stream) {
   UBR_CHECK(red && k1 && k2 && C > 0 && count >= 1.0, "ubr_bn_bwd_finalize: bad arguments");
   ubr_launch(bn_bwd_finalize_kernel, dim3(ubr_cdiv(C, 128)), dim3(128), 0, (hipStream_t)stream, red, count, C, dgamma, dbeta, accumulate, k1, k2);
   UBR_LAUNCH_CHECK("ubr_bn_bwd_finalize");

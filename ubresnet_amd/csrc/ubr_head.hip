@@ -588,4 +588,4 @@ extern "C" void ubr_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 extern "C" const char* ubr_last_error(void) { return g_err; }
-extern "C" int ubr_version(void) { return 1; }
+extern "C" int ubr_version(void) { return 2; }

@@ -11,7 +11,7 @@ only OWNS parameters; this executor runs the fused schedule explicitly:
     while loading its operand -- conv -> BN -> ReLU costs one write and one read.
   * frozen BatchNorm (a module in eval mode with running statistics, decided per module as nn.BatchNorm2d.forward does):
     the site's vectors come from the running statistics (nothing is accumulated or updated), and its backward is ONE
-    pass, g_c = scale*g_y, with dgamma / dbeta summed on the side (ubr_bn_bwd_frozen, ubr_block_tail_bwd_frozen).
+    pass, g_c = scale*g_y, with dgamma / dbeta summed on the side (UBR_PASS_FROZEN of ubr_bn_bwd and ubr_block_tail_bwd).
   * backward is scheduled by hand in reverse order; parameter gradients land in one flat fp32
     buffer laid out in completion order so data-parallel all-reduce can start per stage.
 """

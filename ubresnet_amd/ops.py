@@ -541,44 +541,53 @@ def _npix(t):
     return t.shape[0] * t.shape[1] * t.shape[2]
 
 
+def _pix(t):
+    """ubr_pix of a pixel-dense NHWC view; None = absent"""
+    return (None, 0) if t is None else (t.data_ptr(), _ps(t))
+
+
+def _site(scale=None, shift=None, mean=None, invstd=None, k1=None, k2=None, red=None, dgamma=None, dbeta=None):
+    """ubr_bn_site: what the pass does not use stays NULL"""
+    return tuple(None if t is None else t.data_ptr() for t in (scale, shift, mean, invstd, k1, k2, red, dgamma, dbeta))
+
+
+def _launch(entry, desc, t, what, /, **fields):
+    """fill the head every descriptor shares (dtype, C, npix: those of the tensor t) and the given fields, and call `entry`"""
+    d = desc(dtype=L.dtype_id(t.dtype), C=t.shape[3], npix=_npix(t), **fields)
+    L.check(getattr(L.lib(), entry)(C.byref(d), L.stream_ptr()), what)
+
+
+def _bn_bwd(pass_, what, ga, ga2, c, relu, bn, gc=None, count=0.0):
+    _launch("ubr_bn_bwd", L.BnBwdDesc, c, what, pass_=pass_, relu=1 if relu else 0, count=float(count),
+            ga=_pix(ga), ga2=_pix(ga2), c=_pix(c), gc=_pix(gc), bn=bn)
+
+
 @_timed("bn_bwd_reduce")
 def bn_bwd_reduce(ga, ga2, c, scale, shift, mean, invstd, relu, red):
-    L.check(L.lib().ubr_bn_bwd_reduce(L.dtype_id(c.dtype), _npix(c), c.shape[3], ga.data_ptr(), _ps(ga),
-                                      L.ptr(ga2), _ps(ga2) if ga2 is not None else 0, c.data_ptr(), _ps(c),
-                                      scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), 1 if relu else 0,
-                                      red.data_ptr(), L.stream_ptr()), "bn_bwd_reduce")
+    _bn_bwd(L.PASS_REDUCE, "bn_bwd_reduce", ga, ga2, c, relu, _site(scale, shift, mean, invstd, red=red))
 
 
 def bn_bwd_finalize(red, count, Cn, dgamma, dbeta, accumulate, k1, k2):
-    L.check(L.lib().ubr_bn_bwd_finalize(red.data_ptr(), float(count), None, None, Cn, L.ptr(dgamma), L.ptr(dbeta),
+    L.check(L.lib().ubr_bn_bwd_finalize(red.data_ptr(), float(count), Cn, L.ptr(dgamma), L.ptr(dbeta),
                                         1 if accumulate else 0, k1.data_ptr(), k2.data_ptr(), L.stream_ptr()), "bn_bwd_finalize")
 
 
 @_timed("bn_bwd_apply")
 def bn_bwd_apply(ga, ga2, c, scale, shift, mean, invstd, relu, k1, k2, gc):
-    L.check(L.lib().ubr_bn_bwd_apply(L.dtype_id(c.dtype), _npix(c), c.shape[3], ga.data_ptr(), _ps(ga),
-                                     L.ptr(ga2), _ps(ga2) if ga2 is not None else 0, c.data_ptr(), _ps(c),
-                                     scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), 1 if relu else 0,
-                                     k1.data_ptr(), k2.data_ptr(), gc.data_ptr(), _ps(gc), L.stream_ptr()), "bn_bwd_apply")
+    _bn_bwd(L.PASS_APPLY, "bn_bwd_apply", ga, ga2, c, relu, _site(scale, shift, mean, invstd, k1=k1, k2=k2), gc)
 
 
 @_timed("bn_bwd_apply")
 def bn_bwd_apply_fin(ga, ga2, c, scale, shift, mean, invstd, relu, red, count, dgamma, dbeta, gc):
     """apply pass with the finalize fused: k1 / k2 are formed from `red` inside the kernel, workgroup 0 writes dgamma / dbeta"""
-    L.check(L.lib().ubr_bn_bwd_apply_fin(L.dtype_id(c.dtype), _npix(c), c.shape[3], ga.data_ptr(), _ps(ga),
-                                         L.ptr(ga2), _ps(ga2) if ga2 is not None else 0, c.data_ptr(), _ps(c),
-                                         scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), 1 if relu else 0,
-                                         red.data_ptr(), float(count), L.ptr(dgamma), L.ptr(dbeta), gc.data_ptr(), _ps(gc), L.stream_ptr()),
-            "bn_bwd_apply_fin")
+    _bn_bwd(L.PASS_APPLY_FIN, "bn_bwd_apply_fin", ga, ga2, c, relu,
+            _site(scale, shift, mean, invstd, red=red, dgamma=dgamma, dbeta=dbeta), gc, count)
 
 
 @_timed("bn_bwd_frozen")
 def bn_bwd_frozen(ga, ga2, c, scale, shift, mean, invstd, relu, red, gc):
     """one-pass backward of a frozen site: g_c = scale * g_y, sums for dgamma / dbeta into `red` (None: already reduced)"""
-    L.check(L.lib().ubr_bn_bwd_frozen(L.dtype_id(c.dtype), _npix(c), c.shape[3], ga.data_ptr(), _ps(ga),
-                                      L.ptr(ga2), _ps(ga2) if ga2 is not None else 0, c.data_ptr(), _ps(c),
-                                      scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr(), 1 if relu else 0,
-                                      L.ptr(red), gc.data_ptr(), _ps(gc), L.stream_ptr()), "bn_bwd_frozen")
+    _bn_bwd(L.PASS_FROZEN, "bn_bwd_frozen", ga, ga2, c, relu, _site(scale, shift, mean, invstd, red=red), gc)
 
 
 def bn_bwd_finalize_frozen(red, Cn, dgamma, dbeta, k1=None, k2=None, stream=None):
@@ -590,16 +599,15 @@ def bn_bwd_finalize_frozen(red, Cn, dgamma, dbeta, k1=None, k2=None, stream=None
 # ------------------------------------------------------------------------------------------
 # BasicBlock tail
 # ------------------------------------------------------------------------------------------
+def _tail_fwd(what, c2, sc, out, relu_mask, **form):
+    _launch("ubr_block_tail_fwd", L.BlockTailFwdDesc, c2, what, c2=_pix(c2), sc=_pix(sc), out=_pix(out), relu_mask=L.ptr(relu_mask), **form)
+
+
 @_timed("block_tail_fwd")
 def block_tail_fwd(c2, mean2, scale2, shift2, sc, mean_b, scale_b, shift_b, out, relu_mask=None):
     """relu_mask: uint8 [npix * C / channels-per-unit], written with one bit per channel (stored output > 0) for the backward"""
-    a = (L.dtype_id(c2.dtype), _npix(c2), c2.shape[3], c2.data_ptr(), _ps(c2), mean2.data_ptr(),
-         scale2.data_ptr(), shift2.data_ptr(), sc.data_ptr(), _ps(sc), L.ptr(mean_b), L.ptr(scale_b),
-         L.ptr(shift_b), out.data_ptr(), _ps(out))
-    if relu_mask is None:
-        L.check(L.lib().ubr_block_tail_fwd(*a, L.stream_ptr()), "block_tail_fwd")
-    else:
-        L.check(L.lib().ubr_block_tail_fwd_masked(*a, relu_mask.data_ptr(), L.stream_ptr()), "block_tail_fwd_masked")
+    _tail_fwd("block_tail_fwd", c2, sc, out, relu_mask, mean2=L.ptr(mean2), scale2=L.ptr(scale2), shift2=L.ptr(shift2),
+              mean_b=L.ptr(mean_b), scale_b=L.ptr(scale_b), shift_b=L.ptr(shift_b))
 
 
 def bn_fwd_fin(stats, bn, scale, shift, mean, invstd) -> "L.BnFwdFin":
@@ -619,58 +627,46 @@ def bn_fwd_fin(stats, bn, scale, shift, mean, invstd) -> "L.BnFwdFin":
 @_timed("block_tail_fwd")
 def block_tail_fwd_fin(c2, fin2, sc, fin_b, count, out, relu_mask=None):
     """block tail forward with the BatchNorm finalize(s) of bn2 (and bnpass) fused: fin2 / fin_b from bn_fwd_fin()"""
-    L.check(L.lib().ubr_block_tail_fwd_fin(L.dtype_id(c2.dtype), _npix(c2), c2.shape[3], c2.data_ptr(), _ps(c2), C.byref(fin2),
-                                           sc.data_ptr(), _ps(sc), C.byref(fin_b) if fin_b is not None else None, float(count),
-                                           out.data_ptr(), _ps(out), L.ptr(relu_mask), L.stream_ptr()), "block_tail_fwd_fin")
+    _tail_fwd("block_tail_fwd_fin", c2, sc, out, relu_mask, count=float(count), fin2=C.pointer(fin2),
+              fin_b=C.pointer(fin_b) if fin_b is not None else None)
+
+
+def _tail_bwd(pass_, what, go, go2, out, relu_mask, c2, cb, bn2, bnb, g_c2=None, g_sc=None, count=0.0):
+    """relu_mask (from block_tail_fwd): read instead of `out`"""
+    _launch("ubr_block_tail_bwd", L.BlockTailBwdDesc, c2, what, pass_=pass_, count=float(count), go=_pix(go), go2=_pix(go2),
+            out=_pix(out if relu_mask is None else None), c2=_pix(c2), cb=_pix(cb), g_c2=_pix(g_c2), g_sc=_pix(g_sc),
+            relu_mask=L.ptr(relu_mask), bn2=bn2, bnb=bnb)
 
 
 @_timed("block_tail_bwd_reduce")
 def block_tail_bwd_reduce(go, go2, out, c2, scale2, shift2, mean2, invstd2, cb, mean_b, invstd_b, red2, red_b, relu_mask=None):
-    """relu_mask (from block_tail_fwd): read instead of `out`"""
-    head = (L.dtype_id(c2.dtype), _npix(c2), c2.shape[3], go.data_ptr(), _ps(go), L.ptr(go2), _ps(go2) if go2 is not None else 0)
-    rest = (c2.data_ptr(), _ps(c2), scale2.data_ptr(), shift2.data_ptr(), mean2.data_ptr(), invstd2.data_ptr(),
-            L.ptr(cb), _ps(cb) if cb is not None else 0, L.ptr(mean_b), L.ptr(invstd_b), red2.data_ptr(), L.ptr(red_b), L.stream_ptr())
-    if relu_mask is None:
-        L.check(L.lib().ubr_block_tail_bwd_reduce(*head, out.data_ptr(), _ps(out), *rest), "block_tail_bwd_reduce")
-    else:
-        L.check(L.lib().ubr_block_tail_bwd_reduce_masked(*head, relu_mask.data_ptr(), *rest), "block_tail_bwd_reduce_masked")
+    _tail_bwd(L.PASS_REDUCE, "block_tail_bwd_reduce", go, go2, out, relu_mask, c2, cb,
+              _site(scale2, shift2, mean2, invstd2, red=red2), _site(mean=mean_b, invstd=invstd_b, red=red_b))
 
 
 @_timed("block_tail_bwd_apply")
 def block_tail_bwd_apply(go, go2, out, c2, scale2, shift2, mean2, invstd2, k1_2, k2_2,
                          cb, scale_b, mean_b, invstd_b, k1_b, k2_b, g_c2, g_sc, relu_mask=None):
-    head = (L.dtype_id(c2.dtype), _npix(c2), c2.shape[3], go.data_ptr(), _ps(go), L.ptr(go2), _ps(go2) if go2 is not None else 0)
-    rest = (c2.data_ptr(), _ps(c2), scale2.data_ptr(), shift2.data_ptr(), mean2.data_ptr(), invstd2.data_ptr(),
-            k1_2.data_ptr(), k2_2.data_ptr(),
-            L.ptr(cb), _ps(cb) if cb is not None else 0, L.ptr(scale_b), L.ptr(mean_b), L.ptr(invstd_b), L.ptr(k1_b), L.ptr(k2_b),
-            g_c2.data_ptr(), _ps(g_c2), g_sc.data_ptr(), _ps(g_sc), L.stream_ptr())
-    if relu_mask is None:
-        L.check(L.lib().ubr_block_tail_bwd_apply(*head, out.data_ptr(), _ps(out), *rest), "block_tail_bwd_apply")
-    else:
-        L.check(L.lib().ubr_block_tail_bwd_apply_masked(*head, relu_mask.data_ptr(), *rest), "block_tail_bwd_apply_masked")
+    _tail_bwd(L.PASS_APPLY, "block_tail_bwd_apply", go, go2, out, relu_mask, c2, cb,
+              _site(scale2, shift2, mean2, invstd2, k1=k1_2, k2=k2_2),
+              _site(scale_b, mean=mean_b, invstd=invstd_b, k1=k1_b, k2=k2_b), g_c2, g_sc)
 
 
 @_timed("block_tail_bwd_apply")
 def block_tail_bwd_apply_fin(go, go2, relu_mask, c2, scale2, shift2, mean2, invstd2, red2, dgamma2, dbeta2,
                              cb, scale_b, mean_b, invstd_b, red_b, dgamma_b, dbeta_b, count, g_c2, g_sc):
     """masked apply pass with both finalizes fused; g_sc may be None on an identity block (skip gradient re-formed by the consumer)"""
-    L.check(L.lib().ubr_block_tail_bwd_apply_fin(
-        L.dtype_id(c2.dtype), _npix(c2), c2.shape[3], go.data_ptr(), _ps(go), L.ptr(go2), _ps(go2) if go2 is not None else 0,
-        relu_mask.data_ptr(), c2.data_ptr(), _ps(c2), scale2.data_ptr(), shift2.data_ptr(), mean2.data_ptr(), invstd2.data_ptr(),
-        red2.data_ptr(), L.ptr(dgamma2), L.ptr(dbeta2),
-        L.ptr(cb), _ps(cb) if cb is not None else 0, L.ptr(scale_b), L.ptr(mean_b), L.ptr(invstd_b), L.ptr(red_b), L.ptr(dgamma_b), L.ptr(dbeta_b),
-        float(count), g_c2.data_ptr(), _ps(g_c2), L.ptr(g_sc), _ps(g_sc) if g_sc is not None else 0, L.stream_ptr()), "block_tail_bwd_apply_fin")
+    _tail_bwd(L.PASS_APPLY_FIN, "block_tail_bwd_apply_fin", go, go2, None, relu_mask, c2, cb,
+              _site(scale2, shift2, mean2, invstd2, red=red2, dgamma=dgamma2, dbeta=dbeta2),
+              _site(scale_b, mean=mean_b, invstd=invstd_b, red=red_b, dgamma=dgamma_b, dbeta=dbeta_b), g_c2, g_sc, count)
 
 
 @_timed("block_tail_bwd_frozen")
 def block_tail_bwd_frozen(go, go2, relu_mask, c2, scale2, shift2, mean2, invstd2, red2,
                           cb, scale_b, mean_b, invstd_b, red_b, g_c2, g_sc):
     """one-pass backward of a block tail whose BatchNorm sites are all frozen; g_sc may be None on an identity block"""
-    L.check(L.lib().ubr_block_tail_bwd_frozen(
-        L.dtype_id(c2.dtype), _npix(c2), c2.shape[3], go.data_ptr(), _ps(go), L.ptr(go2), _ps(go2) if go2 is not None else 0,
-        relu_mask.data_ptr(), c2.data_ptr(), _ps(c2), scale2.data_ptr(), shift2.data_ptr(), mean2.data_ptr(), invstd2.data_ptr(),
-        red2.data_ptr(), L.ptr(cb), _ps(cb) if cb is not None else 0, L.ptr(scale_b), L.ptr(mean_b), L.ptr(invstd_b), L.ptr(red_b),
-        g_c2.data_ptr(), _ps(g_c2), L.ptr(g_sc), _ps(g_sc) if g_sc is not None else 0, L.stream_ptr()), "block_tail_bwd_frozen")
+    _tail_bwd(L.PASS_FROZEN, "block_tail_bwd_frozen", go, go2, None, relu_mask, c2, cb,
+              _site(scale2, shift2, mean2, invstd2, red=red2), _site(scale_b, mean=mean_b, invstd=invstd_b, red=red_b), g_c2, g_sc)
 
 
 # ------------------------------------------------------------------------------------------
