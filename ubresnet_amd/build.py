@@ -1,11 +1,12 @@
 """Build libubresnet_hip.so (all HIP kernels of the network + the C ABI), libubresnet_post.so (event products of
-whole-view inference), libubresnet_data.so (device-side batch preparation of the loader) and libubresnet_aug.so (device-side
-augmentation of training batches), the latter three self-contained libraries of their own, with hipcc for gfx950, in-tree.
+whole-view inference), libubresnet_data.so (device-side batch preparation of the loader), libubresnet_aug.so (device-side
+augmentation of training batches) and libubresnet_opt.so (the guarded flat optimizer step), the latter four self-contained
+libraries of their own, with hipcc for gfx950, in-tree.
 
     python -m ubresnet_amd.build [--force]
 
 The shared libraries have NO PyTorch dependency: they are plain HIP behind include/ubresnet_hip.h,
-include/ubresnet_post.h, include/ubresnet_data.h and include/ubresnet_aug.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
+include/ubresnet_post.h, include/ubresnet_data.h, include/ubresnet_aug.h and include/ubresnet_opt.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
 """
 import os
 import subprocess
@@ -29,6 +30,10 @@ DATA_HEADERS = [os.path.join("..", "..", "include", "ubresnet_data.h")]
 AUG_OUT = os.path.join(HERE, "libubresnet_aug.so")
 AUG_SOURCES = ["ubr_aug.hip"]
 AUG_HEADERS = [os.path.join("..", "..", "include", "ubresnet_aug.h")]
+# the fifth library: it links against none of the others either
+OPT_OUT = os.path.join(HERE, "libubresnet_opt.so")
+OPT_SOURCES = ["ubr_opt.hip"]
+OPT_HEADERS = [os.path.join("..", "..", "include", "ubresnet_opt.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=off"]
@@ -52,9 +57,10 @@ def _newer(target, deps):
 
 
 def build(force=False, verbose=True):
-    """compile what is out of date and link the four libraries; -> path of the main library"""
+    """compile what is out of date and link the five libraries; -> path of the main library"""
     libs = [(OUT, SOURCES, HEADERS), (POST_OUT, POST_SOURCES, POST_HEADERS),
-            (DATA_OUT, DATA_SOURCES, DATA_HEADERS), (AUG_OUT, AUG_SOURCES, AUG_HEADERS)]
+            (DATA_OUT, DATA_SOURCES, DATA_HEADERS), (AUG_OUT, AUG_SOURCES, AUG_HEADERS),
+            (OPT_OUT, OPT_SOURCES, OPT_HEADERS)]
     jobs, links = [], []
     for out, sources, headers in libs:
         hdrs = [os.path.join(CSRC, h) for h in headers]

@@ -13,9 +13,16 @@ once per epoch, and the rows are read back at every ``print_freq``-th batch and 
 ``track_shower=True`` keeps one more meter, the fifth figure of the LArCV1 drivers' ``accuracy()``
 (training/train_ubresnet2018_wlarcv1.py:584: classes 1 and 2 together), appends it to the log lines and to what is returned:
 ``train`` -> (loss, acc[1], track/shower), ``validate`` -> (total, track/shower).
+
+With a guarded optimizer (``FlatAdam(..., max_grad_norm=..., skip_nonfinite=True)``: ``optimizer.guard`` is set) ``train`` keeps
+one more device row per batch -- the gradient norm and whether the step was applied, copied from ``optimizer.guard.row()`` on
+the stream -- drains it with the others, and its log lines gain ``GradNorm %.3e (%.3e)  Skipped %d`` (last norm, average of the
+finite norms, steps skipped so far this epoch).  What it returns does not change.  The step comes after ``reducer.finish()``, so
+under data parallelism every rank takes the norm of the same reduced bytes and decides alike.
 """
 from __future__ import annotations
 
+import math
 import time
 
 import torch
@@ -50,8 +57,9 @@ class _EpochRecord(object):
     def __init__(self, nbatches, nclasses, track_shower=False):
         self.nbatches, self.nclasses = int(nbatches), int(nclasses)
         self.track_shower = AverageMeter() if track_shower else None            # the fifth meter, apart from acc_list
-        self.loss = self.cm = None
+        self.loss = self.cm = self.guard = None
         self.read = 0
+        self.gradnorm, self.skipped = AverageMeter(), 0                         # guarded optimizers only
         self.losses = AverageMeter()
         self.acc_list = [AverageMeter() for _ in range(self.nclasses + 1)]      # last accuracy is for total
 
@@ -69,10 +77,19 @@ class _EpochRecord(object):
         self.loss[i:i + 1].copy_(loss.detach().reshape(1))
         ops.confusion(pred.contiguous(), label.contiguous(), self.cm[i])
 
+    def put_guard(self, i, guard):
+        """row i <- (norm, scale, apply) of the guarded step just issued; a device-to-device copy on the stream"""
+        if self.guard is None:
+            self.guard = torch.zeros((self.nbatches, 3), dtype=torch.float32, device=guard.ctl.device)
+        self.guard[i].copy_(guard.row())
+
     def tail(self):
-        """what track_shower adds to a log line"""
+        """what track_shower and a guarded optimizer add to a log line"""
         ts = self.track_shower
-        return "" if ts is None else "\tAcc[trk/shr] %.3f (%.3f)" % (ts.val, ts.avg)
+        s = "" if ts is None else "\tAcc[trk/shr] %.3f (%.3f)" % (ts.val, ts.avg)
+        if self.guard is not None:
+            s += "\tGradNorm %.3e (%.3e)  Skipped %d" % (self.gradnorm.val, self.gradnorm.avg, self.skipped)
+        return s
 
     def drain(self, upto):
         if self.loss is None or upto <= self.read:
@@ -80,6 +97,13 @@ class _EpochRecord(object):
         C = self.nclasses
         loss = self.loss[self.read:upto].cpu()                                   # the host waits here, and only here
         cm = self.cm[self.read:upto].cpu()
+        if self.guard is not None:
+            for norm, _, applied in self.guard[self.read:upto].cpu().tolist():
+                if math.isfinite(norm):
+                    self.gradnorm.update(norm)
+                else:
+                    self.gradnorm.val = norm                                     # shown as the last value, kept out of the average
+                self.skipped += int(applied == 0.0)
         for j in range(upto - self.read):
             acc_values = metrics.accuracy_from_confusion(cm[j].view(C, C), track_shower=self.track_shower is not None)
             self.losses.update(loss[j].item())
@@ -123,6 +147,8 @@ def train(stager, model, criterion, optimizer, nbatches, iiter=0, nclasses=3, pr
         optimizer.step()
 
         rec.put(i, loss, pred_t, label_t)
+        if getattr(optimizer, "guard", None) is not None:
+            rec.put_guard(i, optimizer.guard)
         batch_time.update(time.time() - batchstart)           # host time: the device runs behind it between two read-backs
 
         if i % print_freq == 0:
