@@ -31,6 +31,14 @@ packed device copy is dropped behind the launch (it was allocated and used on th
 depends on ``(augment.seed, seq)`` alone, so neither thread timing nor ``skip(n)`` changes it.  A validation stager takes no
 ``augment``.
 
+``weights=PixelWeights(...)`` (ubresnet_amd/pixel_weights.py) makes the weight image on the device from the labels the network
+will see (converted, thresholded, cropped and flipped, the pad label included): behind ``ubd_prep_batch`` or
+``uba_augment_batch`` and before the event the consumer launches ``ubw_pixel_weights`` (libubresnet_weight.so) on the copy
+stream.  ``weights.when == "missing"`` does so only for a batch whose wire has no ``weight_<tag>`` entry (one that gets all ones
+without it), ``"always"`` for every batch; a wire weight that is replaced is not copied to the device.  ``stager.counts`` is
+then the ``[B,16]`` int64 device tensor of per-image class counts of the batch ``next()`` returned last (None where its weights
+came off the wire).  ``weights=None`` changes nothing.
+
 ``device=None`` runs the host half alone (``pin=False`` then needs no GPU at all): ``next()`` returns a ``HostBatch`` of numpy
 views of the slot, which stay valid until the following ``next()``, ``skip()`` or ``close()`` releases the slot.  Nothing is
 augmented there: ``stager.augment.params(batch.seq, B)`` gives the caller the batch's parameters.
@@ -66,7 +74,7 @@ class _Slot(object):
 
 class BatchStager(object):
     def __init__(self, loader, batchsize, height, width, planes=1, tag="train", device="cuda", threads=2, slots=None,
-                 label_offset=0, adc_threshold=None, timeout=60.0, pin=True, augment=None):
+                 label_offset=0, adc_threshold=None, timeout=60.0, pin=True, augment=None, weights=None):
         if threads < 1:
             raise ValueError("BatchStager: threads must be >= 1")
         self.loader, self.tag = loader, tag
@@ -77,6 +85,10 @@ class BatchStager(object):
         self.adc_threshold = None if adc_threshold is None else float(adc_threshold)
         self.timeout = float(timeout)
         self.augment = augment
+        self.weights = weights
+        self.counts = None
+        if weights is not None and device is None:
+            raise ValueError("BatchStager: weights are made on the device; device=None (the host half alone) takes none")
         nslots = int(slots) if slots is not None else int(threads) + 1
         if nslots < 1:
             raise ValueError("BatchStager: slots must be >= 1")
@@ -97,6 +109,10 @@ class BatchStager(object):
                 _aug.lib()
                 if b > _aug.MAX_BATCH:
                     raise ValueError("BatchStager: augment takes at most %d images per batch (got %d)" % (_aug.MAX_BATCH, b))
+            if weights is not None:
+                from . import _weight
+                self._weight = _weight
+                _weight.lib()
             self.stream = torch.cuda.Stream(device=self.device)
         self._slots = [_Slot(i, (p + 2) * self.npix, pin) for i in range(nslots)]
         self._free = collections.deque(self._slots)
@@ -109,7 +125,7 @@ class BatchStager(object):
         self._halt = False                                 # a batch failed: no producer begins another one
         self._closed = False
         self._held = None                                  # host mode: the slot whose views the caller holds
-        self._inflight = None                              # device mode: (tensors, event) of the staged batch, or an exception
+        self._inflight = None                              # device mode: (tensors, event, counts) of the staged batch, or an exception
         self._times = {"loader": [0.0, 0], "fill": [0.0, 0], "wait_slot": [0.0, 0]}
         self._nthreads = int(threads)
         self._threads = []
@@ -243,18 +259,21 @@ class BatchStager(object):
         with torch.cuda.stream(self.stream):
             packed = torch.empty((p + 2) * n, dtype=torch.float32, device=self.device)
             label = torch.empty((b, h, w), dtype=torch.int64, device=self.device)
-            m = (p + 2) * n if slot.has_weight else (p + 1) * n
+            make = self._makes_weights(slot)
+            m = (p + 2) * n if slot.has_weight and not make else (p + 1) * n
             packed[:m].copy_(slot.tensor[:m] if slot.tensor is not None else torch.from_numpy(slot.array[:m]),
                              non_blocking=slot.tensor is not None)
             base = packed.data_ptr()
             self._data.prep_batch(base + 4 * p * n, label.data_ptr(), n, self.label_offset, image=base, planes=p, hw=h * w,
-                                  threshold=self.adc_threshold, weight_fill=None if slot.has_weight else base + 4 * (p + 1) * n,
+                                  threshold=self.adc_threshold,
+                                  weight_fill=None if slot.has_weight or make else base + 4 * (p + 1) * n,
                                   stream=self.stream.cuda_stream)
+            counts = self._launch_weights(label, base + 4 * (p + 1) * n) if make else None
             ev = torch.cuda.Event()
             ev.record(self.stream)
         slot.event = ev
         self._release(slot)
-        self._inflight = ((packed[:p * n].view(b, p, h, w), label, packed[(p + 1) * n:].view(b, h, w)), ev)
+        self._inflight = ((packed[:p * n].view(b, p, h, w), label, packed[(p + 1) * n:].view(b, h, w)), ev, counts)
 
     def _issue_augmented(self, slot, seq):
         """_issue with an Augment: the same copy, then uba_augment_batch out of the packed copy into three fresh tensors"""
@@ -267,20 +286,32 @@ class BatchStager(object):
             adc = torch.empty((b, p, h, w), dtype=torch.float32, device=self.device)
             label = torch.empty((b, h, w), dtype=torch.int64, device=self.device)
             weight = torch.empty((b, h, w), dtype=torch.float32, device=self.device)
-            m = (p + 2) * n if slot.has_weight else (p + 1) * n
+            make = self._makes_weights(slot)
+            m = (p + 2) * n if slot.has_weight and not make else (p + 1) * n
             packed[:m].copy_(slot.tensor[:m] if slot.tensor is not None else torch.from_numpy(slot.array[:m]),
                              non_blocking=slot.tensor is not None)
             base = packed.data_ptr()
-            self._aug.augment_batch(base, base + 4 * p * n, base + 4 * (p + 1) * n if slot.has_weight else None,
+            self._aug.augment_batch(base, base + 4 * p * n, base + 4 * (p + 1) * n if slot.has_weight and not make else None,
                                     adc.data_ptr(), label.data_ptr(), weight.data_ptr(), self.shape, aug.pad,
                                     aug.params(seq, b), label_offset=self.label_offset, threshold=self.adc_threshold,
                                     pad_label=aug.pad_label, pad_weight=aug.pad_weight, stream=self.stream.cuda_stream)
+            counts = self._launch_weights(label, weight.data_ptr()) if make else None
             ev = torch.cuda.Event()
             ev.record(self.stream)
         del packed                                          # allocated and used on the copy stream only: its reuse is ordered
         slot.event = ev
         self._release(slot)
-        self._inflight = ((adc, label, weight), ev)
+        self._inflight = ((adc, label, weight), ev, counts)
+
+    def _makes_weights(self, slot):
+        return self.weights is not None and (self.weights.when == "always" or not slot.has_weight)
+
+    def _launch_weights(self, label, weight_ptr):
+        """ubw_pixel_weights on the copy stream (the caller has made it current): `label` -> the weights at `weight_ptr`;
+        -> the counts tensor"""
+        counts = self._torch.empty((self.shape[0], self._weight.MAX_CLASSES), dtype=self._torch.int64, device=self.device)
+        self.weights.launch(label.data_ptr(), weight_ptr, counts.data_ptr(), tuple(label.shape), self.stream.cuda_stream)
+        return counts
 
     def _staged(self):
         """take the staged batch; what it hit while it was staged is raised by the call it belongs to"""
@@ -308,11 +339,14 @@ class BatchStager(object):
                              a[(p + 1) * n:].reshape(b, h, w) if slot.has_weight else None)
         if self._inflight is None:
             self._issue()
-        dev, ev = self._staged()
+        dev, ev, counts = self._staged()
         cur = self._torch.cuda.current_stream(self.device)
         cur.wait_event(ev)
         for t in dev:
             t.record_stream(cur)
+        if counts is not None:
+            counts.record_stream(cur)
+        self.counts = counts
         self._issue()
         return dev
 
