@@ -65,10 +65,11 @@ def _stitch_products(logp, nclass, th, tw, tiles, adc, vplanes, adc_threshold, f
 
 
 def load_model(checkpointfile: Optional[str], device, num_classes: int = 4, inplanes: int = 16, input_channels: int = 1,
-               map_location=None, state_dict=None, arch: str = "uresnet"):
+               map_location=None, state_dict=None, arch: str = "uresnet", ema: bool = False):
     """UResNet (arch="uresnet") or ASPP_ResNet (arch="aspp") for deployment (deploy/ubresnet_funcs.py:41-68).
     `checkpointfile` is the reference's ``{iter, epoch, state_dict, best_prec1, optimizer}`` tar; tensors only are
-    read (weights_only)."""
+    read (weights_only).  `ema=True`: the checkpoint dict carries ``"ema": ParamEMA.state_dict()`` and the averaged tensors
+    in it override those of ``state_dict``; a checkpoint without that entry is a KeyError."""
     if arch == "uresnet":
         from .models.ub_uresnet import UResNet
         model = UResNet(inplanes=inplanes, input_channels=input_channels, num_classes=num_classes, showsizes=False)
@@ -80,6 +81,15 @@ def load_model(checkpointfile: Optional[str], device, num_classes: int = 4, inpl
     if state_dict is None and checkpointfile is not None:
         ckpt = torch.load(checkpointfile, map_location=map_location or "cpu", weights_only=True)
         state_dict = ckpt["state_dict"] if isinstance(ckpt, dict) and "state_dict" in ckpt else ckpt
+        if ema:
+            if not (isinstance(ckpt, dict) and isinstance(ckpt.get("ema"), dict)):
+                raise KeyError("load_model(ema=True): the checkpoint %s has no \"ema\" entry (add \"ema\": ema.state_dict() to "
+                               "the dict given to save_checkpoint)" % checkpointfile)
+            state_dict = dict(state_dict)
+            state_dict.update(ckpt["ema"]["shadow"])
+            state_dict.update(ckpt["ema"].get("stats", {}))
+    elif ema:
+        raise KeyError("load_model(ema=True) needs a checkpoint file whose dict has an \"ema\" entry")
     if state_dict is not None:
         clean = {}
         for k, v in state_dict.items():

@@ -19,9 +19,15 @@ one more device row per batch -- the gradient norm and whether the step was appl
 the stream -- drains it with the others, and its log lines gain ``GradNorm %.3e (%.3e)  Skipped %d`` (last norm, average of the
 finite norms, steps skipped so far this epoch).  What it returns does not change.  The step comes after ``reducer.finish()``, so
 under data parallelism every rank takes the norm of the same reduced bytes and decides alike.
+
+With ``ema=ParamEMA(optimizer, ...)`` (ubresnet_amd/ema.py) ``train`` calls ``ema.update()`` right after ``optimizer.step()`` and its
+log lines gain ``EMA %d/%d`` (updates applied / withheld so far), read where the other rows are drained, never per step;
+``validate`` runs its whole loop inside ``ema.applied()``: the model is evaluated with the averaged weights and has its own back
+afterwards.  With ``ema=None`` (the default) both loops are what they were.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import time
 
@@ -60,6 +66,7 @@ class _EpochRecord(object):
         self.loss = self.cm = self.guard = None
         self.read = 0
         self.gradnorm, self.skipped = AverageMeter(), 0                         # guarded optimizers only
+        self.ema, self.ema_counts = None, (0, 0)                                # train(..., ema=...) only
         self.losses = AverageMeter()
         self.acc_list = [AverageMeter() for _ in range(self.nclasses + 1)]      # last accuracy is for total
 
@@ -89,6 +96,8 @@ class _EpochRecord(object):
         s = "" if ts is None else "\tAcc[trk/shr] %.3f (%.3f)" % (ts.val, ts.avg)
         if self.guard is not None:
             s += "\tGradNorm %.3e (%.3e)  Skipped %d" % (self.gradnorm.val, self.gradnorm.avg, self.skipped)
+        if self.ema is not None:
+            s += "\tEMA %d/%d" % self.ema_counts
         return s
 
     def drain(self, upto):
@@ -104,6 +113,8 @@ class _EpochRecord(object):
                 else:
                     self.gradnorm.val = norm                                     # shown as the last value, kept out of the average
                 self.skipped += int(applied == 0.0)
+        if self.ema is not None:
+            self.ema_counts = self.ema.counts()
         for j in range(upto - self.read):
             acc_values = metrics.accuracy_from_confusion(cm[j].view(C, C), track_shower=self.track_shower is not None)
             self.losses.update(loss[j].item())
@@ -121,11 +132,12 @@ def _flush(criterion):
 
 
 def train(stager, model, criterion, optimizer, nbatches, iiter=0, nclasses=3, print_freq=10, reducer=None, log=print,
-          track_shower=False):
+          track_shower=False, ema=None):
     """one epoch of `nbatches` train steps fed by `stager.next()`; -> (losses.avg, acc_list[1].avg) as the reference (:396),
-    with `track_shower` -> (losses.avg, acc_list[1].avg, track/shower avg)"""
+    with `track_shower` -> (losses.avg, acc_list[1].avg, track/shower avg); `ema`: a ParamEMA updated after every step"""
     batch_time, data_time = AverageMeter(), AverageMeter()
     rec = _EpochRecord(nbatches, nclasses, track_shower)
+    rec.ema = ema
 
     # switch to train mode
     model.train()
@@ -145,6 +157,8 @@ def train(stager, model, criterion, optimizer, nbatches, iiter=0, nclasses=3, pr
         if reducer is not None:
             reducer.finish()
         optimizer.step()
+        if ema is not None:
+            ema.update()
 
         rec.put(i, loss, pred_t, label_t)
         if getattr(optimizer, "guard", None) is not None:
@@ -166,16 +180,17 @@ def train(stager, model, criterion, optimizer, nbatches, iiter=0, nclasses=3, pr
     return rec.losses.avg, rec.acc_list[1].avg
 
 
-def validate(stager, model, criterion, nbatches, iiter=0, nclasses=3, print_freq=10, log=print, track_shower=False):
+def validate(stager, model, criterion, nbatches, iiter=0, nclasses=3, print_freq=10, log=print, track_shower=False, ema=None):
     """`nbatches` batches of `stager.next()` through the model in eval mode, without gradients (the folded inference schedule);
-    -> float(acc_list[-1].avg), the average total accuracy in percent (:471), with `track_shower` -> (that, track/shower avg)"""
+    -> float(acc_list[-1].avg), the average total accuracy in percent (:471), with `track_shower` -> (that, track/shower avg);
+    `ema`: a ParamEMA whose averaged weights the model computes with for the length of the loop"""
     batch_time, load_data = AverageMeter(), AverageMeter()
     rec = _EpochRecord(nbatches, nclasses, track_shower)
 
     # switch to evaluate mode
     model.eval()
 
-    with torch.no_grad():
+    with torch.no_grad(), (ema.applied() if ema is not None else contextlib.nullcontext()):
         for i in range(0, nbatches):
             batchstart = time.time()
             adc_t, label_t, weight_t = stager.next()
