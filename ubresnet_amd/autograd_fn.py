@@ -74,6 +74,9 @@ class _NetFn(torch.autograd.Function):
         # Accumulation semantics are kept: an existing .grad is added to, never overwritten.
         if not accumulating:
             ctx.model.__dict__["_ubr_flat_grad"] = flat
+        # (for accum.GradAccumulator: an accumulated pass adds IN PLACE into .grad tensors that are still the views of an earlier
+        # pass's flat buffer, so their addresses do not tell that it happened)
+        ctx.model.__dict__["_ubr_grad_accumulated"] = accumulating
         for p in ctx.params:
             if not p.requires_grad:
                 continue

@@ -1,14 +1,14 @@
 """Build libubresnet_hip.so (all HIP kernels of the network + the C ABI), libubresnet_post.so (event products of
 whole-view inference), libubresnet_data.so (device-side batch preparation of the loader), libubresnet_aug.so (device-side
 augmentation of training batches), libubresnet_opt.so (the guarded flat optimizer step), libubresnet_weight.so (device-side
-pixel weights of the loss), libubresnet_group.so (flat optimizer steps with parameter groups) and libubresnet_ema.so (the
-exponential moving average of the parameters), the latter seven self-contained libraries of their own, with hipcc for gfx950,
-in-tree.
+pixel weights of the loss), libubresnet_group.so (flat optimizer steps with parameter groups), libubresnet_ema.so (the
+exponential moving average of the parameters) and libubresnet_accum.so (gradient accumulation over the flat gradient buffer),
+the latter eight self-contained libraries of their own, with hipcc for gfx950, in-tree.
 
     python -m ubresnet_amd.build [--force]
 
 The shared libraries have NO PyTorch dependency: they are plain HIP behind include/ubresnet_hip.h,
-include/ubresnet_post.h, include/ubresnet_data.h, include/ubresnet_aug.h, include/ubresnet_opt.h, include/ubresnet_weight.h, include/ubresnet_group.h and include/ubresnet_ema.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
+include/ubresnet_post.h, include/ubresnet_data.h, include/ubresnet_aug.h, include/ubresnet_opt.h, include/ubresnet_weight.h, include/ubresnet_group.h, include/ubresnet_ema.h and include/ubresnet_accum.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
 """
 import os
 import subprocess
@@ -48,6 +48,10 @@ GROUP_HEADERS = ["ubr_group_plan.h", os.path.join("..", "..", "include", "ubresn
 EMA_OUT = os.path.join(HERE, "libubresnet_ema.so")
 EMA_SOURCES = ["ubr_ema.hip"]
 EMA_HEADERS = ["ubr_ema_sched.h", os.path.join("..", "..", "include", "ubresnet_ema.h")]
+# the ninth library: it links against none of the others either
+ACCUM_OUT = os.path.join(HERE, "libubresnet_accum.so")
+ACCUM_SOURCES = ["ubr_accum.hip"]
+ACCUM_HEADERS = [os.path.join("..", "..", "include", "ubresnet_accum.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=off"]
@@ -71,11 +75,12 @@ def _newer(target, deps):
 
 
 def build(force=False, verbose=True):
-    """compile what is out of date and link the eight libraries; -> path of the main library"""
+    """compile what is out of date and link the nine libraries; -> path of the main library"""
     libs = [(OUT, SOURCES, HEADERS), (POST_OUT, POST_SOURCES, POST_HEADERS),
             (DATA_OUT, DATA_SOURCES, DATA_HEADERS), (AUG_OUT, AUG_SOURCES, AUG_HEADERS),
             (OPT_OUT, OPT_SOURCES, OPT_HEADERS), (WEIGHT_OUT, WEIGHT_SOURCES, WEIGHT_HEADERS),
-            (GROUP_OUT, GROUP_SOURCES, GROUP_HEADERS), (EMA_OUT, EMA_SOURCES, EMA_HEADERS)]
+            (GROUP_OUT, GROUP_SOURCES, GROUP_HEADERS), (EMA_OUT, EMA_SOURCES, EMA_HEADERS),
+            (ACCUM_OUT, ACCUM_SOURCES, ACCUM_HEADERS)]
     jobs, links = [], []
     for out, sources, headers in libs:
         hdrs = [os.path.join(CSRC, h) for h in headers]

@@ -24,6 +24,13 @@ With ``ema=ParamEMA(optimizer, ...)`` (ubresnet_amd/ema.py) ``train`` calls ``em
 log lines gain ``EMA %d/%d`` (updates applied / withheld so far), read where the other rows are drained, never per step;
 ``validate`` runs its whole loop inside ``ema.applied()``: the model is evaluated with the averaged weights and has its own back
 afterwards.  With ``ema=None`` (the default) both loops are what they were.
+
+With ``accumulate=K`` (K > 1) ``train`` takes one optimizer step per K batches: a ``GradAccumulator(model, every=K)``
+(ubresnet_amd/accum.py) sums the micro-batches' flat gradients on the device and leaves their mean in the flat gradient buffer of
+the K-th, where the optimizer reads it; ``optimizer.step()``, ``ema.update()`` and the guard row happen on that batch only, and
+the ``zero_grad()`` before every backward keeps each one a plain, replayed pass.  ``nbatches`` must be a multiple of K.  Loss and
+confusion rows, hence the meters and what is returned, stay per batch; ``GradNorm`` / ``Skipped`` count optimizer steps.  With
+``accumulate=1`` (the default) the loop is what it was.
 """
 from __future__ import annotations
 
@@ -64,6 +71,7 @@ class _EpochRecord(object):
         self.nbatches, self.nclasses = int(nbatches), int(nclasses)
         self.track_shower = AverageMeter() if track_shower else None            # the fifth meter, apart from acc_list
         self.loss = self.cm = self.guard = None
+        self.guard_rows = []                                                    # the rows of self.guard that were written, ascending
         self.read = 0
         self.gradnorm, self.skipped = AverageMeter(), 0                         # guarded optimizers only
         self.ema, self.ema_counts = None, (0, 0)                                # train(..., ema=...) only
@@ -89,6 +97,7 @@ class _EpochRecord(object):
         if self.guard is None:
             self.guard = torch.zeros((self.nbatches, 3), dtype=torch.float32, device=guard.ctl.device)
         self.guard[i].copy_(guard.row())
+        self.guard_rows.append(i)
 
     def tail(self):
         """what track_shower and a guarded optimizer add to a log line"""
@@ -107,7 +116,9 @@ class _EpochRecord(object):
         loss = self.loss[self.read:upto].cpu()                                   # the host waits here, and only here
         cm = self.cm[self.read:upto].cpu()
         if self.guard is not None:
-            for norm, _, applied in self.guard[self.read:upto].cpu().tolist():
+            rows = self.guard[self.read:upto].cpu().tolist()
+            # (with train(..., accumulate=K) only every K-th row is written: a row without a step is not a skipped step)
+            for norm, _, applied in (rows[j - self.read] for j in self.guard_rows if self.read <= j < upto):
                 if math.isfinite(norm):
                     self.gradnorm.update(norm)
                 else:
@@ -132,9 +143,19 @@ def _flush(criterion):
 
 
 def train(stager, model, criterion, optimizer, nbatches, iiter=0, nclasses=3, print_freq=10, reducer=None, log=print,
-          track_shower=False, ema=None):
+          track_shower=False, accumulate=1, ema=None):
     """one epoch of `nbatches` train steps fed by `stager.next()`; -> (losses.avg, acc_list[1].avg) as the reference (:396),
-    with `track_shower` -> (losses.avg, acc_list[1].avg, track/shower avg); `ema`: a ParamEMA updated after every step"""
+    with `track_shower` -> (losses.avg, acc_list[1].avg, track/shower avg); `ema`: a ParamEMA updated after every step;
+    `accumulate`: batches per optimizer step (their gradients are averaged on the device; `nbatches` must be a multiple)"""
+    if int(accumulate) != accumulate or int(accumulate) < 1:
+        raise ValueError("accumulate must be an integer >= 1, got %r" % (accumulate,))
+    accumulate = int(accumulate)
+    if nbatches % accumulate != 0:
+        raise ValueError("nbatches=%d is not a multiple of accumulate=%d: the last optimizer step would be left open" % (nbatches, accumulate))
+    acc = None
+    if accumulate > 1:
+        from ubresnet_amd.accum import GradAccumulator
+        acc = GradAccumulator(model, every=accumulate)
     batch_time, data_time = AverageMeter(), AverageMeter()
     rec = _EpochRecord(nbatches, nclasses, track_shower)
     rec.ema = ema
@@ -156,12 +177,14 @@ def train(stager, model, criterion, optimizer, nbatches, iiter=0, nclasses=3, pr
         loss.backward()
         if reducer is not None:
             reducer.finish()
-        optimizer.step()
-        if ema is not None:
-            ema.update()
+        stepped = acc is None or acc.add()                    # accumulate=K: True on every K-th batch, the mean is in place
+        if stepped:
+            optimizer.step()
+            if ema is not None:
+                ema.update()
 
         rec.put(i, loss, pred_t, label_t)
-        if getattr(optimizer, "guard", None) is not None:
+        if stepped and getattr(optimizer, "guard", None) is not None:
             rec.put_guard(i, optimizer.guard)
         batch_time.update(time.time() - batchstart)           # host time: the device runs behind it between two read-backs
 
