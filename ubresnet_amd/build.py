@@ -2,13 +2,16 @@
 whole-view inference), libubresnet_data.so (device-side batch preparation of the loader), libubresnet_aug.so (device-side
 augmentation of training batches), libubresnet_opt.so (the guarded flat optimizer step), libubresnet_weight.so (device-side
 pixel weights of the loss), libubresnet_group.so (flat optimizer steps with parameter groups), libubresnet_ema.so (the
-exponential moving average of the parameters) and libubresnet_accum.so (gradient accumulation over the flat gradient buffer),
-the latter eight self-contained libraries of their own, with hipcc for gfx950, in-tree.
+exponential moving average of the parameters), libubresnet_accum.so (gradient accumulation over the flat gradient buffer) and
+libubresnet_stats.so (the guard of the BatchNorm running statistics), the latter nine self-contained libraries of their own, with
+hipcc for gfx950, in-tree.
 
     python -m ubresnet_amd.build [--force]
 
 The shared libraries have NO PyTorch dependency: they are plain HIP behind include/ubresnet_hip.h,
-include/ubresnet_post.h, include/ubresnet_data.h, include/ubresnet_aug.h, include/ubresnet_opt.h, include/ubresnet_weight.h, include/ubresnet_group.h, include/ubresnet_ema.h and include/ubresnet_accum.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
+include/ubresnet_post.h, include/ubresnet_data.h, include/ubresnet_aug.h, include/ubresnet_opt.h, include/ubresnet_weight.h, include/ubresnet_group.h, include/ubresnet_ema.h, include/ubresnet_accum.h and include/ubresnet_stats.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
+
+build() makes the first nine, build_stats() the tenth by the same steps; the command line and the driver entry point call both.
 """
 import os
 import subprocess
@@ -52,6 +55,10 @@ EMA_HEADERS = ["ubr_ema_sched.h", os.path.join("..", "..", "include", "ubresnet_
 ACCUM_OUT = os.path.join(HERE, "libubresnet_accum.so")
 ACCUM_SOURCES = ["ubr_accum.hip"]
 ACCUM_HEADERS = [os.path.join("..", "..", "include", "ubresnet_accum.h")]
+# the tenth library: it links against none of the others either
+STATS_OUT = os.path.join(HERE, "libubresnet_stats.so")
+STATS_SOURCES = ["ubr_stats.hip"]
+STATS_HEADERS = ["ubr_stats_decide.h", os.path.join("..", "..", "include", "ubresnet_stats.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=off"]
@@ -81,6 +88,17 @@ def build(force=False, verbose=True):
             (OPT_OUT, OPT_SOURCES, OPT_HEADERS), (WEIGHT_OUT, WEIGHT_SOURCES, WEIGHT_HEADERS),
             (GROUP_OUT, GROUP_SOURCES, GROUP_HEADERS), (EMA_OUT, EMA_SOURCES, EMA_HEADERS),
             (ACCUM_OUT, ACCUM_SOURCES, ACCUM_HEADERS)]
+    _build(libs, force, verbose)
+    return OUT
+
+
+def build_stats(force=False, verbose=True):
+    """the tenth library by the same steps: one more (OUT, SOURCES, HEADERS) tuple; -> its path"""
+    _build([(STATS_OUT, STATS_SOURCES, STATS_HEADERS)], force, verbose)
+    return STATS_OUT
+
+
+def _build(libs, force, verbose):
     jobs, links = [], []
     for out, sources, headers in libs:
         hdrs = [os.path.join(CSRC, h) for h in headers]
@@ -115,8 +133,8 @@ def build(force=False, verbose=True):
             if r.returncode != 0:
                 sys.stderr.write(r.stdout + r.stderr)
                 raise RuntimeError("link failed")
-    return OUT
 
 
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
+    print(build_stats(force="--force" in sys.argv))

@@ -149,6 +149,8 @@ class ParamEMA(object):
             self._check_table()
             E.swap_segs(self._table.data_ptr(), len(self._stats), L.stream_ptr())
         self._swapped = not self._swapped
+        # (how many averages are swapped into this model now: a StatsGuard refuses to resolve over them)
+        self.model.__dict__["_ube_swapped"] = self.model.__dict__.get("_ube_swapped", 0) + (1 if self._swapped else -1)
 
     @contextlib.contextmanager
     def applied(self):

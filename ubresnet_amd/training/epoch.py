@@ -31,6 +31,13 @@ the K-th, where the optimizer reads it; ``optimizer.step()``, ``ema.update()`` a
 the ``zero_grad()`` before every backward keeps each one a plain, replayed pass.  ``nbatches`` must be a multiple of K.  Loss and
 confusion rows, hence the meters and what is returned, stay per batch; ``GradNorm`` / ``Skipped`` count optimizer steps.  With
 ``accumulate=1`` (the default) the loop is what it was.
+
+With ``stats_guard=StatsGuard(model, optimizer=optimizer)`` (ubresnet_amd/bnguard.py) ``train`` calls ``stats_guard.resolve()``
+right after ``optimizer.step()`` and before ``ema.update()`` -- the average then sees the restored statistics -- on the batches
+that take an optimizer step only: with ``accumulate=K`` a bad micro-batch rolls the BatchNorm running statistics back over the
+whole cycle of K.  It keeps one more device row per step, copied from ``stats_guard.row()`` on the stream and drained with the
+others, and the log lines gain ``BNRestored %d`` (restores so far this epoch).  With ``stats_guard=None`` (the default) the loop is
+what it was.  ``validate`` does not take it: eval mode writes no statistics.
 """
 from __future__ import annotations
 
@@ -75,6 +82,7 @@ class _EpochRecord(object):
         self.read = 0
         self.gradnorm, self.skipped = AverageMeter(), 0                         # guarded optimizers only
         self.ema, self.ema_counts = None, (0, 0)                                # train(..., ema=...) only
+        self.stats, self.stats_rows, self.bn_restored = None, [], 0             # train(..., stats_guard=...) only
         self.losses = AverageMeter()
         self.acc_list = [AverageMeter() for _ in range(self.nclasses + 1)]      # last accuracy is for total
 
@@ -99,6 +107,13 @@ class _EpochRecord(object):
         self.guard[i].copy_(guard.row())
         self.guard_rows.append(i)
 
+    def put_stats(self, i, stats_guard):
+        """row i <- (keep, bad_rows) of the decision just issued; a device-to-device copy on the stream"""
+        if self.stats is None:
+            self.stats = torch.zeros((self.nbatches, 2), dtype=torch.int32, device=stats_guard.ctl.device)
+        self.stats[i].copy_(stats_guard.row())
+        self.stats_rows.append(i)
+
     def tail(self):
         """what track_shower and a guarded optimizer add to a log line"""
         ts = self.track_shower
@@ -107,6 +122,8 @@ class _EpochRecord(object):
             s += "\tGradNorm %.3e (%.3e)  Skipped %d" % (self.gradnorm.val, self.gradnorm.avg, self.skipped)
         if self.ema is not None:
             s += "\tEMA %d/%d" % self.ema_counts
+        if self.stats is not None:
+            s += "\tBNRestored %d" % self.bn_restored
         return s
 
     def drain(self, upto):
@@ -126,6 +143,9 @@ class _EpochRecord(object):
                 self.skipped += int(applied == 0.0)
         if self.ema is not None:
             self.ema_counts = self.ema.counts()
+        if self.stats is not None:
+            rows = self.stats[self.read:upto].cpu().tolist()
+            self.bn_restored += sum(int(rows[j - self.read][0] == 0) for j in self.stats_rows if self.read <= j < upto)
         for j in range(upto - self.read):
             acc_values = metrics.accuracy_from_confusion(cm[j].view(C, C), track_shower=self.track_shower is not None)
             self.losses.update(loss[j].item())
@@ -143,10 +163,11 @@ def _flush(criterion):
 
 
 def train(stager, model, criterion, optimizer, nbatches, iiter=0, nclasses=3, print_freq=10, reducer=None, log=print,
-          track_shower=False, accumulate=1, ema=None):
+          track_shower=False, accumulate=1, stats_guard=None, ema=None):
     """one epoch of `nbatches` train steps fed by `stager.next()`; -> (losses.avg, acc_list[1].avg) as the reference (:396),
     with `track_shower` -> (losses.avg, acc_list[1].avg, track/shower avg); `ema`: a ParamEMA updated after every step;
-    `accumulate`: batches per optimizer step (their gradients are averaged on the device; `nbatches` must be a multiple)"""
+    `accumulate`: batches per optimizer step (their gradients are averaged on the device; `nbatches` must be a multiple);
+    `stats_guard`: a StatsGuard resolved after every optimizer step, before the `ema` update"""
     if int(accumulate) != accumulate or int(accumulate) < 1:
         raise ValueError("accumulate must be an integer >= 1, got %r" % (accumulate,))
     accumulate = int(accumulate)
@@ -180,12 +201,16 @@ def train(stager, model, criterion, optimizer, nbatches, iiter=0, nclasses=3, pr
         stepped = acc is None or acc.add()                    # accumulate=K: True on every K-th batch, the mean is in place
         if stepped:
             optimizer.step()
+            if stats_guard is not None:
+                stats_guard.resolve()
             if ema is not None:
                 ema.update()
 
         rec.put(i, loss, pred_t, label_t)
         if stepped and getattr(optimizer, "guard", None) is not None:
             rec.put_guard(i, optimizer.guard)
+        if stepped and stats_guard is not None:
+            rec.put_stats(i, stats_guard)
         batch_time.update(time.time() - batchstart)           # host time: the device runs behind it between two read-backs
 
         if i % print_freq == 0:
