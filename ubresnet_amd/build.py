@@ -2,16 +2,17 @@
 whole-view inference), libubresnet_data.so (device-side batch preparation of the loader), libubresnet_aug.so (device-side
 augmentation of training batches), libubresnet_opt.so (the guarded flat optimizer step), libubresnet_weight.so (device-side
 pixel weights of the loss), libubresnet_group.so (flat optimizer steps with parameter groups), libubresnet_ema.so (the
-exponential moving average of the parameters), libubresnet_accum.so (gradient accumulation over the flat gradient buffer) and
-libubresnet_stats.so (the guard of the BatchNorm running statistics), the latter nine self-contained libraries of their own, with
-hipcc for gfx950, in-tree.
+exponential moving average of the parameters), libubresnet_accum.so (gradient accumulation over the flat gradient buffer),
+libubresnet_stats.so (the guard of the BatchNorm running statistics) and libubresnet_loss.so (the pixel-wise focal loss and its
+normalised means), the latter ten self-contained libraries of their own, with hipcc for gfx950, in-tree.
 
     python -m ubresnet_amd.build [--force]
 
 The shared libraries have NO PyTorch dependency: they are plain HIP behind include/ubresnet_hip.h,
-include/ubresnet_post.h, include/ubresnet_data.h, include/ubresnet_aug.h, include/ubresnet_opt.h, include/ubresnet_weight.h, include/ubresnet_group.h, include/ubresnet_ema.h, include/ubresnet_accum.h and include/ubresnet_stats.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
+include/ubresnet_post.h, include/ubresnet_data.h, include/ubresnet_aug.h, include/ubresnet_opt.h, include/ubresnet_weight.h, include/ubresnet_group.h, include/ubresnet_ema.h, include/ubresnet_accum.h, include/ubresnet_stats.h and include/ubresnet_loss.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
 
-build() makes the first nine, build_stats() the tenth by the same steps; the command line and the driver entry point call both.
+build() makes the first nine, build_stats() the tenth and build_loss() the eleventh by the same steps; the command line and the
+driver entry point call all three.
 """
 import os
 import subprocess
@@ -59,6 +60,10 @@ ACCUM_HEADERS = [os.path.join("..", "..", "include", "ubresnet_accum.h")]
 STATS_OUT = os.path.join(HERE, "libubresnet_stats.so")
 STATS_SOURCES = ["ubr_stats.hip"]
 STATS_HEADERS = ["ubr_stats_decide.h", os.path.join("..", "..", "include", "ubresnet_stats.h")]
+# the eleventh library: it links against none of the others either
+LOSS_OUT = os.path.join(HERE, "libubresnet_loss.so")
+LOSS_SOURCES = ["ubr_loss.hip"]
+LOSS_HEADERS = ["ubr_loss_term.h", os.path.join("..", "..", "include", "ubresnet_loss.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=off"]
@@ -96,6 +101,12 @@ def build_stats(force=False, verbose=True):
     """the tenth library by the same steps: one more (OUT, SOURCES, HEADERS) tuple; -> its path"""
     _build([(STATS_OUT, STATS_SOURCES, STATS_HEADERS)], force, verbose)
     return STATS_OUT
+
+
+def build_loss(force=False, verbose=True):
+    """the eleventh library by the same steps; -> its path"""
+    _build([(LOSS_OUT, LOSS_SOURCES, LOSS_HEADERS)], force, verbose)
+    return LOSS_OUT
 
 
 def _build(libs, force, verbose):
@@ -138,3 +149,4 @@ def _build(libs, force, verbose):
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_stats(force="--force" in sys.argv))
+    print(build_loss(force="--force" in sys.argv))
