@@ -10,7 +10,7 @@ from ubresnet_amd.augment import Augment
 from ubresnet_amd.pixel_weights import PixelWeights
 from ubresnet_amd.ema import ParamEMA
 from ubresnet_amd.bnguard import StatsGuard
-augment = Augment() if "--augment" in sys.argv else None      # python tools/soak.py [--augment] [--weights] [--ema] [--accumulate K] [--stats-guard] [--focal GAMMA] [--normalize MODE]
+augment = Augment() if "--augment" in sys.argv else None      # python tools/soak.py [--augment] [--weights] [--ema] [--accumulate K] [--stats-guard] [--focal GAMMA] [--normalize MODE] [--dice LAMBDA [--tversky A B]]
 weights = PixelWeights(num_classes=3, radius=1, gain=2.0) if "--weights" in sys.argv else None
 class NoWeight(object):                                        # --weights: the wire carries no weight entry, the device makes the weights
     def __init__(self, inner): self.inner = inner
@@ -23,6 +23,10 @@ if focal is not None or "--normalize" in sys.argv:
     from ubresnet_amd.training import PixelWiseFocalLoss
     crit = PixelWiseFocalLoss(gamma=focal if focal is not None else 0.0, normalize=normalize)
 else: crit = PixelWiseNLLLoss()
+if "--dice" in sys.argv:                                       # --dice LAMBDA [--tversky A B]: NLL (or the chosen focal) + LAMBDA * PixelWiseDiceLoss(alpha=A, beta=B), 0.5 0.5 without --tversky
+    from ubresnet_amd.training import PixelWiseDiceLoss, WeightedSumLoss
+    ab = [float(v) for v in sys.argv[sys.argv.index("--tversky") + 1:sys.argv.index("--tversky") + 3]] if "--tversky" in sys.argv else [0.5, 0.5]
+    crit = WeightedSumLoss([(1.0, crit), (float(sys.argv[sys.argv.index("--dice") + 1]), PixelWiseDiceLoss(alpha=ab[0], beta=ab[1]))])
 opt = FlatAdam(model, lr=1e-3, weight_decay=1e-4)
 ema = ParamEMA(opt, decay=0.999, warmup=10) if "--ema" in sys.argv else None   # --ema: averaged weights, updated after every step
 sg = StatsGuard(model, optimizer=opt) if "--stats-guard" in sys.argv else None   # --stats-guard: BatchNorm statistics committed or restored after every step (the optimizer here is unguarded: the scan alone decides)
@@ -36,5 +40,6 @@ with BatchStager(ld, 16, 512, 512, tag="train", augment=augment, weights=weights
         print(ep, round(loss, 4), "mem GB %.2f" % (torch.cuda.max_memory_allocated() / 2**30), "acc[1] %.1f" % acc, st.stage_times(), flush=True)
 torch.cuda.synchronize(); print("%d steps (%d batches) in %.1f s; finite params: %s" % (opt.steps, 300 * accumulate, time.perf_counter() - t0, all(torch.isfinite(p).all().item() for p in model.parameters())))
 if ema is not None: print("ema updates %d held %d; finite average: %s" % (ema.updates, ema.held, bool(torch.isfinite(ema.shadow).all())))
-if hasattr(crit, "read"): print("criterion: gamma %g, normalize %s, last batch %s" % (crit.gamma, crit.normalize, crit.read()))
+if hasattr(crit, "gamma"): print("criterion: gamma %g, normalize %s, last batch %s" % (crit.gamma, crit.normalize, crit.read()))
+elif hasattr(crit, "read"): print("criterion: weights %s, last batch %s" % (crit.weights, crit.read()))
 if sg is not None: print("stats guard: %s; finite statistics: %s" % (sg.read(), all(torch.isfinite(b).all().item() for b in model.buffers() if b.is_floating_point())))

@@ -3,16 +3,17 @@ whole-view inference), libubresnet_data.so (device-side batch preparation of the
 augmentation of training batches), libubresnet_opt.so (the guarded flat optimizer step), libubresnet_weight.so (device-side
 pixel weights of the loss), libubresnet_group.so (flat optimizer steps with parameter groups), libubresnet_ema.so (the
 exponential moving average of the parameters), libubresnet_accum.so (gradient accumulation over the flat gradient buffer),
-libubresnet_stats.so (the guard of the BatchNorm running statistics) and libubresnet_loss.so (the pixel-wise focal loss and its
-normalised means), the latter ten self-contained libraries of their own, with hipcc for gfx950, in-tree.
+libubresnet_stats.so (the guard of the BatchNorm running statistics), libubresnet_loss.so (the pixel-wise focal loss and its
+normalised means) and libubresnet_dice.so (the soft Dice / Tversky region loss), the latter eleven self-contained libraries of
+their own, with hipcc for gfx950, in-tree.
 
     python -m ubresnet_amd.build [--force]
 
 The shared libraries have NO PyTorch dependency: they are plain HIP behind include/ubresnet_hip.h,
-include/ubresnet_post.h, include/ubresnet_data.h, include/ubresnet_aug.h, include/ubresnet_opt.h, include/ubresnet_weight.h, include/ubresnet_group.h, include/ubresnet_ema.h, include/ubresnet_accum.h, include/ubresnet_stats.h and include/ubresnet_loss.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
+include/ubresnet_post.h, include/ubresnet_data.h, include/ubresnet_aug.h, include/ubresnet_opt.h, include/ubresnet_weight.h, include/ubresnet_group.h, include/ubresnet_ema.h, include/ubresnet_accum.h, include/ubresnet_stats.h, include/ubresnet_loss.h and include/ubresnet_dice.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
 
-build() makes the first nine, build_stats() the tenth and build_loss() the eleventh by the same steps; the command line and the
-driver entry point call all three.
+build() makes the first nine, build_stats() the tenth, build_loss() the eleventh and build_dice() the twelfth by the same steps;
+the command line and the driver entry point call all four.
 """
 import os
 import subprocess
@@ -64,6 +65,10 @@ STATS_HEADERS = ["ubr_stats_decide.h", os.path.join("..", "..", "include", "ubre
 LOSS_OUT = os.path.join(HERE, "libubresnet_loss.so")
 LOSS_SOURCES = ["ubr_loss.hip"]
 LOSS_HEADERS = ["ubr_loss_term.h", os.path.join("..", "..", "include", "ubresnet_loss.h")]
+# the twelfth library: it links against none of the others either
+DICE_OUT = os.path.join(HERE, "libubresnet_dice.so")
+DICE_SOURCES = ["ubr_dice.hip"]
+DICE_HEADERS = ["ubr_dice_term.h", os.path.join("..", "..", "include", "ubresnet_dice.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=off"]
@@ -109,6 +114,12 @@ def build_loss(force=False, verbose=True):
     return LOSS_OUT
 
 
+def build_dice(force=False, verbose=True):
+    """the twelfth library by the same steps; -> its path"""
+    _build([(DICE_OUT, DICE_SOURCES, DICE_HEADERS)], force, verbose)
+    return DICE_OUT
+
+
 def _build(libs, force, verbose):
     jobs, links = [], []
     for out, sources, headers in libs:
@@ -150,3 +161,4 @@ if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_stats(force="--force" in sys.argv))
     print(build_loss(force="--force" in sys.argv))
+    print(build_dice(force="--force" in sys.argv))

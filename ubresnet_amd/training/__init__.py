@@ -7,4 +7,7 @@ def __getattr__(name):
     if name == "PixelWiseFocalLoss":
         from .pixelwise_focalloss import PixelWiseFocalLoss
         return PixelWiseFocalLoss
+    if name in ("PixelWiseDiceLoss", "WeightedSumLoss"):
+        from . import pixelwise_diceloss
+        return getattr(pixelwise_diceloss, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
