@@ -4,16 +4,16 @@ augmentation of training batches), libubresnet_opt.so (the guarded flat optimize
 pixel weights of the loss), libubresnet_group.so (flat optimizer steps with parameter groups), libubresnet_ema.so (the
 exponential moving average of the parameters), libubresnet_accum.so (gradient accumulation over the flat gradient buffer),
 libubresnet_stats.so (the guard of the BatchNorm running statistics), libubresnet_loss.so (the pixel-wise focal loss and its
-normalised means) and libubresnet_dice.so (the soft Dice / Tversky region loss), the latter eleven self-contained libraries of
-their own, with hipcc for gfx950, in-tree.
+normalised means), libubresnet_dice.so (the soft Dice / Tversky region loss) and libubresnet_tta.so (flip test-time augmentation
+of inference), the latter twelve self-contained libraries of their own, with hipcc for gfx950, in-tree.
 
     python -m ubresnet_amd.build [--force]
 
 The shared libraries have NO PyTorch dependency: they are plain HIP behind include/ubresnet_hip.h,
-include/ubresnet_post.h, include/ubresnet_data.h, include/ubresnet_aug.h, include/ubresnet_opt.h, include/ubresnet_weight.h, include/ubresnet_group.h, include/ubresnet_ema.h, include/ubresnet_accum.h, include/ubresnet_stats.h, include/ubresnet_loss.h and include/ubresnet_dice.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
+include/ubresnet_post.h, include/ubresnet_data.h, include/ubresnet_aug.h, include/ubresnet_opt.h, include/ubresnet_weight.h, include/ubresnet_group.h, include/ubresnet_ema.h, include/ubresnet_accum.h, include/ubresnet_stats.h, include/ubresnet_loss.h, include/ubresnet_dice.h and include/ubresnet_tta.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
 
-build() makes the first nine, build_stats() the tenth, build_loss() the eleventh and build_dice() the twelfth by the same steps;
-the command line and the driver entry point call all four.
+build() makes the first nine, build_stats() the tenth, build_loss() the eleventh, build_dice() the twelfth and build_tta() the
+thirteenth by the same steps; the command line and the driver entry point call all five.
 """
 import os
 import subprocess
@@ -69,6 +69,10 @@ LOSS_HEADERS = ["ubr_loss_term.h", os.path.join("..", "..", "include", "ubresnet
 DICE_OUT = os.path.join(HERE, "libubresnet_dice.so")
 DICE_SOURCES = ["ubr_dice.hip"]
 DICE_HEADERS = ["ubr_dice_term.h", os.path.join("..", "..", "include", "ubresnet_dice.h")]
+# the thirteenth library: it links against none of the others either
+TTA_OUT = os.path.join(HERE, "libubresnet_tta.so")
+TTA_SOURCES = ["ubr_tta.hip"]
+TTA_HEADERS = [os.path.join("..", "..", "include", "ubresnet_tta.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=off"]
@@ -120,6 +124,12 @@ def build_dice(force=False, verbose=True):
     return DICE_OUT
 
 
+def build_tta(force=False, verbose=True):
+    """the thirteenth library by the same steps; -> its path"""
+    _build([(TTA_OUT, TTA_SOURCES, TTA_HEADERS)], force, verbose)
+    return TTA_OUT
+
+
 def _build(libs, force, verbose):
     jobs, links = [], []
     for out, sources, headers in libs:
@@ -162,3 +172,4 @@ if __name__ == "__main__":
     print(build_stats(force="--force" in sys.argv))
     print(build_loss(force="--force" in sys.argv))
     print(build_dice(force="--force" in sys.argv))
+    print(build_tta(force="--force" in sys.argv))

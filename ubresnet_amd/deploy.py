@@ -16,6 +16,9 @@ Mirrors the inference side of the reference:
   * event products (``output="products"``): what the downstream chain keeps of the dense scores -- a class per pixel, its
     probability and per-plane class counts, only where the wire signal is above threshold (tf/compare_caffe_to_tf.py:17,81-89,
     ADC_THRESHOLD = 10.0) -- written by one fused kernel in place of the stitch (include/ubresnet_post.h).
+  * flip test-time augmentation (``tta=("rows", "cols", "both")``): training flips every axis with probability 1/2 (``Augment``),
+    so the network is evaluated on the flipped views of every batch as well and the class probabilities are averaged
+    (include/ubresnet_tta.h) before the unchanged stitch or event products.
 """
 from __future__ import annotations
 
@@ -26,6 +29,7 @@ import torch
 
 from . import _lib as L
 from . import _post as PL
+from . import _tta as TL
 
 
 class Products(NamedTuple):
@@ -111,14 +115,58 @@ def save_checkpoint(state: dict, is_best: bool, p: int, filename: str = "checkpo
     return filename
 
 
+def _merged_views(model, x, flips, xin, merged):
+    """the flip views of one batch: `x` [m,C,H,W] is written flipped into `xin` (the identity view is read where it lies), the
+    model runs on it and its float32 log-probabilities are merged, un-flipped, into `merged` [m,classes,H,W]"""
+    m, cin, H, W = x.shape
+    K = len(flips)
+    for k, flip in enumerate(flips):
+        if flip:
+            TL.flip_planes(x.data_ptr(), xin.data_ptr(), m * cin, H, W, flip, L.stream_ptr())
+        logp = model(xin[:m] if flip else x).contiguous()
+        if logp.dtype != torch.float32 or tuple(logp.shape) != tuple(merged.shape):
+            raise RuntimeError("segment_crops: the model must return float32 log-probabilities %s (got %s %s)"
+                               % (tuple(merged.shape), logp.dtype, tuple(logp.shape)))
+        TL.merge_view(logp.data_ptr(), merged.data_ptr(), merged.shape[0] * merged.shape[1], H, W, flip, k, K, L.stream_ptr())
+
+
 @torch.no_grad()
 def segment_crops(model, adc: torch.Tensor, batch: int = 4, output: str = "scores", adc_threshold: Optional[float] = 10.0,
-                  fill_label: int = 255):
+                  fill_label: int = 255, tta=None):
     """eval forward over pre-cropped images [n,C,H,W] in batches (deploy/run_ubresnet_precropped.py:115-182).
     output="products": Products of [n,H,W] / [n,H,W] / [n,classes] instead of the scores; every image is one whole-image tile
-    of ubp_stitch_products and is lit where any of its channels is above `adc_threshold` (None: everywhere)."""
+    of ubp_stitch_products and is lit where any of its channels is above `adc_threshold` (None: everywhere).
+    tta: None / () or a tuple drawn from "rows", "cols", "both": every batch also runs flipped that way and the scores are the log
+    of the mean probability over the views, the identity first (needs a CUDA float32 input; the lit test reads the unflipped
+    `adc`)."""
     _check_output(output)
+    flips = TL.parse_views(tta)
     model.eval()
+    if flips:
+        L.require_cuda(adc, "adc")
+        if adc.dtype != torch.float32 or adc.dim() != 4:
+            raise RuntimeError("segment_crops: expected float32 [n,C,H,W], got %s %s" % (adc.dtype, tuple(adc.shape)))
+        adc = adc.contiguous()
+        n, cin, H, W = adc.shape
+        nclass = model.conv11.out_channels
+        xin = torch.empty((min(batch, n), cin, H, W), dtype=torch.float32, device=adc.device)
+        if output == "scores":
+            out = torch.empty((n, nclass, H, W), dtype=torch.float32, device=adc.device)
+            for i in range(0, n, batch):
+                _merged_views(model, adc[i:i + batch], flips, xin, out[i:i + batch])
+            return out
+        prod = Products(torch.empty((n, H, W), dtype=torch.uint8, device=adc.device),
+                        torch.empty((n, H, W), dtype=torch.float16, device=adc.device),
+                        torch.zeros((n, nclass), dtype=torch.int64, device=adc.device))
+        merged = torch.empty((min(batch, n), nclass, H, W), dtype=torch.float32, device=adc.device)
+        for i in range(0, n, batch):
+            nb = min(batch, n - i)
+            _merged_views(model, adc[i:i + nb], flips, xin, merged[:nb])
+            for j in range(0, nb, PL.MAX_TILES):
+                m = min(PL.MAX_TILES, nb - j)
+                tiles = [(i + j + q, 0, 0, 0, H, 0, W) for q in range(m)]
+                _stitch_products(merged[j:j + m], nclass, H, W, tiles, adc, cin, adc_threshold, fill_label, prod, n, H, W)
+        return prod
     if output == "scores":
         outs = []
         for i in range(0, adc.shape[0], batch):
@@ -201,12 +249,18 @@ class WholeViewSegmenter:
     own.  A model that takes `planes` channels (ASPP_ResNet, the three planes stacked as channels) sees one stacked tile per
     position, and the result is one class-score map per event, [C,rows,cols] (products: [rows,cols] and [C]; a pixel is lit if
     any plane is).
+
+    tta=("rows", "cols", "both") or any part of it: flip test-time augmentation.  Every chunk of tiles is cropped once, runs
+    through the same captured graph once per view (the identity first, then the named flips in the order given) and the views'
+    log-probabilities are merged, un-flipped, into the log of their mean probability (include/ubresnet_tta.h) before the unchanged
+    stitch or event products.  None / (): off, today's path call for call.
     """
 
     def __init__(self, model, rows: int, cols: int, planes: int = 3, tile=(512, 832), batch: int = 10,
                  dtype: torch.dtype = torch.float16, use_graph: bool = True, output: str = "scores",
-                 adc_threshold: Optional[float] = 10.0, fill_label: int = 255):
+                 adc_threshold: Optional[float] = 10.0, fill_label: int = 255, tta=None):
         _check_output(output)
+        self._flips = TL.parse_views(tta)                   # () or (0, flip mask of every named view)
         self.output, self.adc_threshold, self.fill_label = output, adc_threshold, fill_label
         self.model, self.rows, self.cols, self.planes = model, rows, cols, planes
         self.th, self.tw = tile
@@ -229,6 +283,8 @@ class WholeViewSegmenter:
         self._static_in = None
         self._static_out = None
         self._captured_sig = None
+        self._tta_side = None                               # the cropped chunk, unflipped; lives and dies with _static_in
+        self._tta_merged = None                             # the running merge of the views' log-probabilities
 
     @property
     def tiles_per_event(self):
@@ -254,11 +310,14 @@ class WholeViewSegmenter:
         # load_state_dict(assign=True)) the replay would read freed memory -- capture again
         sig = self._signature()
         if self._static_in is not None and sig != self._captured_sig:
-            self._graph = self._static_in = self._static_out = None
+            self._graph = self._static_in = self._static_out = self._tta_side = self._tta_merged = None
         if self._static_in is not None:
             return
         self._captured_sig = sig
         self._static_in = torch.zeros((self.batch, self.cin, self.th, self.tw), dtype=torch.float32, device=device)
+        if self._flips:
+            self._tta_side = torch.zeros_like(self._static_in)
+            self._tta_merged = torch.empty((self.batch, self.nclass, self.th, self.tw), dtype=torch.float32, device=device)
         self.model.eval()
         with torch.no_grad():
             self._forward_batch(self._static_in)            # warm-up: packs weights, raises LDS limits, fills allocator
@@ -293,12 +352,20 @@ class WholeViewSegmenter:
             cdesc = self._desc(stacked_crop_desc(chunk, self.planes)) if self.stacked else desc
             st = L.stream_ptr()
             L.check(lib.ubr_crop_tiles(view.data_ptr(), self.planes, self.rows, self.cols, cdesc, n * self.cin, self.th, self.tw,
-                                       self._static_in.data_ptr(), st), "crop_tiles")
-            if self._graph is not None:
-                self._graph.replay()
-                scores = self._static_out
-            else:
-                scores = self._forward_batch(self._static_in)
+                                       (self._tta_side if self._flips else self._static_in).data_ptr(), st), "crop_tiles")
+            for k, flip in enumerate(self._flips or (None,)):
+                if flip is not None:
+                    TL.flip_planes(self._tta_side.data_ptr(), self._static_in.data_ptr(), n * self.cin, self.th, self.tw, flip, st)
+                if self._graph is not None:
+                    self._graph.replay()
+                    scores = self._static_out
+                else:
+                    scores = self._forward_batch(self._static_in)
+                if flip is not None:
+                    TL.merge_view(scores.data_ptr(), self._tta_merged.data_ptr(), n * self.nclass, self.th, self.tw, flip, k,
+                                  len(self._flips), L.stream_ptr())
+            if self._flips:
+                scores = self._tta_merged
             if products:
                 _stitch_products(scores, self.nclass, self.th, self.tw, chunk, view, self.planes if self.stacked else 1,
                                  self.adc_threshold, self.fill_label, out, oplanes, self.rows, self.cols)
