@@ -10,8 +10,10 @@ from ubresnet_amd.augment import Augment
 from ubresnet_amd.pixel_weights import PixelWeights
 from ubresnet_amd.ema import ParamEMA
 from ubresnet_amd.bnguard import StatsGuard
-augment = Augment() if "--augment" in sys.argv else None      # python tools/soak.py [--augment] [--weights] [--ema] [--accumulate K] [--stats-guard] [--focal GAMMA] [--normalize MODE] [--dice LAMBDA [--tversky A B]]
+augment = Augment() if "--augment" in sys.argv else None      # python tools/soak.py [--augment] [--weights] [--detector] [--ema] [--accumulate K] [--stats-guard] [--focal GAMMA] [--normalize MODE] [--dice LAMBDA [--tversky A B]]
 weights = PixelWeights(num_classes=3, radius=1, gain=2.0) if "--weights" in sys.argv else None
+from ubresnet_amd.detector import DetectorEffects
+detector = DetectorEffects(dead_runs=(0, 3), run_len=(1, 32), gain=(0.9, 1.1), noise_sigma=1.5, dead_label=0, dead_weight=0.0, seed=1) if "--detector" in sys.argv else None   # --detector: up to three runs of 1..32 dead wires per image, a gain in [0.9, 1.1], noise of sigma 1.5 on lit pixels; a dead pixel is background of weight 0
 class NoWeight(object):                                        # --weights: the wire carries no weight entry, the device makes the weights
     def __init__(self, inner): self.inner = inner
     def __getitem__(self, idx): return {k: v for k, v in self.inner[idx].items() if not k.startswith("weight_")}
@@ -34,7 +36,7 @@ accumulate = int(sys.argv[sys.argv.index("--accumulate") + 1]) if "--accumulate"
 ld = synthetic.SyntheticLArCVDataset(height=512, width=512, tag="train", nentries=64, cache=64); ld.start(16)
 if weights is not None: ld = NoWeight(ld)
 t0 = time.perf_counter()
-with BatchStager(ld, 16, 512, 512, tag="train", augment=augment, weights=weights) as st:
+with BatchStager(ld, 16, 512, 512, tag="train", augment=augment, weights=weights, detector=detector) as st:
     for ep in range(6):
         loss, acc = epoch.train(st, model, crit, opt, 50 * accumulate, iiter=ep, print_freq=25 * accumulate, accumulate=accumulate, stats_guard=sg, ema=ema)
         print(ep, round(loss, 4), "mem GB %.2f" % (torch.cuda.max_memory_allocated() / 2**30), "acc[1] %.1f" % acc, st.stage_times(), flush=True)

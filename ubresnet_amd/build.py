@@ -4,16 +4,17 @@ augmentation of training batches), libubresnet_opt.so (the guarded flat optimize
 pixel weights of the loss), libubresnet_group.so (flat optimizer steps with parameter groups), libubresnet_ema.so (the
 exponential moving average of the parameters), libubresnet_accum.so (gradient accumulation over the flat gradient buffer),
 libubresnet_stats.so (the guard of the BatchNorm running statistics), libubresnet_loss.so (the pixel-wise focal loss and its
-normalised means), libubresnet_dice.so (the soft Dice / Tversky region loss) and libubresnet_tta.so (flip test-time augmentation
-of inference), the latter twelve self-contained libraries of their own, with hipcc for gfx950, in-tree.
+normalised means), libubresnet_dice.so (the soft Dice / Tversky region loss), libubresnet_tta.so (flip test-time augmentation
+of inference) and libubresnet_det.so (detector effects on training batches), the latter thirteen self-contained libraries of
+their own, with hipcc for gfx950, in-tree.
 
     python -m ubresnet_amd.build [--force]
 
 The shared libraries have NO PyTorch dependency: they are plain HIP behind include/ubresnet_hip.h,
-include/ubresnet_post.h, include/ubresnet_data.h, include/ubresnet_aug.h, include/ubresnet_opt.h, include/ubresnet_weight.h, include/ubresnet_group.h, include/ubresnet_ema.h, include/ubresnet_accum.h, include/ubresnet_stats.h, include/ubresnet_loss.h, include/ubresnet_dice.h and include/ubresnet_tta.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
+include/ubresnet_post.h, include/ubresnet_data.h, include/ubresnet_aug.h, include/ubresnet_opt.h, include/ubresnet_weight.h, include/ubresnet_group.h, include/ubresnet_ema.h, include/ubresnet_accum.h, include/ubresnet_stats.h, include/ubresnet_loss.h, include/ubresnet_dice.h, include/ubresnet_tta.h and include/ubresnet_det.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
 
-build() makes the first nine, build_stats() the tenth, build_loss() the eleventh, build_dice() the twelfth and build_tta() the
-thirteenth by the same steps; the command line and the driver entry point call all five.
+build() makes the first nine, build_stats() the tenth, build_loss() the eleventh, build_dice() the twelfth, build_tta() the
+thirteenth and build_det() the fourteenth by the same steps; the command line and the driver entry point call all six.
 """
 import os
 import subprocess
@@ -73,6 +74,10 @@ DICE_HEADERS = ["ubr_dice_term.h", os.path.join("..", "..", "include", "ubresnet
 TTA_OUT = os.path.join(HERE, "libubresnet_tta.so")
 TTA_SOURCES = ["ubr_tta.hip"]
 TTA_HEADERS = [os.path.join("..", "..", "include", "ubresnet_tta.h")]
+# the fourteenth library: it links against none of the others either
+DET_OUT = os.path.join(HERE, "libubresnet_det.so")
+DET_SOURCES = ["ubr_det.hip"]
+DET_HEADERS = ["ubr_det_rule.h", os.path.join("..", "..", "include", "ubresnet_det.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=off"]
@@ -130,6 +135,12 @@ def build_tta(force=False, verbose=True):
     return TTA_OUT
 
 
+def build_det(force=False, verbose=True):
+    """the fourteenth library by the same steps; -> its path"""
+    _build([(DET_OUT, DET_SOURCES, DET_HEADERS)], force, verbose)
+    return DET_OUT
+
+
 def _build(libs, force, verbose):
     jobs, links = [], []
     for out, sources, headers in libs:
@@ -173,3 +184,4 @@ if __name__ == "__main__":
     print(build_loss(force="--force" in sys.argv))
     print(build_dice(force="--force" in sys.argv))
     print(build_tta(force="--force" in sys.argv))
+    print(build_det(force="--force" in sys.argv))

@@ -39,6 +39,13 @@ without it), ``"always"`` for every batch; a wire weight that is replaced is not
 then the ``[B,16]`` int64 device tensor of per-image class counts of the batch ``next()`` returned last (None where its weights
 came off the wire).  ``weights=None`` changes nothing.
 
+``detector=DetectorEffects(...)`` (ubresnet_amd/detector.py) puts dead wires, a gain per plane and noise into the prepared
+batch, in place: the producer that fills a slot also writes ``detector.table(seq, B, P, W)`` into a small pinned array of the
+slot; the consumer copies it to the slot's device table (one more small non-blocking copy on the copy stream, no allocation) and launches ``ubx_apply``
+(libubresnet_det.so) behind ``ubd_prep_batch`` / ``uba_augment_batch`` and BEFORE ``ubw_pixel_weights``, so that the weights
+balance the labels as they finally are.  Table and noise depend on ``(detector.seed, seq)`` alone.  ``detector=None`` changes
+nothing.
+
 ``device=None`` runs the host half alone (``pin=False`` then needs no GPU at all): ``next()`` returns a ``HostBatch`` of numpy
 views of the slot, which stay valid until the following ``next()``, ``skip()`` or ``close()`` releases the slot.  Nothing is
 augmented there: ``stager.augment.params(batch.seq, B)`` gives the caller the batch's parameters.
@@ -57,9 +64,9 @@ HostBatch = collections.namedtuple("HostBatch", ["seq", "image", "label_wire", "
 
 
 class _Slot(object):
-    __slots__ = ("index", "tensor", "array", "event", "has_weight")
+    __slots__ = ("index", "tensor", "array", "event", "has_weight", "table_tensor", "table", "table_dev")
 
-    def __init__(self, index, nfloats, pin):
+    def __init__(self, index, nfloats, pin, ntable=0):
         self.index = index
         self.tensor = None
         if pin:
@@ -68,13 +75,21 @@ class _Slot(object):
             self.array = self.tensor.numpy()
         else:
             self.array = np.empty(nfloats, dtype=np.float32)
+        self.table_tensor = self.table = None          # the detector's table of the batch in this slot (int32 / its uint32 view)
+        self.table_dev = None                          # its device copy: written and read on the copy stream only
+        if ntable:
+            import torch
+            self.table_tensor = torch.empty(ntable, dtype=torch.int32)
+            if pin:
+                self.table_tensor = self.table_tensor.pin_memory()
+            self.table = self.table_tensor.numpy().view(np.uint32)
         self.event = None              # recorded behind the last host-to-device copy that read this slot
         self.has_weight = True
 
 
 class BatchStager(object):
     def __init__(self, loader, batchsize, height, width, planes=1, tag="train", device="cuda", threads=2, slots=None,
-                 label_offset=0, adc_threshold=None, timeout=60.0, pin=True, augment=None, weights=None):
+                 label_offset=0, adc_threshold=None, timeout=60.0, pin=True, augment=None, weights=None, detector=None):
         if threads < 1:
             raise ValueError("BatchStager: threads must be >= 1")
         self.loader, self.tag = loader, tag
@@ -86,7 +101,10 @@ class BatchStager(object):
         self.timeout = float(timeout)
         self.augment = augment
         self.weights = weights
+        self.detector = detector
         self.counts = None
+        if detector is not None and device is None:
+            raise ValueError("BatchStager: detector effects are made on the device; device=None (the host half alone) takes none")
         if weights is not None and device is None:
             raise ValueError("BatchStager: weights are made on the device; device=None (the host half alone) takes none")
         nslots = int(slots) if slots is not None else int(threads) + 1
@@ -113,8 +131,15 @@ class BatchStager(object):
                 from . import _weight
                 self._weight = _weight
                 _weight.lib()
+            if detector is not None:
+                from . import _det
+                _det.lib()
             self.stream = torch.cuda.Stream(device=self.device)
-        self._slots = [_Slot(i, (p + 2) * self.npix, pin) for i in range(nslots)]
+        ntable = b * p * detector.row_words(w) if detector is not None else 0
+        self._slots = [_Slot(i, (p + 2) * self.npix, pin, ntable) for i in range(nslots)]
+        if ntable:
+            for slot in self._slots:
+                slot.table_dev = self._torch.empty(ntable, dtype=self._torch.int32, device=self.device)
         self._free = collections.deque(self._slots)
         self._ready = {}                                   # sequence number -> filled slot, or the exception that batch hit
         self._cond = threading.Condition()                 # guards _free, _ready, _stop, the stage times
@@ -172,6 +197,8 @@ class BatchStager(object):
                 if not self._wait_copied(slot):
                     return
                 self._fill(slot, data)
+                if slot.table is not None:
+                    slot.table[:] = self.detector.table(seq, *self.shape[:2], self.shape[3]).reshape(-1)
                 self._note("fill", time.perf_counter() - t0)
                 result = slot
             except BaseException as e:                     # delivered to the next() that asks for this batch
@@ -268,6 +295,8 @@ class BatchStager(object):
                                   threshold=self.adc_threshold,
                                   weight_fill=None if slot.has_weight or make else base + 4 * (p + 1) * n,
                                   stream=self.stream.cuda_stream)
+            if self.detector is not None:
+                self._launch_detector(slot, self._want - 1, base, label.data_ptr(), base + 4 * (p + 1) * n)
             counts = self._launch_weights(label, base + 4 * (p + 1) * n) if make else None
             ev = torch.cuda.Event()
             ev.record(self.stream)
@@ -295,6 +324,8 @@ class BatchStager(object):
                                     adc.data_ptr(), label.data_ptr(), weight.data_ptr(), self.shape, aug.pad,
                                     aug.params(seq, b), label_offset=self.label_offset, threshold=self.adc_threshold,
                                     pad_label=aug.pad_label, pad_weight=aug.pad_weight, stream=self.stream.cuda_stream)
+            if self.detector is not None:
+                self._launch_detector(slot, seq, adc.data_ptr(), label.data_ptr(), weight.data_ptr())
             counts = self._launch_weights(label, weight.data_ptr()) if make else None
             ev = torch.cuda.Event()
             ev.record(self.stream)
@@ -305,6 +336,13 @@ class BatchStager(object):
 
     def _makes_weights(self, slot):
         return self.weights is not None and (self.weights.when == "always" or not slot.has_weight)
+
+    def _launch_detector(self, slot, seq, image_ptr, label_ptr, weight_ptr):
+        """the slot's table to its device copy and ubx_apply, both on the copy stream (the caller has made it current).  The
+        device copy belongs to the slot and is written and read on the copy stream only, so the copy for the slot's next batch
+        is ordered behind this launch."""
+        slot.table_dev.copy_(slot.table_tensor, non_blocking=slot.table_tensor.is_pinned())
+        self.detector.launch(image_ptr, label_ptr, weight_ptr, self.shape, slot.table_dev.data_ptr(), seq, stream=self.stream.cuda_stream)
 
     def _launch_weights(self, label, weight_ptr):
         """ubw_pixel_weights on the copy stream (the caller has made it current): `label` -> the weights at `weight_ptr`;
