@@ -1,8 +1,6 @@
 """The gradient-accumulation library without a GPU: libubresnet_accum.so's header is C99; header, binding, reference and library
-agree on the entry points and the geometry; the library stands alone; build.py and the entry point cover it and source_hash()
-does not; every argument refusal returns UBC_EINVAL with a message before any launch; the numpy reference against an fp64 sum;
-GradAccumulator's and epoch.train's refusals that need no device."""
-import ast
+agree on the entry points and the geometry; every argument refusal returns UBC_EINVAL with a message before any launch; the numpy
+reference against an fp64 sum; GradAccumulator's and epoch.train's refusals that need no device."""
 import os
 import re
 import subprocess
@@ -19,22 +17,12 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "ubresnet_accum.h")
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import kernel_symbols  # noqa: E402
+from cpu_helpers import cc, need_lib  # noqa: E402
 from ubresnet_amd import _accum as A  # noqa: E402
 from ubresnet_amd import build as B  # noqa: E402
 
-LIB = B.ACCUM_OUT
-LLVM = "/opt/rocm/lib/llvm/bin"
+LIB = B.LIBS["accum"].out
 f32 = np.float32
-
-
-def _need_lib():
-    # (the library is a build product: __graft_entry__.build() makes it; a tree that was never built has nothing to inspect)
-    assert os.path.exists(LIB), "libubresnet_accum.so is not built (python -m ubresnet_amd.build)"
-
-
-def _cc():
-    cc = os.path.join(LLVM, "clang")
-    return cc if os.path.exists(cc) else "cc"
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -50,7 +38,7 @@ def test_header_compiles_as_c99(tmp_path):
                      '  const char* (*e)(void) = ubc_last_error;\n'
                      '  int (*v)(void) = ubc_version;\n'
                      '  return s == 0 || a == 0 || f == 0 || e == 0 || v == 0 || UBC_OK != 0 || UBC_EINVAL != -1 || UBC_ELAUNCH != -2;\n}\n')
-    r = subprocess.run([_cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(proto)],
+    r = subprocess.run([cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(proto)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
 
@@ -59,7 +47,7 @@ def test_header_binding_reference_and_library_agree():
     raw = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
     declared = set(re.findall(r"\b(ubc_[a-z_0-9]+)\s*\(", text))
-    _need_lib()
+    need_lib(LIB)
     assert declared == set(A.SYMBOLS) and len(A.SYMBOLS) == len(set(A.SYMBOLS)) == 5
     geometry = {k: int(v) for k, v in re.findall(r"#define\s+UBC_(BLOCK|UNROLL|MAX_GRID)\s+(\d+)", text)}
     assert geometry == dict(BLOCK=A.BLOCK, UNROLL=A.UNROLL, MAX_GRID=A.MAX_GRID)
@@ -67,19 +55,6 @@ def test_header_binding_reference_and_library_agree():
     # the arithmetic rules are stated in the header
     for phrase in ("rounded to nearest even", "contracted", "Subnormal", "NaN", "payload"):
         assert phrase in raw, phrase
-    lib = A.lib()
-    assert all(hasattr(lib, s) for s in A.SYMBOLS)
-    assert lib.ubc_version() == 1
-    # the exports with the library's prefix are exactly the declared ones, and none has another library's prefix
-    syms = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--dyn-syms", "-W", LIB], capture_output=True, text=True, check=True).stdout
-    defined = [l.split()[-1] for l in syms.split("\n") if len(l.split()) == 8 and l.split()[6] != "UND"]
-    assert set(n for n in defined if n.startswith("ubc_")) == set(A.SYMBOLS)
-    assert not [n for n in defined if re.match(r"ub[rpdaowge]_", n)], "a symbol of another library"
-    # the ninth library stands alone: it links against none of the others
-    dyn = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "-d", LIB], capture_output=True, text=True, check=True).stdout
-    for other in ("libubresnet_hip", "libubresnet_post", "libubresnet_data", "libubresnet_aug", "libubresnet_opt", "libubresnet_weight",
-                  "libubresnet_group", "libubresnet_ema"):
-        assert other not in dyn
     # three kernels
     assert sorted(k.split("(")[0].split("::")[-1] for k in kernel_symbols.kernels(LIB)) == ["add_kernel", "finish_kernel", "set_kernel"]
 
@@ -90,63 +65,6 @@ def test_the_sizes_cover_the_paths_of_the_launch():
     assert sizes == [4, 4 * (t - 1), 4 * t, 4 * (t + 1), 4 * (R.MAX_GRID * t + 1)]
     assert [R.grid(n) for n in sizes] == [1, 1, 1, 2, R.MAX_GRID]
     assert sizes[-1] // 4 == R.MAX_GRID * R.BLOCK * R.UNROLL + 1 and 15 << 20 < 4 * sizes[-1] < 17 << 20      # about 16 MB per buffer
-
-
-def test_build_covers_the_ninth_library_and_the_hash_only_the_network():
-    assert B.ACCUM_SOURCES == ["ubr_accum.hip"]
-    others = B.SOURCES + B.POST_SOURCES + B.DATA_SOURCES + B.AUG_SOURCES + B.OPT_SOURCES + B.WEIGHT_SOURCES + B.GROUP_SOURCES + B.EMA_SOURCES
-    assert "ubr_accum.hip" not in others
-    assert os.path.basename(B.ACCUM_OUT) == "libubresnet_accum.so"
-    assert not any("accum" in h for h in B.HEADERS + B.POST_HEADERS + B.DATA_HEADERS + B.AUG_HEADERS + B.OPT_HEADERS + B.WEIGHT_HEADERS
-                   + B.GROUP_HEADERS + B.EMA_HEADERS)
-    assert any("ubresnet_accum.h" in h for h in B.ACCUM_HEADERS)
-    assert "-ffp-contract=off" in B.FLAGS and "--offload-arch=gfx950" in B.FLAGS
-    lines = []
-    old = subprocess.run
-
-    def fake(cmd, **kw):
-        lines.append(cmd)
-        return old(["true"], **kw)
-    subprocess.run = fake
-    try:
-        B.build(force=True, verbose=False)
-    finally:
-        subprocess.run = old
-    assert sum(1 for c in lines if "-shared" in c) == 9, "nine libraries"
-    mine = [c for c in lines if any("ubr_accum" in a or "libubresnet_accum" in a for a in c)]
-    assert len(mine) == 2, mine
-    compile_, link = mine
-    assert all(f in compile_ for f in B.FLAGS), "the accumulation library is compiled with the shared FLAGS"
-    assert link[-1].endswith("ubr_accum.o") and B.ACCUM_OUT in link and sum(a.endswith(".o") for a in link) == 1, "links nothing else"
-    entry = open(os.path.join(REPO, "__graft_entry__.py")).read()
-    assert "_accum.SYMBOLS" in entry and "ubc_version" in entry
-    import hashlib
-    h = hashlib.sha256()
-    for f in sorted(B.SOURCES) + sorted(B.HEADERS):
-        with open(os.path.join(B.CSRC, f), "rb") as fh:
-            h.update(f.encode() + b"\0" + fh.read())
-    assert B.source_hash() == h.hexdigest()
-    assert not any("accum" in f for f in B.SOURCES + B.HEADERS)
-
-
-def test_accum_binding_does_not_import_torch_and_has_no_fallback():
-    tree = ast.parse(open(os.path.join(REPO, "ubresnet_amd", "_accum.py")).read())
-    names = [a.name for n in ast.walk(tree) if isinstance(n, ast.Import) for a in n.names]
-    names += [n.module for n in ast.walk(tree) if isinstance(n, ast.ImportFrom)]
-    assert "torch" not in [str(n).split(".")[0] for n in names]
-    import importlib.util
-    old = os.environ.get("UBC_LIB")
-    os.environ["UBC_LIB"] = os.path.join(REPO, "no_such_dir", "libubresnet_accum.so")
-    try:
-        fresh = importlib.util.module_from_spec(importlib.util.spec_from_file_location("_accum_missing", os.path.join(REPO, "ubresnet_amd", "_accum.py")))
-        fresh.__spec__.loader.exec_module(fresh)
-        with pytest.raises(RuntimeError, match="is missing"):
-            fresh.lib()
-    finally:
-        if old is None:
-            del os.environ["UBC_LIB"]
-        else:
-            os.environ["UBC_LIB"] = old
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -182,7 +100,7 @@ _ENTRY = dict(set="ubc_set", add="ubc_add", finish="ubc_finish")
 
 @pytest.mark.parametrize("name", sorted(_BAD))
 def test_argument_refusals_precede_any_launch(name):
-    _need_lib()
+    need_lib(LIB)
     which, change, message = _BAD[name]
     a = dict(_A)
     a.update(change)

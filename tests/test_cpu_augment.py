@@ -1,8 +1,8 @@
-"""Batch augmentation without a GPU: Augment's draws and the numpy reference of uba_augment_batch reproduce the recorded outputs
-of the reference's padandcropandflip bit for bit; params is a pure function of (seed, seq); libubresnet_aug.so's header is C99,
-header / binding / library agree on the entry points, the library stands alone, the kernels compiled into it are exactly the
-ones the case table of tests/test_gpu_augment_exact.py claims, every argument refusal returns its error before any launch; the
-track/shower accuracy; and the host half of a stager that carries an Augment."""
+"""Batch augmentation without a GPU: Augment's draws and the numpy reference of uba_augment_batch reproduce the recorded outputs of
+the reference's padandcropandflip bit for bit; params is a pure function of (seed, seq); libubresnet_aug.so's header is C99,
+header / binding / library agree on the entry points, the kernels compiled into it are exactly the ones the case table of
+tests/test_gpu_augment_exact.py claims, every argument refusal returns its error before any launch; the track/shower accuracy; and
+the host half of a stager that carries an Augment."""
 import ast
 import ctypes as C
 import os
@@ -21,17 +21,13 @@ HEADER = os.path.join(REPO, "include", "ubresnet_aug.h")
 GOLDEN = os.path.join(REPO, "tests", "golden", "augment_padcropflip.npz")
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import kernel_symbols  # noqa: E402
+from cpu_helpers import cc, need_lib, case_ids_run_by_the_gpu_module  # noqa: E402
 from ubresnet_amd import _aug, metrics, synthetic  # noqa: E402
 from ubresnet_amd import build as B  # noqa: E402
 from ubresnet_amd.augment import Augment  # noqa: E402
 from ubresnet_amd.staging import BatchStager  # noqa: E402
 
-LIB = B.AUG_OUT
-
-
-def _need_lib():
-    # (the library is a build product: __graft_entry__.build() makes it; a tree that was never built has nothing to inspect)
-    assert os.path.exists(LIB), "libubresnet_aug.so is not built (python -m ubresnet_amd.build)"
+LIB = B.LIBS["aug"].out
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -114,10 +110,7 @@ def test_header_compiles_as_c99(tmp_path):
     src.write_text('#include "ubresnet_aug.h"\nint main(void) { int (*f)(const float*, const float*, const float*, float*, int64_t*, float*, '
                    'int, int, int, int, int, const int32_t*, int32_t, int, float, int32_t, float, void*) = uba_augment_batch; '
                    'return f == 0 || UBA_LANE_PIXELS != 4 || UBA_OK != 0 || UBA_MAX_BATCH != 256; }\n')
-    cc = "/opt/rocm/lib/llvm/bin/clang"
-    if not os.path.exists(cc):
-        cc = "cc"
-    r = subprocess.run([cc, "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(src)],
+    r = subprocess.run([cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(src)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
 
@@ -131,70 +124,17 @@ def test_header_binding_and_library_agree():
     assert geometry == dict(LANE_PIXELS=_aug.LANE_PIXELS, BLOCK=_aug.BLOCK, MAX_GRID=_aug.MAX_GRID, MAX_BATCH=_aug.MAX_BATCH, MAX_PAD=_aug.MAX_PAD)
     assert geometry == dict(LANE_PIXELS=R.LANE_PIXELS, BLOCK=R.BLOCK, MAX_GRID=R.MAX_GRID, MAX_BATCH=R.MAX_BATCH, MAX_PAD=R.MAX_PAD)
     assert geometry["LANE_PIXELS"] == 4 and geometry["BLOCK"] == 256 and geometry["MAX_BATCH"] == 256
-    _need_lib()
-    lib = _aug.lib()
-    assert all(hasattr(lib, s) for s in _aug.SYMBOLS)
-    assert lib.uba_version() == 1
-    llvm = "/opt/rocm/lib/llvm/bin"
-    # the exports with the library's prefix are exactly the declared ones
-    syms = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--dyn-syms", "-W", LIB], capture_output=True, text=True, check=True).stdout
-    defined = [l.split()[-1] for l in syms.split("\n") if len(l.split()) == 8 and l.split()[6] != "UND"]
-    assert set(n for n in defined if n.startswith("uba_")) == set(_aug.SYMBOLS)
-    assert not [n for n in defined if re.match(r"ub[rpd]_", n)], "a symbol of another library"
-    # the fourth library stands alone: it links against none of the others
-    dyn = subprocess.run([os.path.join(llvm, "llvm-readelf"), "-d", LIB], capture_output=True, text=True, check=True).stdout
-    assert "libubresnet_hip" not in dyn and "libubresnet_post" not in dyn and "libubresnet_data" not in dyn
-
-
-def test_build_covers_the_fourth_library_and_the_hash_only_the_network():
-    assert B.AUG_SOURCES == ["ubr_aug.hip"] and "ubr_aug.hip" not in B.SOURCES + B.POST_SOURCES + B.DATA_SOURCES
-    assert os.path.basename(B.AUG_OUT) == "libubresnet_aug.so"
-    assert not any("aug" in h for h in B.HEADERS + B.POST_HEADERS + B.DATA_HEADERS)
-    assert any("ubresnet_aug.h" in h for h in B.AUG_HEADERS)
-    entry = open(os.path.join(REPO, "__graft_entry__.py")).read()
-    assert "_aug.SYMBOLS" in entry
-
-
-def _case_ids_run_by_the_gpu_module():
-    """the ids that the test functions of tests/test_gpu_augment_exact.py pass to _run() as `what`, from its syntax tree: a
-    literal, or a parameter whose values a parametrize decorator lists literally"""
-    tree = ast.parse(open(os.path.join(REPO, "tests", "test_gpu_augment_exact.py")).read())
-    assert any(isinstance(n, ast.Assign) and ast.unparse(n) == "CASES = R.KERNEL_CASES" for n in tree.body)
-    ran = set()
-    for fn in tree.body:
-        if not (isinstance(fn, ast.FunctionDef) and fn.name.startswith("test_")):
-            continue
-        params = {}
-        for d in fn.decorator_list:
-            if isinstance(d, ast.Call) and ast.unparse(d.func).endswith("parametrize"):
-                try:
-                    names, values = ast.literal_eval(d.args[0]), ast.literal_eval(d.args[1])
-                except ValueError:
-                    continue
-                names = [n.strip() for n in names.split(",")] if isinstance(names, str) else list(names)
-                for row in values:
-                    row = row if len(names) > 1 else (row,)
-                    for n, v in zip(names, row):
-                        params.setdefault(n, []).append(v)
-        for call in ast.walk(fn):
-            if isinstance(call, ast.Call) and isinstance(call.func, ast.Name) and call.func.id == "_run":
-                a = call.args[0]
-                if isinstance(a, ast.Constant):
-                    ran.add(a.value)
-                else:
-                    assert isinstance(a, ast.Name) and a.id in params, "cannot tell the case id of %s" % ast.unparse(call)
-                    ran.update(params[a.id])
-    return ran
+    need_lib(LIB)
 
 
 def test_case_table_equals_the_compiled_kernels():
-    _need_lib()
+    need_lib(LIB)
     have = set(kernel_symbols.kernels(LIB))
     claimed = set(R.KERNEL_CASES)
     assert have - claimed == set(), "compiled kernels without a case in tests/test_gpu_augment_exact.py: %s" % sorted(have - claimed)
     assert claimed - have == set(), "cases for kernels that are not compiled: %s" % sorted(claimed - have)
     assert len(have) <= 2
-    assert _case_ids_run_by_the_gpu_module() == set(i for ids in R.KERNEL_CASES.values() for i in ids)
+    assert case_ids_run_by_the_gpu_module(os.path.join(REPO, "tests", "test_gpu_augment_exact.py")) == set(i for ids in R.KERNEL_CASES.values() for i in ids)
     assert all(ids for ids in R.KERNEL_CASES.values())
 
 
@@ -244,7 +184,7 @@ _BAD = {
 
 @pytest.mark.parametrize("name", sorted(_BAD))
 def test_argument_refusals_precede_any_launch(name):
-    _need_lib()
+    need_lib(LIB)
     a = dict(_GOOD)
     change, message = _BAD[name]
     a.update(change)
@@ -261,7 +201,7 @@ def test_argument_refusals_precede_any_launch(name):
 
 
 def test_binding_checks_the_shape_of_params():
-    _need_lib()
+    need_lib(LIB)
     with pytest.raises(ValueError, match="params"):
         _aug.augment_batch(_P, _P + 0x1000, None, _P + 0x3000, _P + 0x4000, _P + 0x5000, (2, 1, 8, 8), 4, np.zeros((3, 4), np.int32))
     with pytest.raises(RuntimeError, match="image 1: offsets"):

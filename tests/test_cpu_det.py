@@ -1,9 +1,8 @@
 """Detector effects without a GPU: libubresnet_det.so's header is C99; header, binding, reference and library agree on the entry
-points and the geometry; the library stands alone; build.py and the entry point cover it and build() does not; the compiled
-kernels are exactly those the case table of tests/test_gpu_det_exact.py runs; every argument refusal returns UBX_EINVAL with a
-message before any launch; the rule header as a stand-alone program under the host sanitizers against tests/det_ref.py (Philox
-words and dead / gained values bit for bit, noisy values within the derived bound); DetectorEffects.table; the distribution of
-the reference's normals; the host-side refusals of a stager that carries a detector."""
+points and the geometry; the compiled kernels are exactly those the case table of tests/test_gpu_det_exact.py runs; every argument
+refusal returns UBX_EINVAL with a message before any launch; the rule header as a stand-alone program under the host sanitizers
+against tests/det_ref.py (Philox words and dead / gained values bit for bit, noisy values within the derived bound);
+DetectorEffects.table; the distribution of the reference's normals; the host-side refusals of a stager that carries a detector."""
 import ast
 import ctypes as C
 import math
@@ -21,6 +20,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "ubresnet_det.h")
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import kernel_symbols  # noqa: E402
+from cpu_helpers import cc, need_lib, case_ids_run_by_the_gpu_module  # noqa: E402
 from ubresnet_amd import _det as K  # noqa: E402
 from ubresnet_amd import build as B  # noqa: E402
 from ubresnet_amd import synthetic  # noqa: E402
@@ -28,19 +28,8 @@ from ubresnet_amd.augment import Augment  # noqa: E402
 from ubresnet_amd.detector import DetectorEffects, STREAM_TAG  # noqa: E402
 from ubresnet_amd.staging import BatchStager  # noqa: E402
 
-LIB = B.DET_OUT
-LLVM = "/opt/rocm/lib/llvm/bin"
+LIB = B.LIBS["det"].out
 f32 = np.float32
-
-
-def _need_lib():
-    # (the library is a build product: __graft_entry__.build() makes it; a tree that was never built has nothing to inspect)
-    assert os.path.exists(LIB), "libubresnet_det.so is not built (python -m ubresnet_amd.build)"
-
-
-def _cc(plus=False):
-    cc = os.path.join(LLVM, "clang++" if plus else "clang")
-    return cc if os.path.exists(cc) else ("c++" if plus else "cc")
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -56,7 +45,7 @@ def test_header_compiles_as_c99(tmp_path):
                      '  int (*v)(void) = ubx_version;\n'
                      '  return f == 0 || e == 0 || v == 0 || UBX_OK != 0 || UBX_EINVAL != -1 || UBX_ELAUNCH != -2 || UBX_LANE_PIXELS != 4\n'
                      '         || UBX_PHILOX_TAG != 0x55425844u;\n}\n')
-    r = subprocess.run([_cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(proto)],
+    r = subprocess.run([cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(proto)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
 
@@ -76,40 +65,17 @@ def test_header_binding_reference_and_library_agree():
     for phrase in ("THE KERNEL TRUSTS THE TABLE", "0xD2511F53", "0xCD9E8D57", "0x9E3779B9", "0xBB67AE85", "cospif(2 u2)", "sinpif(2 u2)",
                    "__fsqrt_rn", "bit for bit", "EVERY plane", "detector_kernel<false>", "detector_kernel<true>", "not a byte is written"):
         assert phrase in raw, phrase
-    _need_lib()
-    lib = K.lib()
-    assert all(hasattr(lib, s) for s in K.SYMBOLS)
-    assert lib.ubx_version() == 1
-    # the exports with the library's prefix are exactly the declared ones, and none has another library's prefix
-    syms = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--dyn-syms", "-W", LIB], capture_output=True, text=True, check=True).stdout
-    defined = [l.split()[-1] for l in syms.split("\n") if len(l.split()) == 8 and l.split()[6] != "UND"]
-    assert set(n for n in defined if n.startswith("ubx_")) == set(K.SYMBOLS)
-    assert not [n for n in defined if re.match(r"ub[rpdaowgecslkt]_", n)], "a symbol of another library"
-    # the fourteenth library stands alone: it links against none of the others
-    dyn = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "-d", LIB], capture_output=True, text=True, check=True).stdout
-    assert "libubresnet_" not in dyn.replace("libubresnet_det", ""), dyn
-
-
-def _case_ids_run_by_the_gpu_module():
-    """the ids that tests/test_gpu_det_exact.py passes to _run() as `what`: every one a string literal"""
-    tree = ast.parse(open(os.path.join(REPO, "tests", "test_gpu_det_exact.py")).read())
-    assert any(isinstance(n, ast.Assign) and ast.unparse(n) == "CASES = R.KERNEL_CASES" for n in tree.body)
-    ran = set()
-    for call in ast.walk(tree):
-        if isinstance(call, ast.Call) and isinstance(call.func, ast.Name) and call.func.id == "_run":
-            assert isinstance(call.args[0], ast.Constant), "cannot tell the case id of %s" % ast.unparse(call)
-            ran.add(call.args[0].value)
-    return ran
+    need_lib(LIB)
 
 
 def test_the_compiled_kernels_are_the_case_table():
     """no kernel without a case, no case without a kernel; the table's ids are the ids the GPU module runs"""
-    _need_lib()
+    need_lib(LIB)
     compiled = kernel_symbols.kernels(LIB)
     assert compiled == sorted(R.KERNEL_CASES) == ["detector_kernel<false>", "detector_kernel<true>"], compiled
     assert all(R.KERNEL_CASES[k] for k in compiled)
     ids = [i for v in R.KERNEL_CASES.values() for i in v]
-    assert len(ids) == len(set(ids)) and _case_ids_run_by_the_gpu_module() == set(ids)
+    assert len(ids) == len(set(ids)) and case_ids_run_by_the_gpu_module(os.path.join(REPO, "tests", "test_gpu_det_exact.py")) == set(ids)
 
 
 def test_shapes_follow_the_launch_geometry():
@@ -120,66 +86,11 @@ def test_shapes_follow_the_launch_geometry():
     assert R.groups(1, 5, 7) == 10 and R.groups(2, 2, 37) == 40
 
 
-def test_build_covers_the_fourteenth_library_and_build_is_unchanged():
-    assert B.DET_SOURCES == ["ubr_det.hip"]
-    others = (B.SOURCES + B.POST_SOURCES + B.DATA_SOURCES + B.AUG_SOURCES + B.OPT_SOURCES + B.WEIGHT_SOURCES + B.GROUP_SOURCES
-              + B.EMA_SOURCES + B.ACCUM_SOURCES + B.STATS_SOURCES + B.LOSS_SOURCES + B.DICE_SOURCES + B.TTA_SOURCES)
-    assert "ubr_det.hip" not in others
-    assert os.path.basename(B.DET_OUT) == "libubresnet_det.so"
-    assert not any("det" in h for h in B.HEADERS + B.POST_HEADERS + B.DATA_HEADERS + B.AUG_HEADERS + B.OPT_HEADERS + B.WEIGHT_HEADERS
-                   + B.GROUP_HEADERS + B.EMA_HEADERS + B.ACCUM_HEADERS + B.STATS_HEADERS + B.LOSS_HEADERS + B.DICE_HEADERS + B.TTA_HEADERS)
-    assert any("ubresnet_det.h" in h for h in B.DET_HEADERS) and "ubr_det_rule.h" in B.DET_HEADERS
-    assert "-ffp-contract=off" in B.FLAGS and "--offload-arch=gfx950" in B.FLAGS
-    # the new file names carry none of the substrings by which the tests of the other libraries pick out their own commands
-    for name in ("ubr_det.hip", "ubr_det_rule.h", "ubresnet_det.h", "libubresnet_det.so", "_det.py"):
-        assert not any(s in name for s in ("stats", "accum", "ema", "group", "opt", "weight", "aug", "data", "post", "loss", "dice", "tta")), name
-    lines = []
-    old = subprocess.run
-
-    def fake(cmd, **kw):
-        lines.append(cmd)
-        return old(["true"], **kw)
-    subprocess.run = fake
-    try:
-        assert B.build_det(force=True, verbose=False) == B.DET_OUT
-        only = list(lines)
-        del lines[:]
-        B.build(force=True, verbose=False)
-        rest = list(lines)
-    finally:
-        subprocess.run = old
-    assert len(only) == 2, only                                    # build_det() compiles and links this library and nothing else
-    compile_, link = only
-    assert all(f in compile_ for f in B.FLAGS) and compile_[-3].endswith("ubr_det.hip"), "compiled with the shared FLAGS"
-    assert link[-1].endswith("ubr_det.o") and B.DET_OUT in link and sum(a.endswith(".o") for a in link) == 1, "links nothing else"
-    assert sum(1 for c in rest if "-shared" in c) == 9 and not any("ubr_det" in a or "libubresnet_det" in a for c in rest for a in c), \
-        "build() is the nine libraries it was"
-    entry = open(os.path.join(REPO, "__graft_entry__.py")).read()
-    assert "_det.SYMBOLS" in entry and "ubx_version" in entry and "b.build_det(" in entry
-    main = open(os.path.join(REPO, "ubresnet_amd", "build.py")).read().split('if __name__ == "__main__":')[1]
-    assert all("build%s(" % s in main for s in ("", "_stats", "_loss", "_dice", "_tta", "_det")), "the command line builds all fourteen"
-    assert not any("det" in f for f in B.SOURCES + B.HEADERS)        # source_hash() covers the network's kernels only
-
-
-def test_binding_and_detector_do_not_import_torch_and_have_no_fallback():
-    for name in ("_det.py", "detector.py"):
-        tree = ast.parse(open(os.path.join(REPO, "ubresnet_amd", name)).read())
-        names = [a.name for n in ast.walk(tree) if isinstance(n, ast.Import) for a in n.names]
-        names += [n.module for n in ast.walk(tree) if isinstance(n, ast.ImportFrom)]
-        assert "torch" not in [str(n).split(".")[0] for n in names], name
-    import importlib.util
-    old = os.environ.get("UBX_LIB")
-    os.environ["UBX_LIB"] = os.path.join(REPO, "no_such_dir", "libubresnet_det.so")
-    try:
-        fresh = importlib.util.module_from_spec(importlib.util.spec_from_file_location("_det_missing", os.path.join(REPO, "ubresnet_amd", "_det.py")))
-        fresh.__spec__.loader.exec_module(fresh)
-        with pytest.raises(RuntimeError, match="is missing"):
-            fresh.lib()
-    finally:
-        if old is None:
-            del os.environ["UBX_LIB"]
-        else:
-            os.environ["UBX_LIB"] = old
+def test_detector_does_not_import_torch():
+    tree = ast.parse(open(os.path.join(REPO, "ubresnet_amd", "detector.py")).read())
+    names = [a.name for n in ast.walk(tree) if isinstance(n, ast.Import) for a in n.names]
+    names += [n.module for n in ast.walk(tree) if isinstance(n, ast.ImportFrom)]
+    assert "torch" not in [str(n).split(".")[0] for n in names]
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -227,7 +138,7 @@ def _call(a):
 
 @pytest.mark.parametrize("name", sorted(_BAD))
 def test_argument_refusals_precede_any_launch(name):
-    _need_lib()
+    need_lib(LIB)
     a = dict(_GOOD)
     change, message = _BAD[name]
     a.update(change)
@@ -258,7 +169,7 @@ def test_rule_as_a_program_under_the_host_sanitizers(tmp_path):
     x five gains x four sigmas x dead x lit/all x the four columns: dead and gained values bit for bit, noisy ones within the
     bound; the normals at the ends of the uniforms"""
     exe = str(tmp_path / "det_host")
-    r = subprocess.run([_cc(plus=True), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
+    r = subprocess.run([cc(plus=True), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
                         "-Wall", "-Werror", "-I", os.path.join(REPO, "ubresnet_amd", "csrc"), os.path.join(REPO, "tests", "det_host.cpp"), "-o", exe],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr

@@ -1,9 +1,8 @@
 """The region-loss library without a GPU: libubresnet_dice.so's header is C99; header, binding, reference and library agree on the
-entry points, the geometry, the workspace row and the control block; the library stands alone and holds exactly its thirteen
-kernels; build.py and the entry point cover it with one object; every argument refusal returns UBK_EINVAL with a message before
-any launch; tests/dice_ref.py against torch.autograd on the plain fp64 composite; the arithmetic header as a stand-alone host
-program against dice_ref over its edge cases; the refusals of PixelWiseDiceLoss and WeightedSumLoss that need no device."""
-import ast
+entry points, the geometry, the workspace row and the control block; the library holds exactly its thirteen kernels; every
+argument refusal returns UBK_EINVAL with a message before any launch; tests/dice_ref.py against torch.autograd on the plain fp64
+composite; the arithmetic header as a stand-alone host program against dice_ref over its edge cases; the refusals of
+PixelWiseDiceLoss and WeightedSumLoss that need no device."""
 import math
 import os
 import re
@@ -20,21 +19,11 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "ubresnet_dice.h")
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import kernel_symbols  # noqa: E402
+from cpu_helpers import cc, need_lib  # noqa: E402
 from ubresnet_amd import _dice as K  # noqa: E402
 from ubresnet_amd import build as B  # noqa: E402
 
-LIB = B.DICE_OUT
-LLVM = "/opt/rocm/lib/llvm/bin"
-
-
-def _need_lib():
-    # (the library is a build product: __graft_entry__.build() makes it; a tree that was never built has nothing to inspect)
-    assert os.path.exists(LIB), "libubresnet_dice.so is not built (python -m ubresnet_amd.build)"
-
-
-def _cc(plus=False):
-    cc = os.path.join(LLVM, "clang++" if plus else "clang")
-    return cc if os.path.exists(cc) else ("c++" if plus else "cc")
+LIB = B.LIBS["dice"].out
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -51,7 +40,7 @@ def test_header_compiles_as_c99(tmp_path):
                      '  const char* (*e)(void) = ubk_last_error;\n'
                      '  int (*v)(void) = ubk_version;\n'
                      '  return f == 0 || b == 0 || e == 0 || v == 0 || UBK_OK != 0 || UBK_EINVAL != -1 || UBK_ELAUNCH != -2;\n}\n')
-    r = subprocess.run([_cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(proto)],
+    r = subprocess.run([cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(proto)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
 
@@ -60,7 +49,7 @@ def test_header_binding_reference_and_library_agree():
     raw = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
     declared = set(re.findall(r"\b(ubk_[a-z_0-9]+)\s*\(", text))
-    _need_lib()
+    need_lib(LIB)
     assert declared == set(K.SYMBOLS) and len(K.SYMBOLS) == len(set(K.SYMBOLS)) == 4
     num = {k: int(v) for k, v in re.findall(r"#define\s+UBK_([A-Z_0-9]+)\s+\(?(-?\d+)\)?\s", text)}
     assert dict(BLOCK=num["BLOCK"], UNROLL=num["UNROLL"], MAX_GRID=num["MAX_GRID"]) == dict(BLOCK=K.BLOCK, UNROLL=K.UNROLL, MAX_GRID=K.MAX_GRID)
@@ -77,17 +66,6 @@ def test_header_binding_reference_and_library_agree():
     for phrase in ("expm1f", "expf(lp_c)", "not contracted", "NaN", "Dn_c == 0", "S == 0", "present_only", "no atomic", "4 C + 12", "8 C + 12",
                    "the other channels stay finite", "lp = -inf"):
         assert phrase in raw, phrase
-    lib = K.lib()
-    assert all(hasattr(lib, s) for s in K.SYMBOLS)
-    assert lib.ubk_version() == 1
-    # the exports with the library's prefix are exactly the declared ones, and none has another library's prefix
-    syms = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--dyn-syms", "-W", LIB], capture_output=True, text=True, check=True).stdout
-    defined = [l.split()[-1] for l in syms.split("\n") if len(l.split()) == 8 and l.split()[6] != "UND"]
-    assert set(n for n in defined if n.startswith("ubk_")) == set(K.SYMBOLS)
-    assert not [n for n in defined if re.match(r"ub[rpdaowgecsl]_", n)], "a symbol of another library"
-    # the twelfth library stands alone: it links against none of the others
-    dyn = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "-d", LIB], capture_output=True, text=True, check=True).stdout
-    assert "libubresnet_" not in dyn.replace("libubresnet_dice", "")
     # thirteen kernels: the forward for C = 1 .. 4 and for the runtime C, in both forms; the finish; both forms of the backward
     want = ["dice_fwd_kernel<%d, %s>" % (c, v) for c in range(K.REG_CLASSES + 1) for v in ("false", "true")]
     want += ["dice_bwd_kernel<false>", "dice_bwd_kernel<true>", "dice_finish_kernel"]
@@ -108,55 +86,6 @@ def test_read_ctl_unpacks_the_words():
     assert (c["tp"][1], c["fp"][2], c["fn"][15], c["T"][3], c["S"], c["pixels"][4], c["valid"], c["bad"]) == (1.5, 2.5, 3.5, 0.75, 2.0, 9, 7, 3)
     assert (c["k1"][5], c["k0"][15], c["loss"]) == (-0.25, 0.125, 0.75)
     assert all(len(c[k]) == 16 for k in ("tp", "fp", "fn", "pixels", "T", "k1", "k0"))
-
-
-def test_build_covers_the_twelfth_library_with_one_object():
-    assert B.DICE_SOURCES == ["ubr_dice.hip"]
-    others = (B.SOURCES + B.POST_SOURCES + B.DATA_SOURCES + B.AUG_SOURCES + B.OPT_SOURCES + B.WEIGHT_SOURCES + B.GROUP_SOURCES + B.EMA_SOURCES
-              + B.ACCUM_SOURCES + B.STATS_SOURCES + B.LOSS_SOURCES)
-    assert "ubr_dice.hip" not in others
-    assert os.path.basename(B.DICE_OUT) == "libubresnet_dice.so"
-    assert any("ubresnet_dice.h" in h for h in B.DICE_HEADERS) and "ubr_dice_term.h" in B.DICE_HEADERS
-    assert "-ffp-contract=off" in B.FLAGS and "--offload-arch=gfx950" in B.FLAGS
-    lines = []
-    old = subprocess.run
-
-    def fake(cmd, **kw):
-        lines.append(cmd)
-        return old(["true"], **kw)
-    subprocess.run = fake
-    try:
-        assert B.build_dice(force=True, verbose=False) == B.DICE_OUT
-    finally:
-        subprocess.run = old
-    assert len(lines) == 2, lines                                  # build_dice() compiles and links this library and nothing else
-    compile_, link = lines
-    assert all(f in compile_ for f in B.FLAGS) and compile_[-3].endswith("ubr_dice.hip"), "compiled with the shared FLAGS"
-    assert link[-1].endswith("ubr_dice.o") and B.DICE_OUT in link and sum(a.endswith(".o") for a in link) == 1, "links nothing else"
-    entry = open(os.path.join(REPO, "__graft_entry__.py")).read()
-    assert "_dice.SYMBOLS" in entry and "ubk_version" in entry and "b.build_dice(" in entry
-    main = open(os.path.join(REPO, "ubresnet_amd", "build.py")).read().split('if __name__ == "__main__":')[1]
-    assert "build_dice(" in main, "the command line builds all twelve"
-
-
-def test_dice_binding_does_not_import_torch_and_has_no_fallback():
-    tree = ast.parse(open(os.path.join(REPO, "ubresnet_amd", "_dice.py")).read())
-    names = [a.name for n in ast.walk(tree) if isinstance(n, ast.Import) for a in n.names]
-    names += [n.module for n in ast.walk(tree) if isinstance(n, ast.ImportFrom)]
-    assert "torch" not in [str(n).split(".")[0] for n in names]
-    import importlib.util
-    old = os.environ.get("UBK_LIB")
-    os.environ["UBK_LIB"] = os.path.join(REPO, "no_such_dir", "libubresnet_dice.so")
-    try:
-        fresh = importlib.util.module_from_spec(importlib.util.spec_from_file_location("_dice_missing", os.path.join(REPO, "ubresnet_amd", "_dice.py")))
-        fresh.__spec__.loader.exec_module(fresh)
-        with pytest.raises(RuntimeError, match="is missing"):
-            fresh.lib()
-    finally:
-        if old is None:
-            del os.environ["UBK_LIB"]
-        else:
-            os.environ["UBK_LIB"] = old
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -224,7 +153,7 @@ _ENTRY = dict(fwd="ubk_dice_fwd", bwd="ubk_dice_bwd")
 
 @pytest.mark.parametrize("name", sorted(_BAD))
 def test_argument_refusals_precede_any_launch(name):
-    _need_lib()
+    need_lib(LIB)
     which, change, message = _BAD[name]
     a = dict(_A)
     a.update(change)
@@ -325,7 +254,7 @@ def test_arithmetic_as_a_host_program_matches_the_reference(tmp_path):
     as a process of its own.  lp over {0, -0.0, -1e-30, -1e-45, -104, -110, -inf, NaN, below the underflow of expf} and ordinary
     values, pw over {0.5, 2, a subnormal, 0}: the addends and the gradient against dice_ref within its bound; then the finish rule"""
     exe = str(tmp_path / "dice_host")
-    r = subprocess.run([_cc(plus=True), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Werror",
+    r = subprocess.run([cc(plus=True), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Werror",
                         "-I", os.path.join(REPO, "ubresnet_amd", "csrc"), os.path.join(REPO, "tests", "dice_host.cpp"), "-o", exe],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr

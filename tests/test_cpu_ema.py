@@ -1,8 +1,7 @@
-"""The parameter-averaging library without a GPU: libubresnet_ema.so's header is C99; header, binding, reference and library agree
-on the entry points, the geometry and the control block; the library stands alone; build.py and the entry point cover it and
-source_hash() does not; every argument refusal returns UBE_EINVAL with a message before any launch; the schedule (a host/device
-inline function) as a stand-alone program under the host sanitizers against ema_ref bit for bit; ParamEMA's own refusals."""
-import ast
+"""The parameter-averaging library without a GPU: libubresnet_ema.so's header is C99; header, binding, reference and library agree on
+the entry points, the geometry and the control block; every argument refusal returns UBE_EINVAL with a message before any launch;
+the schedule (a host/device inline function) as a stand-alone program under the host sanitizers against ema_ref bit for bit;
+ParamEMA's own refusals."""
 import ctypes as C
 import os
 import re
@@ -19,21 +18,11 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "ubresnet_ema.h")
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import kernel_symbols  # noqa: E402
+from cpu_helpers import cc, need_lib  # noqa: E402
 from ubresnet_amd import _ema as E  # noqa: E402
 from ubresnet_amd import build as B  # noqa: E402
 
-LIB = B.EMA_OUT
-LLVM = "/opt/rocm/lib/llvm/bin"
-
-
-def _need_lib():
-    # (the library is a build product: __graft_entry__.build() makes it; a tree that was never built has nothing to inspect)
-    assert os.path.exists(LIB), "libubresnet_ema.so is not built (python -m ubresnet_amd.build)"
-
-
-def _cc(plus=False):
-    cc = os.path.join(LLVM, "clang++" if plus else "clang")
-    return cc if os.path.exists(cc) else ("c++" if plus else "cc")
+LIB = B.LIBS["ema"].out
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -50,7 +39,7 @@ def test_header_compiles_as_c99_and_fixes_the_layout(tmp_path):
                      '  int (*us)(const void*, int64_t, const void*, void*) = ube_update_segs;\n'
                      '  int (*ss)(const void*, int64_t, void*) = ube_swap_segs;\n'
                      '  return i == 0 || a == 0 || u == 0 || s == 0 || us == 0 || ss == 0 || UBE_OK != 0 || UBE_EINVAL != -1;\n}\n')
-    r = subprocess.run([_cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(proto)],
+    r = subprocess.run([cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(proto)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "ubresnet_ema.h"\n'
@@ -59,7 +48,7 @@ def test_header_compiles_as_c99_and_fixes_the_layout(tmp_path):
                    '         (int)offsetof(ube_ctl, d), (int)offsetof(ube_ctl, reserved), (int)offsetof(ube_ctl, updates), (int)offsetof(ube_ctl, held));\n'
                    '  printf("seg %d %d %d %d\\n", (int)sizeof(ube_seg), (int)offsetof(ube_seg, shadow), (int)offsetof(ube_seg, live), (int)offsetof(ube_seg, count));\n'
                    '  return 0;\n}\n')
-    r = subprocess.run([_cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.dirname(HEADER), str(src), "-o", str(exe)],
+    r = subprocess.run([cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.dirname(HEADER), str(src), "-o", str(exe)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     out = {l.split()[0]: [int(x) for x in l.split()[1:]] for l in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.strip().split("\n")}
@@ -81,81 +70,14 @@ def test_header_binding_and_library_agree():
     raw = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
     declared = set(re.findall(r"\b(ube_[a-z_0-9]+)\s*\(", text))
-    _need_lib()
+    need_lib(LIB)
     assert declared == set(E.SYMBOLS) and len(E.SYMBOLS) == len(set(E.SYMBOLS))
     geometry = {k: int(v) for k, v in re.findall(r"#define\s+UBE_(BLOCK|UNROLL|MAX_GRID|SEG_GRID|CTL_BYTES)\s+(\d+)", text)}
     assert geometry == dict(BLOCK=E.BLOCK, UNROLL=E.UNROLL, MAX_GRID=E.MAX_GRID, SEG_GRID=E.SEG_GRID, CTL_BYTES=E.CTL_BYTES)
     assert geometry == dict(BLOCK=R.BLOCK, UNROLL=R.UNROLL, MAX_GRID=R.MAX_GRID, SEG_GRID=R.SEG_GRID, CTL_BYTES=R.CTL_BYTES)
-    lib = E.lib()
-    assert all(hasattr(lib, s) for s in E.SYMBOLS)
-    assert lib.ube_version() == 1
-    # the exports with the library's prefix are exactly the declared ones, and none has another library's prefix
-    syms = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--dyn-syms", "-W", LIB], capture_output=True, text=True, check=True).stdout
-    defined = [l.split()[-1] for l in syms.split("\n") if len(l.split()) == 8 and l.split()[6] != "UND"]
-    assert set(n for n in defined if n.startswith("ube_")) == set(E.SYMBOLS)
-    assert not [n for n in defined if re.match(r"ub[rpdaowg]_", n)], "a symbol of another library"
-    # the eighth library stands alone: it links against none of the others
-    dyn = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "-d", LIB], capture_output=True, text=True, check=True).stdout
-    for other in ("libubresnet_hip", "libubresnet_post", "libubresnet_data", "libubresnet_aug", "libubresnet_opt", "libubresnet_weight",
-                  "libubresnet_group"):
-        assert other not in dyn
     # six kernels, and nothing of them in the network library
     assert sorted(k.split("(")[0].split("::")[-1] for k in kernel_symbols.kernels(LIB)) == [
         "advance_kernel", "ctl_init_kernel", "swap_kernel", "swap_segs_kernel", "update_kernel", "update_segs_kernel"]
-
-
-def test_build_covers_the_eighth_library_and_the_hash_only_the_network():
-    assert B.EMA_SOURCES == ["ubr_ema.hip"]
-    assert "ubr_ema.hip" not in B.SOURCES + B.POST_SOURCES + B.DATA_SOURCES + B.AUG_SOURCES + B.OPT_SOURCES + B.WEIGHT_SOURCES + B.GROUP_SOURCES
-    assert os.path.basename(B.EMA_OUT) == "libubresnet_ema.so"
-    assert not any("ema" in h for h in B.HEADERS + B.POST_HEADERS + B.DATA_HEADERS + B.AUG_HEADERS + B.OPT_HEADERS + B.WEIGHT_HEADERS + B.GROUP_HEADERS)
-    assert any("ubresnet_ema.h" in h for h in B.EMA_HEADERS) and "ubr_ema_sched.h" in B.EMA_HEADERS
-    assert "-ffp-contract=off" in B.FLAGS and "--offload-arch=gfx950" in B.FLAGS
-    lines = []
-    old = subprocess.run
-
-    def fake(cmd, **kw):
-        lines.append(cmd)
-        return old(["true"], **kw)
-    subprocess.run = fake
-    try:
-        B.build(force=True, verbose=False)
-    finally:
-        subprocess.run = old
-    mine = [c for c in lines if any("ubr_ema" in a or "libubresnet_ema" in a for a in c)]
-    assert len(mine) == 2, mine
-    compile_, link = mine
-    assert all(f in compile_ for f in B.FLAGS), "the averaging library is compiled with the shared FLAGS"
-    assert link[-1].endswith("ubr_ema.o") and B.EMA_OUT in link and sum(a.endswith(".o") for a in link) == 1, "links nothing else"
-    entry = open(os.path.join(REPO, "__graft_entry__.py")).read()
-    assert "_ema.SYMBOLS" in entry and "ube_version" in entry
-    import hashlib
-    h = hashlib.sha256()
-    for f in sorted(B.SOURCES) + sorted(B.HEADERS):
-        with open(os.path.join(B.CSRC, f), "rb") as fh:
-            h.update(f.encode() + b"\0" + fh.read())
-    assert B.source_hash() == h.hexdigest()
-
-
-def test_ema_binding_does_not_import_torch():
-    tree = ast.parse(open(os.path.join(REPO, "ubresnet_amd", "_ema.py")).read())
-    names = [a.name for n in ast.walk(tree) if isinstance(n, ast.Import) for a in n.names]
-    names += [n.module for n in ast.walk(tree) if isinstance(n, ast.ImportFrom)]
-    assert "torch" not in [str(n).split(".")[0] for n in names]
-    # and no fallback: a library that is not there is an error
-    import importlib.util
-    old = os.environ.get("UBE_LIB")
-    os.environ["UBE_LIB"] = os.path.join(REPO, "no_such_dir", "libubresnet_ema.so")
-    try:
-        fresh = importlib.util.module_from_spec(importlib.util.spec_from_file_location("_ema_missing", os.path.join(REPO, "ubresnet_amd", "_ema.py")))
-        fresh.__spec__.loader.exec_module(fresh)
-        with pytest.raises(RuntimeError, match="is missing"):
-            fresh.lib()
-    finally:
-        if old is None:
-            del os.environ["UBE_LIB"]
-        else:
-            os.environ["UBE_LIB"] = old
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -215,7 +137,7 @@ _ENTRY = dict(init="ube_ctl_init", advance="ube_advance", update="ube_update", s
 
 @pytest.mark.parametrize("name", sorted(_BAD))
 def test_argument_refusals_precede_any_launch(name):
-    _need_lib()
+    need_lib(LIB)
     which, change, message = _BAD[name]
     a = dict(_A)
     a.update(change)
@@ -265,7 +187,7 @@ def test_schedule_as_a_program_under_the_host_sanitizers(tmp_path):
     """tests/ema_host.cpp has its own main and includes the schedule's header; built with -fsanitize=address,undefined and run as
     a process of its own; (w, d) bit for bit against ema_ref for u = 0 .. 2000 and around the u where the minimum changes sides"""
     exe = str(tmp_path / "ema_host")
-    r = subprocess.run([_cc(plus=True), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Werror",
+    r = subprocess.run([cc(plus=True), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Werror",
                         "-ffp-contract=off", "-I", os.path.join(REPO, "ubresnet_amd", "csrc"), os.path.join(REPO, "tests", "ema_host.cpp"), "-o", exe],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr

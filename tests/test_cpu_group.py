@@ -1,10 +1,8 @@
-"""The grouped optimizer library without a GPU: libubresnet_group.so's header is C99; header, binding and library agree on the
-entry points and on the control block, whose head is ubo_ctl's; the library stands alone; build.py and the entry point cover it
-and source_hash() does not; the kernels compiled into it are exactly the ones the case table of tests/test_gpu_group_exact.py
-claims; the tile planner (pure host code) against group_ref's, through the library and as a stand-alone program under the host
-sanitizers; every argument refusal returns its error before any launch; split_decay, the group rules and torch's numbering of
-state_dict() on a stand-in that launches nothing."""
-import ast
+"""The grouped optimizer library without a GPU: libubresnet_group.so's header is C99; header, binding and library agree on the entry
+points and on the control block, whose head is ubo_ctl's; the kernels compiled into it are exactly the ones the case table of
+tests/test_gpu_group_exact.py claims; the tile planner (pure host code) against group_ref's, through the library and as a
+stand-alone program under the host sanitizers; every argument refusal returns its error before any launch; split_decay, the group
+rules and torch's numbering of state_dict() on a stand-in that launches nothing."""
 import ctypes as C
 import math
 import os
@@ -22,27 +20,12 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "ubresnet_group.h")
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import kernel_symbols  # noqa: E402
+from cpu_helpers import cc, need_lib, case_ids_run_by_the_gpu_module  # noqa: E402
+from ubresnet_amd import _group as G  # noqa: E402
 from ubresnet_amd import _opt  # noqa: E402
 from ubresnet_amd import build as B  # noqa: E402
 
-try:
-    from ubresnet_amd import _group as G
-except ImportError:                         # a tree without the grouped library: every test below fails on its first use of G
-    G = None
-
-LIB = getattr(B, "GROUP_OUT", None)
-LLVM = "/opt/rocm/lib/llvm/bin"
-
-
-def _need_lib():
-    # (the library is a build product: __graft_entry__.build() makes it; a tree that was never built has nothing to inspect)
-    assert G is not None, "ubresnet_amd/_group.py is missing"
-    assert LIB and os.path.exists(LIB), "libubresnet_group.so is not built (python -m ubresnet_amd.build)"
-
-
-def _cc(plus=False):
-    cc = os.path.join(LLVM, "clang++" if plus else "clang")
-    return cc if os.path.exists(cc) else ("c++" if plus else "cc")
+LIB = B.LIBS["group"].out
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -61,7 +44,7 @@ def test_header_compiles_as_c99(tmp_path):
                    '  int (*sg)(const void*, int64_t, ubg_state*, void*) = ubg_state_get;\n'
                    '  return p == 0 || n == 0 || v == 0 || a == 0 || s == 0 || ss == 0 || sg == 0 || UBG_OK != 0 || sizeof(ubg_ctl) != UBG_CTL_HEAD_BYTES\n'
                    '         || sizeof(ubg_tile) != 16 || sizeof(ubg_hyper) != 16 || sizeof(ubg_state) != 16;\n}\n')
-    r = subprocess.run([_cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(src)],
+    r = subprocess.run([cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(src)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
 
@@ -70,7 +53,7 @@ def test_header_binding_and_library_agree():
     raw = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
     declared = set(re.findall(r"\b(ubg_[a-z_0-9]+)\s*\(", text))
-    _need_lib()
+    need_lib(LIB)
     assert declared == set(G.SYMBOLS) and len(G.SYMBOLS) == len(set(G.SYMBOLS))
     geometry = {k: int(v) for k, v in re.findall(r"#define\s+UBG_(BLOCK|TILE_UNITS|MAX_GRID|STEP_GRID|CTL_HEAD_BYTES)\s+(\d+)", text)}
     assert geometry == dict(BLOCK=G.BLOCK, TILE_UNITS=G.TILE_UNITS, MAX_GRID=G.MAX_GRID, STEP_GRID=G.STEP_GRID, CTL_HEAD_BYTES=G.CTL_HEAD_BYTES)
@@ -78,23 +61,11 @@ def test_header_binding_and_library_agree():
     assert G.TILE_UNITS == 4 * G.BLOCK == 1024
     assert re.search(r"#define\s+UBG_CTL_BYTES\s+\(UBG_CTL_HEAD_BYTES \+ 8 \* UBG_MAX_GRID\)", text)
     assert G.CTL_BYTES == R.CTL_BYTES == _opt.CTL_BYTES == geometry["CTL_HEAD_BYTES"] + 8 * geometry["MAX_GRID"]
-    lib = G.lib()
-    assert all(hasattr(lib, s) for s in G.SYMBOLS)
-    assert lib.ubg_version() == 1
-    # the exports with the library's prefix are exactly the declared ones, and none has another library's prefix
-    syms = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--dyn-syms", "-W", LIB], capture_output=True, text=True, check=True).stdout
-    defined = [l.split()[-1] for l in syms.split("\n") if len(l.split()) == 8 and l.split()[6] != "UND"]
-    assert set(n for n in defined if n.startswith("ubg_")) == set(G.SYMBOLS)
-    assert not [n for n in defined if re.match(r"ub[rpdaow]_", n)], "a symbol of another library"
-    # the seventh library stands alone: it links against none of the others
-    dyn = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "-d", LIB], capture_output=True, text=True, check=True).stdout
-    for other in ("libubresnet_hip", "libubresnet_post", "libubresnet_data", "libubresnet_aug", "libubresnet_opt", "libubresnet_weight"):
-        assert other not in dyn
 
 
 def test_control_block_head_is_ubo_ctl_field_by_field(tmp_path):
     """offsetof() of every field of ubg_ctl and of ubo_ctl as a C compiler sees the two headers; the record sizes likewise"""
-    _need_lib()
+    need_lib(LIB)
     assert C.sizeof(G.Ctl) == G.CTL_HEAD_BYTES == 80
     mine = {name: getattr(G.Ctl, name).offset for name, _ in G.Ctl._fields_}
     assert mine == R.OFFSETS
@@ -109,7 +80,7 @@ def test_control_block_head_is_ubo_ctl_field_by_field(tmp_path):
                    '  printf("hyper %d %d %d\\n", (int)offsetof(ubg_hyper, lr), (int)offsetof(ubg_hyper, weight_decay), (int)offsetof(ubg_hyper, active));\n'
                    '  printf("state %d %d %d\\n", (int)offsetof(ubg_state, applied), (int)offsetof(ubg_state, bc1), (int)offsetof(ubg_state, sqrt_bc2));\n'
                    '  return 0;\n}\n')
-    r = subprocess.run([_cc(), "-std=c99", "-I", os.path.dirname(HEADER), str(src), "-o", str(exe)], capture_output=True, text=True)
+    r = subprocess.run([cc(), "-std=c99", "-I", os.path.dirname(HEADER), str(src), "-o", str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     out = {l.split()[0]: tuple(int(x) for x in l.split()[1:]) for l in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.strip().split("\n")}
     for name, off in mine.items():
@@ -123,89 +94,20 @@ def test_control_block_head_is_ubo_ctl_field_by_field(tmp_path):
     assert h.apply == int.from_bytes(bytes(range(20, 24)), "little") and h.skipped == int.from_bytes(bytes(range(48, 56)), "little")
 
 
-def test_build_covers_the_seventh_library_and_the_hash_only_the_network():
-    assert B.GROUP_SOURCES == ["ubr_group.hip"]
-    assert "ubr_group.hip" not in B.SOURCES + B.POST_SOURCES + B.DATA_SOURCES + B.AUG_SOURCES + B.OPT_SOURCES + B.WEIGHT_SOURCES
-    assert os.path.basename(B.GROUP_OUT) == "libubresnet_group.so"
-    assert not any("group" in h for h in B.HEADERS + B.POST_HEADERS + B.DATA_HEADERS + B.AUG_HEADERS + B.OPT_HEADERS + B.WEIGHT_HEADERS)
-    assert any("ubresnet_group.h" in h for h in B.GROUP_HEADERS) and "ubr_group_plan.h" in B.GROUP_HEADERS
-    assert "-ffp-contract=off" in B.FLAGS and "--offload-arch=gfx950" in B.FLAGS
-    lines = []
-    old = subprocess.run
-
-    def fake(cmd, **kw):
-        lines.append(cmd)
-        return old(["true"], **kw)
-    subprocess.run = fake
-    try:
-        B.build(force=True, verbose=False)
-    finally:
-        subprocess.run = old
-    mine = [c for c in lines if any("ubr_group" in a or "libubresnet_group" in a for a in c)]
-    assert len(mine) == 2, mine
-    compile_, link = mine
-    assert all(f in compile_ for f in B.FLAGS), "the group library is compiled with the shared FLAGS"
-    assert link[-1].endswith("ubr_group.o") and B.GROUP_OUT in link and sum(a.endswith(".o") for a in link) == 1, "links nothing else"
-    entry = open(os.path.join(REPO, "__graft_entry__.py")).read()
-    assert "_group.SYMBOLS" in entry and "ubg_version" in entry
-    # source_hash() reads SOURCES and HEADERS only: a hash over those files by hand is the same
-    import hashlib
-    h = hashlib.sha256()
-    for f in sorted(B.SOURCES) + sorted(B.HEADERS):
-        with open(os.path.join(B.CSRC, f), "rb") as fh:
-            h.update(f.encode() + b"\0" + fh.read())
-    assert B.source_hash() == h.hexdigest()
-
-
-def test_group_binding_does_not_import_torch():
-    tree = ast.parse(open(os.path.join(REPO, "ubresnet_amd", "_group.py")).read())
-    names = [a.name for n in ast.walk(tree) if isinstance(n, ast.Import) for a in n.names]
-    names += [n.module for n in ast.walk(tree) if isinstance(n, ast.ImportFrom)]
-    assert "torch" not in [str(n).split(".")[0] for n in names]
-    # and no fallback: a library that is not there is an error
-    import importlib.util
-    old = os.environ.get("UBG_LIB")
-    os.environ["UBG_LIB"] = os.path.join(REPO, "no_such_dir", "libubresnet_group.so")
-    try:
-        fresh = importlib.util.module_from_spec(importlib.util.spec_from_file_location("_group_missing", os.path.join(REPO, "ubresnet_amd", "_group.py")))
-        fresh.__spec__.loader.exec_module(fresh)
-        with pytest.raises(RuntimeError, match="is missing"):
-            fresh.lib()
-    finally:
-        if old is None:
-            del os.environ["UBG_LIB"]
-        else:
-            os.environ["UBG_LIB"] = old
-
-
-def _case_ids_run_by_the_gpu_module():
-    """the literal ids that the test functions of tests/test_gpu_group_exact.py pass to _case()"""
-    tree = ast.parse(open(os.path.join(REPO, "tests", "test_gpu_group_exact.py")).read())
-    assert any(isinstance(n, ast.Assign) and ast.unparse(n) == "CASES = R.KERNEL_CASES" for n in tree.body)
-    ran = set()
-    for fn in tree.body:
-        if isinstance(fn, ast.FunctionDef) and fn.name.startswith("test_"):
-            for call in ast.walk(fn):
-                if isinstance(call, ast.Call) and isinstance(call.func, ast.Name) and call.func.id == "_case":
-                    assert isinstance(call.args[0], ast.Constant), "cannot tell the case id of %s" % ast.unparse(call)
-                    ran.add(call.args[0].value)
-    return ran
-
-
 def test_case_table_equals_the_compiled_kernels():
-    _need_lib()
+    need_lib(LIB)
     have = set(kernel_symbols.kernels(LIB))
     claimed = set(R.KERNEL_CASES)
     assert have - claimed == set(), "compiled kernels without a case in tests/test_gpu_group_exact.py: %s" % sorted(have - claimed)
     assert claimed - have == set(), "cases for kernels that are not compiled: %s" % sorted(claimed - have)
-    assert _case_ids_run_by_the_gpu_module() == set(i for ids in R.KERNEL_CASES.values() for i in ids)
+    assert case_ids_run_by_the_gpu_module(os.path.join(REPO, "tests", "test_gpu_group_exact.py"), call="_case") == set(i for ids in R.KERNEL_CASES.values() for i in ids)
     assert all(ids for ids in R.KERNEL_CASES.values())
 
 
 def test_the_other_optimizer_library_is_as_it_was():
     """libubresnet_opt.so keeps its five kernels and its exports"""
-    assert os.path.exists(B.OPT_OUT), "libubresnet_opt.so is not built"
-    assert len(kernel_symbols.kernels(B.OPT_OUT)) == 5
+    need_lib(B.LIBS["opt"].out)
+    assert len(kernel_symbols.kernels(B.LIBS["opt"].out)) == 5
     assert _opt.SYMBOLS == ["ubo_ctl_init", "ubo_grad_norm", "ubo_adam_step", "ubo_sgd_step", "ubo_last_error", "ubo_version"]
 
 
@@ -226,7 +128,7 @@ def test_reference_planner_by_hand():
 
 @pytest.mark.parametrize("name", [n for n, _, _ in R.PLAN_LISTS])
 def test_plan_tiles_equals_the_reference_planner(name):
-    _need_lib()
+    need_lib(LIB)
     u0, units = {n: (a, b) for n, a, b in _lists()}[name]
     want = R.plan_tiles(u0, units)
     got = G.plan_tiles(u0, units)
@@ -248,7 +150,7 @@ def test_plan_tiles_equals_the_reference_planner(name):
 
 @pytest.mark.parametrize("name", [n for n, _, _ in R.PLAN_LISTS if n != "single-unit"])
 def test_plan_tiles_refuses_a_table_that_is_too_small(name):
-    _need_lib()
+    need_lib(LIB)
     u0, units = {n: (a, b) for n, a, b in _lists()}[name]
     want = R.plan_tiles(u0, units)
     cap = len(want) - 1
@@ -274,7 +176,7 @@ _BAD_PLANS = {
 
 @pytest.mark.parametrize("name", sorted(_BAD_PLANS))
 def test_plan_tiles_refuses_bad_segments(name):
-    _need_lib()
+    need_lib(LIB)
     u0, units, message = _BAD_PLANS[name]
     a0, a1 = np.asarray(u0 + [0], np.int64), np.asarray(units + [0], np.int64)
     table = np.full(64, -1, dtype=np.int64).view(G.TILE)
@@ -289,7 +191,7 @@ def test_planner_as_a_program_under_the_host_sanitizers(tmp_path):
     """tests/group_plan_host.cpp has its own main and includes the planner's header; built with -fsanitize=address,undefined and
     run as a process of its own over the same segment lists, with a table of exactly `cap` tiles on the heap"""
     exe = str(tmp_path / "group_plan_host")
-    r = subprocess.run([_cc(plus=True), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Werror",
+    r = subprocess.run([cc(plus=True), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Werror",
                         "-I", os.path.join(REPO, "ubresnet_amd", "csrc"), os.path.join(REPO, "tests", "group_plan_host.cpp"), "-o", exe],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
@@ -394,7 +296,7 @@ _ENTRY = dict(norm="ubg_grad_norm", advance="ubg_advance", adam="ubg_adam_step",
 
 @pytest.mark.parametrize("name", sorted(_BAD))
 def test_argument_refusals_precede_any_launch(name):
-    _need_lib()
+    need_lib(LIB)
     which, change, message = _BAD[name]
     a = dict(_A)
     a.update(change)

@@ -1,10 +1,8 @@
 """The focal-loss library without a GPU: libubresnet_loss.so's header is C99; header, binding, reference and library agree on the
-entry points, the geometry, the workspace row and the control block; the library stands alone; build.py and the entry point cover
-it and build() does not; every argument refusal returns UBL_EINVAL with a message before any launch; tests/loss_ref.py against
-torch.autograd on the fp64 composite, against kref's NLL reference and the reference criterion's semantics at gamma = 0, and
-against torch's weighted mean; the arithmetic header as a stand-alone program under the host sanitizers against loss_ref over its
-edge cases; PixelWiseFocalLoss's refusals that need no device."""
-import ast
+entry points, the geometry, the workspace row and the control block; every argument refusal returns UBL_EINVAL with a message
+before any launch; tests/loss_ref.py against torch.autograd on the fp64 composite, against kref's NLL reference and the reference
+criterion's semantics at gamma = 0, and against torch's weighted mean; the arithmetic header as a stand-alone program under the
+host sanitizers against loss_ref over its edge cases; PixelWiseFocalLoss's refusals that need no device."""
 import math
 import os
 import re
@@ -22,22 +20,12 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "ubresnet_loss.h")
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import kernel_symbols  # noqa: E402
+from cpu_helpers import cc, need_lib  # noqa: E402
 from ubresnet_amd import _loss as K  # noqa: E402
 from ubresnet_amd import build as B  # noqa: E402
 
-LIB = B.LOSS_OUT
-LLVM = "/opt/rocm/lib/llvm/bin"
+LIB = B.LIBS["loss"].out
 GAMMAS = [0.5, 1.0, 2.0, 5.0]
-
-
-def _need_lib():
-    # (the library is a build product: __graft_entry__.build() makes it; a tree that was never built has nothing to inspect)
-    assert os.path.exists(LIB), "libubresnet_loss.so is not built (python -m ubresnet_amd.build)"
-
-
-def _cc(plus=False):
-    cc = os.path.join(LLVM, "clang++" if plus else "clang")
-    return cc if os.path.exists(cc) else ("c++" if plus else "cc")
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -54,7 +42,7 @@ def test_header_compiles_as_c99(tmp_path):
                      '  const char* (*e)(void) = ubl_last_error;\n'
                      '  int (*v)(void) = ubl_version;\n'
                      '  return f == 0 || b == 0 || e == 0 || v == 0 || UBL_OK != 0 || UBL_EINVAL != -1 || UBL_ELAUNCH != -2;\n}\n')
-    r = subprocess.run([_cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(proto)],
+    r = subprocess.run([cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(proto)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
 
@@ -63,7 +51,7 @@ def test_header_binding_reference_and_library_agree():
     raw = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
     declared = set(re.findall(r"\b(ubl_[a-z_0-9]+)\s*\(", text))
-    _need_lib()
+    need_lib(LIB)
     assert declared == set(K.SYMBOLS) and len(K.SYMBOLS) == len(set(K.SYMBOLS)) == 4
     num = {k: int(v) for k, v in re.findall(r"#define\s+UBL_([A-Z_]+)\s+\(?(-?\d+)\)?\s", text)}
     assert dict(BLOCK=num["BLOCK"], UNROLL=num["UNROLL"], MAX_GRID=num["MAX_GRID"]) == dict(BLOCK=K.BLOCK, UNROLL=K.UNROLL, MAX_GRID=K.MAX_GRID)
@@ -78,19 +66,6 @@ def test_header_binding_reference_and_library_agree():
     # the arithmetic and the contracts are stated in the header
     for phrase in ("expm1f", "exp2f(gamma * log2f(q))", "contracted", "NaN", "nll_bwd_kernel", "denom == 0", "bit for bit", "no atomic"):
         assert phrase in raw, phrase
-    lib = K.lib()
-    assert all(hasattr(lib, s) for s in K.SYMBOLS)
-    assert lib.ubl_version() == 1
-    # the exports with the library's prefix are exactly the declared ones, and none has another library's prefix
-    syms = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--dyn-syms", "-W", LIB], capture_output=True, text=True, check=True).stdout
-    defined = [l.split()[-1] for l in syms.split("\n") if len(l.split()) == 8 and l.split()[6] != "UND"]
-    assert set(n for n in defined if n.startswith("ubl_")) == set(K.SYMBOLS)
-    assert not [n for n in defined if re.match(r"ub[rpdaowgecs]_", n)], "a symbol of another library"
-    # the eleventh library stands alone: it links against none of the others
-    dyn = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "-d", LIB], capture_output=True, text=True, check=True).stdout
-    for other in ("libubresnet_hip", "libubresnet_post", "libubresnet_data", "libubresnet_aug", "libubresnet_opt", "libubresnet_weight",
-                  "libubresnet_group", "libubresnet_ema", "libubresnet_accum", "libubresnet_stats"):
-        assert other not in dyn
     # five kernels: both forms of the two streaming passes, and the finish
     assert sorted(kernel_symbols.kernels(LIB)) == ["focal_bwd_kernel<false>", "focal_bwd_kernel<true>", "focal_finish_kernel",
                                                    "focal_fwd_kernel<false>", "focal_fwd_kernel<true>"]
@@ -110,67 +85,6 @@ def test_read_ctl_unpacks_the_words():
     c = K.read_ctl(words.tobytes())
     assert (c["loss_sum"], c["weight_sum"], c["valid"], c["bad"], c["denom"], c["inv_denom"], c["loss"], c["mode"]) == (1.5, 2.5, 7, 3, 7.0, 0.25, 0.75, 1)
     assert c["class_loss"][2] == 4.0 and c["class_pixels"][15] == 9 and len(c["class_loss"]) == len(c["class_pixels"]) == 16
-
-
-def test_build_covers_the_eleventh_library_and_build_is_unchanged():
-    assert B.LOSS_SOURCES == ["ubr_loss.hip"]
-    others = (B.SOURCES + B.POST_SOURCES + B.DATA_SOURCES + B.AUG_SOURCES + B.OPT_SOURCES + B.WEIGHT_SOURCES + B.GROUP_SOURCES + B.EMA_SOURCES
-              + B.ACCUM_SOURCES + B.STATS_SOURCES)
-    assert "ubr_loss.hip" not in others
-    assert os.path.basename(B.LOSS_OUT) == "libubresnet_loss.so"
-    assert not any("loss" in h for h in B.HEADERS + B.POST_HEADERS + B.DATA_HEADERS + B.AUG_HEADERS + B.OPT_HEADERS + B.WEIGHT_HEADERS
-                   + B.GROUP_HEADERS + B.EMA_HEADERS + B.ACCUM_HEADERS + B.STATS_HEADERS)
-    assert any("ubresnet_loss.h" in h for h in B.LOSS_HEADERS) and "ubr_loss_term.h" in B.LOSS_HEADERS
-    assert "-ffp-contract=off" in B.FLAGS and "--offload-arch=gfx950" in B.FLAGS
-    # the new file names carry none of the substrings by which the tests of the other libraries pick out their own commands
-    for name in ("ubr_loss.hip", "ubr_loss_term.h", "ubresnet_loss.h", "libubresnet_loss.so", "_loss.py"):
-        assert not any(s in name for s in ("stats", "accum", "ema", "group", "opt", "weight", "aug", "data", "post")), name
-    lines = []
-    old = subprocess.run
-
-    def fake(cmd, **kw):
-        lines.append(cmd)
-        return old(["true"], **kw)
-    subprocess.run = fake
-    try:
-        assert B.build_loss(force=True, verbose=False) == B.LOSS_OUT
-        only = list(lines)
-        del lines[:]
-        B.build(force=True, verbose=False)
-        rest = list(lines)
-    finally:
-        subprocess.run = old
-    assert len(only) == 2, only                                    # build_loss() compiles and links this library and nothing else
-    compile_, link = only
-    assert all(f in compile_ for f in B.FLAGS) and compile_[-3].endswith("ubr_loss.hip"), "compiled with the shared FLAGS"
-    assert link[-1].endswith("ubr_loss.o") and B.LOSS_OUT in link and sum(a.endswith(".o") for a in link) == 1, "links nothing else"
-    assert sum(1 for c in rest if "-shared" in c) == 9 and not any("ubr_loss" in a or "libubresnet_loss" in a for c in rest for a in c), \
-        "build() is the nine libraries it was"
-    entry = open(os.path.join(REPO, "__graft_entry__.py")).read()
-    assert "_loss.SYMBOLS" in entry and "ubl_version" in entry and "b.build_loss(" in entry
-    main = open(os.path.join(REPO, "ubresnet_amd", "build.py")).read().split('if __name__ == "__main__":')[1]
-    assert "build(" in main and "build_stats(" in main and "build_loss(" in main, "the command line builds all eleven"
-    assert not any("loss" in f for f in B.SOURCES + B.HEADERS)       # source_hash() covers the network's kernels only
-
-
-def test_loss_binding_does_not_import_torch_and_has_no_fallback():
-    tree = ast.parse(open(os.path.join(REPO, "ubresnet_amd", "_loss.py")).read())
-    names = [a.name for n in ast.walk(tree) if isinstance(n, ast.Import) for a in n.names]
-    names += [n.module for n in ast.walk(tree) if isinstance(n, ast.ImportFrom)]
-    assert "torch" not in [str(n).split(".")[0] for n in names]
-    import importlib.util
-    old = os.environ.get("UBL_LIB")
-    os.environ["UBL_LIB"] = os.path.join(REPO, "no_such_dir", "libubresnet_loss.so")
-    try:
-        fresh = importlib.util.module_from_spec(importlib.util.spec_from_file_location("_loss_missing", os.path.join(REPO, "ubresnet_amd", "_loss.py")))
-        fresh.__spec__.loader.exec_module(fresh)
-        with pytest.raises(RuntimeError, match="is missing"):
-            fresh.lib()
-    finally:
-        if old is None:
-            del os.environ["UBL_LIB"]
-        else:
-            os.environ["UBL_LIB"] = old
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -233,7 +147,7 @@ _ENTRY = dict(fwd="ubl_focal_fwd", bwd="ubl_focal_bwd")
 
 @pytest.mark.parametrize("name", sorted(_BAD))
 def test_argument_refusals_precede_any_launch(name):
-    _need_lib()
+    need_lib(LIB)
     which, change, message = _BAD[name]
     a = dict(_A)
     a.update(change)
@@ -353,7 +267,7 @@ def test_arithmetic_as_a_program_under_the_host_sanitizers(tmp_path):
     +1e-3, NaN} and four ordinary values, gamma over {0, 0.01, 0.5, 1, 2, 5}: q, m, term, d and g against loss_ref within its
     bound; then the finish rule, bit for bit"""
     exe = str(tmp_path / "loss_host")
-    r = subprocess.run([_cc(plus=True), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
+    r = subprocess.run([cc(plus=True), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
                         "-Wall", "-Werror", "-I", os.path.join(REPO, "ubresnet_amd", "csrc"), os.path.join(REPO, "tests", "loss_host.cpp"), "-o", exe],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr

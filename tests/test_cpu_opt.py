@@ -1,9 +1,7 @@
 """The guarded optimizer step without a GPU: libubresnet_opt.so's header is C99; header, binding and library agree on the entry
-points and on the control block; the library stands alone; build.py and the entry point cover it and source_hash() does not; the
-kernels compiled into it are exactly the ones the case table of tests/test_gpu_opt_exact.py claims; the bias-correction table
-against kref.adam_ref's rounded corrections; opt_ref's decision rule by hand; every argument refusal returns its error before
-any launch."""
-import ast
+points and on the control block; the kernels compiled into it are exactly the ones the case table of tests/test_gpu_opt_exact.py
+claims; the bias-correction table against kref.adam_ref's rounded corrections; opt_ref's decision rule by hand; every argument
+refusal returns its error before any launch."""
 import ctypes as C
 import math
 import os
@@ -22,20 +20,11 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "ubresnet_opt.h")
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import kernel_symbols  # noqa: E402
+from cpu_helpers import cc, need_lib, case_ids_run_by_the_gpu_module  # noqa: E402
 from ubresnet_amd import _opt  # noqa: E402
 from ubresnet_amd import build as B  # noqa: E402
 
-LIB = getattr(B, "OPT_OUT", None)
-
-
-def _need_lib():
-    # (the library is a build product: __graft_entry__.build() makes it; a tree that was never built has nothing to inspect)
-    assert LIB and os.path.exists(LIB), "libubresnet_opt.so is not built (python -m ubresnet_amd.build)"
-
-
-def _cc():
-    cc = "/opt/rocm/lib/llvm/bin/clang"
-    return cc if os.path.exists(cc) else "cc"
+LIB = B.LIBS["opt"].out
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -50,7 +39,7 @@ def test_header_compiles_as_c99(tmp_path):
                    '  int (*s)(float*, const float*, float*, int64_t, float, float, float, float, int, const void*, void*) = ubo_sgd_step;\n'
                    '  int (*i)(void*, int64_t, void*) = ubo_ctl_init;\n'
                    '  return n == 0 || a == 0 || s == 0 || i == 0 || UBO_OK != 0 || sizeof(ubo_ctl) != UBO_CTL_HEAD_BYTES;\n}\n')
-    r = subprocess.run([_cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(src)],
+    r = subprocess.run([cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(src)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
 
@@ -65,20 +54,7 @@ def test_header_binding_and_library_agree():
     assert geometry == dict(BLOCK=R.BLOCK, UNROLL=R.UNROLL, MAX_GRID=R.MAX_GRID, CTL_HEAD_BYTES=R.CTL_HEAD_BYTES)
     assert re.search(r"#define\s+UBO_CTL_BYTES\s+\(UBO_CTL_HEAD_BYTES \+ 8 \* UBO_MAX_GRID\)", text)
     assert _opt.CTL_BYTES == R.CTL_BYTES == geometry["CTL_HEAD_BYTES"] + 8 * geometry["MAX_GRID"]
-    _need_lib()
-    lib = _opt.lib()
-    assert all(hasattr(lib, s) for s in _opt.SYMBOLS)
-    assert lib.ubo_version() == 1
-    llvm = "/opt/rocm/lib/llvm/bin"
-    # the exports with the library's prefix are exactly the declared ones
-    syms = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--dyn-syms", "-W", LIB], capture_output=True, text=True, check=True).stdout
-    defined = [l.split()[-1] for l in syms.split("\n") if len(l.split()) == 8 and l.split()[6] != "UND"]
-    assert set(n for n in defined if n.startswith("ubo_")) == set(_opt.SYMBOLS)
-    assert not [n for n in defined if re.match(r"ub[rpda]_", n)], "a symbol of another library"
-    # the fifth library stands alone: it links against none of the others
-    dyn = subprocess.run([os.path.join(llvm, "llvm-readelf"), "-d", LIB], capture_output=True, text=True, check=True).stdout
-    for other in ("libubresnet_hip", "libubresnet_post", "libubresnet_data", "libubresnet_aug"):
-        assert other not in dyn
+    need_lib(LIB)
 
 
 def test_control_block_matches_the_header(tmp_path):
@@ -92,7 +68,7 @@ def test_control_block_matches_the_header(tmp_path):
     src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "ubresnet_opt.h"\nint main(void) {\n' +
                    "".join('  printf("%s %%d\\n", (int)offsetof(ubo_ctl, %s));\n' % (n, n) for n in mine) +
                    '  printf("size %d\\nbytes %d\\n", (int)sizeof(ubo_ctl), (int)UBO_CTL_BYTES);\n  return 0;\n}\n')
-    r = subprocess.run([_cc(), "-std=c99", "-I", os.path.dirname(HEADER), str(src), "-o", str(exe)], capture_output=True, text=True)
+    r = subprocess.run([cc(), "-std=c99", "-I", os.path.dirname(HEADER), str(src), "-o", str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     out = dict(l.split() for l in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.strip().split("\n"))
     assert {k: int(v) for k, v in out.items()} == dict(mine, size=80, bytes=_opt.CTL_BYTES)
@@ -102,65 +78,14 @@ def test_control_block_matches_the_header(tmp_path):
     assert h.apply == int.from_bytes(bytes(range(20, 24)), "little") and h.skipped == int.from_bytes(bytes(range(48, 56)), "little")
 
 
-def test_build_covers_the_fifth_library_and_the_hash_only_the_network():
-    assert B.OPT_SOURCES == ["ubr_opt.hip"] and "ubr_opt.hip" not in B.SOURCES + B.POST_SOURCES + B.DATA_SOURCES + B.AUG_SOURCES
-    assert os.path.basename(B.OPT_OUT) == "libubresnet_opt.so"
-    assert not any("opt" in h for h in B.HEADERS + B.POST_HEADERS + B.DATA_HEADERS + B.AUG_HEADERS)
-    assert any("ubresnet_opt.h" in h for h in B.OPT_HEADERS)
-    entry = open(os.path.join(REPO, "__graft_entry__.py")).read()
-    assert "_opt.SYMBOLS" in entry
-    # source_hash() reads SOURCES and HEADERS only: a hash over those files by hand is the same
-    import hashlib
-    h = hashlib.sha256()
-    for f in sorted(B.SOURCES) + sorted(B.HEADERS):
-        with open(os.path.join(B.CSRC, f), "rb") as fh:
-            h.update(f.encode() + b"\0" + fh.read())
-    assert B.source_hash() == h.hexdigest()
-
-
-def test_opt_binding_does_not_import_torch():
-    tree = ast.parse(open(os.path.join(REPO, "ubresnet_amd", "_opt.py")).read())
-    names = [a.name for n in ast.walk(tree) if isinstance(n, ast.Import) for a in n.names]
-    names += [n.module for n in ast.walk(tree) if isinstance(n, ast.ImportFrom)]
-    assert "torch" not in [str(n).split(".")[0] for n in names]
-    # and no fallback: a library that is not there is an error
-    import importlib.util
-    old = os.environ.get("UBO_LIB")
-    os.environ["UBO_LIB"] = os.path.join(REPO, "no_such_dir", "libubresnet_opt.so")
-    try:
-        fresh = importlib.util.module_from_spec(importlib.util.spec_from_file_location("_opt_missing", os.path.join(REPO, "ubresnet_amd", "_opt.py")))
-        fresh.__spec__.loader.exec_module(fresh)
-        with pytest.raises(RuntimeError, match="is missing"):
-            fresh.lib()
-    finally:
-        if old is None:
-            del os.environ["UBO_LIB"]
-        else:
-            os.environ["UBO_LIB"] = old
-
-
-def _case_ids_run_by_the_gpu_module():
-    """the literal ids that the test functions of tests/test_gpu_opt_exact.py pass to _case()"""
-    tree = ast.parse(open(os.path.join(REPO, "tests", "test_gpu_opt_exact.py")).read())
-    assert any(isinstance(n, ast.Assign) and ast.unparse(n) == "CASES = R.KERNEL_CASES" for n in tree.body)
-    ran = set()
-    for fn in tree.body:
-        if isinstance(fn, ast.FunctionDef) and fn.name.startswith("test_"):
-            for call in ast.walk(fn):
-                if isinstance(call, ast.Call) and isinstance(call.func, ast.Name) and call.func.id == "_case":
-                    assert isinstance(call.args[0], ast.Constant), "cannot tell the case id of %s" % ast.unparse(call)
-                    ran.add(call.args[0].value)
-    return ran
-
-
 def test_case_table_equals_the_compiled_kernels():
-    _need_lib()
+    need_lib(LIB)
     have = set(kernel_symbols.kernels(LIB))
     claimed = set(R.KERNEL_CASES)
     assert have - claimed == set(), "compiled kernels without a case in tests/test_gpu_opt_exact.py: %s" % sorted(have - claimed)
     assert claimed - have == set(), "cases for kernels that are not compiled: %s" % sorted(claimed - have)
     assert len(have) == 5
-    assert _case_ids_run_by_the_gpu_module() == set(i for ids in R.KERNEL_CASES.values() for i in ids)
+    assert case_ids_run_by_the_gpu_module(os.path.join(REPO, "tests", "test_gpu_opt_exact.py"), call="_case") == set(i for ids in R.KERNEL_CASES.values() for i in ids)
     assert all(ids for ids in R.KERNEL_CASES.values())
 
 
@@ -294,7 +219,7 @@ _ENTRY = dict(norm="ubo_grad_norm", adam="ubo_adam_step", sgd="ubo_sgd_step", in
 
 @pytest.mark.parametrize("name", sorted(_BAD))
 def test_argument_refusals_precede_any_launch(name):
-    _need_lib()
+    need_lib(LIB)
     which, change, message = _BAD[name]
     a = dict(_G, applied=0)
     a.update(change)

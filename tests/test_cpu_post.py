@@ -16,25 +16,18 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "ubresnet_post.h")
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import kernel_symbols  # noqa: E402
+from cpu_helpers import cc, need_lib, case_ids_run_by_the_gpu_module  # noqa: E402
 from ubresnet_amd import _post  # noqa: E402
 from ubresnet_amd import build as B  # noqa: E402
 from ubresnet_amd import deploy  # noqa: E402
 
-LIB = B.POST_OUT
-
-
-def _need_lib():
-    # (the library is a build product: __graft_entry__.build() makes it; a tree that was never built has nothing to inspect)
-    assert os.path.exists(LIB), "libubresnet_post.so is not built (python -m ubresnet_amd.build)"
+LIB = B.LIBS["post"].out
 
 
 def test_header_compiles_as_c99(tmp_path):
     src = tmp_path / "t.c"
     src.write_text('#include "ubresnet_post.h"\nint main(void) { int (*f)(const float*, int, int, int, const int32_t*, int, const float*, int, float, uint8_t*, uint16_t*, unsigned long long*, int, int, int, int, void*) = ubp_stitch_products; return f == 0 || UBP_MAX_TILES != 64 || UBP_OK != 0; }\n')
-    cc = "/opt/rocm/lib/llvm/bin/clang"
-    if not os.path.exists(cc):
-        cc = "cc"
-    r = subprocess.run([cc, "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(src)],
+    r = subprocess.run([cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(src)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
 
@@ -43,64 +36,18 @@ def test_header_binding_and_library_agree():
     text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     declared = set(re.findall(r"\b(ubp_[a-z_0-9]+)\s*\(", text))
     assert declared == set(_post.SYMBOLS) and len(_post.SYMBOLS) == len(set(_post.SYMBOLS))
-    _need_lib()
-    lib = _post.lib()
-    assert all(hasattr(lib, s) for s in _post.SYMBOLS)
-    assert lib.ubp_version() == 1 and lib.ubp_last_error() == b""
-    # the second library stands alone: it does not link against the first
-    dyn = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "-d", LIB], capture_output=True, text=True, check=True).stdout
-    assert "libubresnet_hip" not in dyn
-
-
-def test_build_covers_both_libraries_and_the_hash_only_the_network():
-    assert B.POST_SOURCES == ["ubr_post.hip"] and "ubr_post.hip" not in B.SOURCES
-    assert os.path.basename(B.OUT) == "libubresnet_hip.so" and os.path.basename(B.POST_OUT) == "libubresnet_post.so"
-    assert not any("post" in h for h in B.HEADERS)          # source_hash() walks SOURCES + HEADERS: measurement stamps stay valid
-    patterns = open(os.path.join(REPO, ".gitignore")).read().split()
-    assert "*.so" in patterns and "*.o" in patterns          # the new build products stay out of git as the old ones do
+    need_lib(LIB)
+    assert _post.lib().ubp_last_error() == b""
 
 
 def test_case_table_equals_the_compiled_kernels():
-    _need_lib()
+    need_lib(LIB)
     have = set(kernel_symbols.kernels(LIB))
     claimed = set(R.KERNEL_CASES)
     assert have - claimed == set(), "compiled kernels without a case in tests/test_gpu_post_exact.py: %s" % sorted(have - claimed)
     assert claimed - have == set(), "cases for kernels that are not compiled: %s" % sorted(claimed - have)
-    assert _case_ids_run_by_the_gpu_module() == set(i for ids in R.KERNEL_CASES.values() for i in ids)
+    assert case_ids_run_by_the_gpu_module(os.path.join(REPO, "tests", "test_gpu_post_exact.py")) == set(i for ids in R.KERNEL_CASES.values() for i in ids)
     assert all(ids for ids in R.KERNEL_CASES.values())
-
-
-def _case_ids_run_by_the_gpu_module():
-    """the ids that the test functions of tests/test_gpu_post_exact.py pass to _run(), from its syntax tree (text in comments or
-    strings elsewhere does not count): a literal first argument, or a parameter whose values the parametrize decorator lists"""
-    import ast
-    tree = ast.parse(open(os.path.join(REPO, "tests", "test_gpu_post_exact.py")).read())
-    assert any(isinstance(n, ast.Assign) and ast.unparse(n) == "CASES = R.KERNEL_CASES" for n in tree.body)
-    ran = set()
-    for fn in tree.body:
-        if not (isinstance(fn, ast.FunctionDef) and fn.name.startswith("test_")):
-            continue
-        params = {}
-        for d in fn.decorator_list:
-            if isinstance(d, ast.Call) and ast.unparse(d.func).endswith("parametrize"):
-                try:
-                    names, values = ast.literal_eval(d.args[0]), ast.literal_eval(d.args[1])
-                except ValueError:         # computed values (the argument-error names): no case ids there
-                    continue
-                names = [n.strip() for n in names.split(",")] if isinstance(names, str) else list(names)
-                for row in values:
-                    row = row if len(names) > 1 else (row,)
-                    for n, v in zip(names, row):
-                        params.setdefault(n, []).append(v)
-        for call in ast.walk(fn):
-            if isinstance(call, ast.Call) and isinstance(call.func, ast.Name) and call.func.id == "_run":
-                a = call.args[0]
-                if isinstance(a, ast.Constant):
-                    ran.add(a.value)
-                else:
-                    assert isinstance(a, ast.Name) and a.id in params, "cannot tell the case id of %s" % ast.unparse(call)
-                    ran.update(params[a.id])
-    return ran
 
 
 def test_edge_rows_of_the_reference():

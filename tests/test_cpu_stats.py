@@ -1,9 +1,7 @@
-"""The running-statistics guard without a GPU: libubresnet_stats.so's header is C99; header, binding, reference and library agree
-on the entry points, the geometry, the control block and the row; the library stands alone; build.py and the entry point cover
-it and source_hash() does not; every argument refusal returns UBS_EINVAL with a message before any launch; the decision rule (a
-host/device inline function) as a stand-alone program under the host sanitizers against stats_ref over its whole truth table;
-the table builder on a CPU stand-in model; StatsGuard's own refusals; the wiring into the epoch loop."""
-import ast
+"""The running-statistics guard without a GPU: libubresnet_stats.so's header is C99; header, binding, reference and library agree on
+the entry points, the geometry, the control block and the row; every argument refusal returns UBS_EINVAL with a message before any
+launch; the decision rule (a host/device inline function) as a stand-alone program under the host sanitizers against stats_ref
+over its whole truth table; the table builder on a CPU stand-in model; StatsGuard's own refusals; the wiring into the epoch loop."""
 import ctypes as C
 import itertools
 import os
@@ -21,21 +19,11 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "ubresnet_stats.h")
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import kernel_symbols  # noqa: E402
+from cpu_helpers import cc, need_lib  # noqa: E402
 from ubresnet_amd import _stats as S  # noqa: E402
 from ubresnet_amd import build as B  # noqa: E402
 
-LIB = B.STATS_OUT
-LLVM = "/opt/rocm/lib/llvm/bin"
-
-
-def _need_lib():
-    # (the library is a build product: __graft_entry__.build() makes it; a tree that was never built has nothing to inspect)
-    assert os.path.exists(LIB), "libubresnet_stats.so is not built (python -m ubresnet_amd.build)"
-
-
-def _cc(plus=False):
-    cc = os.path.join(LLVM, "clang++" if plus else "clang")
-    return cc if os.path.exists(cc) else ("c++" if plus else "cc")
+LIB = B.LIBS["stats"].out
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -51,7 +39,7 @@ def test_header_compiles_as_c99_and_fixes_the_layout(tmp_path):
                      '  int (*d)(void*, const int32_t*, int64_t, const int32_t*, int32_t, void*) = ubs_decide;\n'
                      '  int (*r)(const void*, int64_t, const void*, void*) = ubs_resolve;\n'
                      '  return i == 0 || s == 0 || n == 0 || d == 0 || r == 0 || UBS_OK != 0 || UBS_EINVAL != -1;\n}\n')
-    r = subprocess.run([_cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(proto)],
+    r = subprocess.run([cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(proto)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "ubresnet_stats.h"\n'
@@ -62,7 +50,7 @@ def test_header_compiles_as_c99_and_fixes_the_layout(tmp_path):
                    '         (int)offsetof(ubs_seg, count), (int)offsetof(ubs_seg, kind));\n'
                    '  printf("kind %d %d\\n", UBS_KIND_F32, UBS_KIND_RAW);\n'
                    '  return 0;\n}\n')
-    r = subprocess.run([_cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.dirname(HEADER), str(src), "-o", str(exe)],
+    r = subprocess.run([cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.dirname(HEADER), str(src), "-o", str(exe)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     out = {l.split()[0]: [int(x) for x in l.split()[1:]] for l in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.strip().split("\n")}
@@ -87,88 +75,14 @@ def test_header_binding_and_library_agree():
     raw = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
     declared = set(re.findall(r"\b(ubs_[a-z_0-9]+)\s*\(", text))
-    _need_lib()
+    need_lib(LIB)
     assert declared == set(S.SYMBOLS) and len(S.SYMBOLS) == len(set(S.SYMBOLS))
     geometry = {k: int(v) for k, v in re.findall(r"#define\s+UBS_(BLOCK|SEG_GRID|CTL_BYTES)\s+(\d+)", text)}
     assert geometry == dict(BLOCK=S.BLOCK, SEG_GRID=S.SEG_GRID, CTL_BYTES=S.CTL_BYTES)
     assert geometry == dict(BLOCK=R.BLOCK, SEG_GRID=R.SEG_GRID, CTL_BYTES=R.CTL_BYTES)
-    lib = S.lib()
-    assert all(hasattr(lib, s) for s in S.SYMBOLS)
-    assert lib.ubs_version() == 1
-    # the exports with the library's prefix are exactly the declared ones, and none has another library's prefix
-    syms = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--dyn-syms", "-W", LIB], capture_output=True, text=True, check=True).stdout
-    defined = [l.split()[-1] for l in syms.split("\n") if len(l.split()) == 8 and l.split()[6] != "UND"]
-    assert set(n for n in defined if n.startswith("ubs_")) == set(S.SYMBOLS)
-    assert not [n for n in defined if re.match(r"ub[rpdaowgec]_", n)], "a symbol of another library"
-    # the tenth library stands alone: it links against none of the others
-    dyn = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "-d", LIB], capture_output=True, text=True, check=True).stdout
-    for other in ("libubresnet_hip", "libubresnet_post", "libubresnet_data", "libubresnet_aug", "libubresnet_opt", "libubresnet_weight",
-                  "libubresnet_group", "libubresnet_ema", "libubresnet_accum"):
-        assert other not in dyn
     # five kernels
     assert sorted(k.split("(")[0].split("::")[-1] for k in kernel_symbols.kernels(LIB)) == [
         "ctl_init_kernel", "decide_kernel", "note_kernel", "resolve_kernel", "scan_kernel"]
-
-
-def test_build_covers_the_tenth_library_and_the_hash_only_the_network():
-    assert B.STATS_SOURCES == ["ubr_stats.hip"]
-    others = (B.SOURCES + B.POST_SOURCES + B.DATA_SOURCES + B.AUG_SOURCES + B.OPT_SOURCES + B.WEIGHT_SOURCES + B.GROUP_SOURCES + B.EMA_SOURCES
-              + B.ACCUM_SOURCES)
-    assert "ubr_stats.hip" not in others
-    assert os.path.basename(B.STATS_OUT) == "libubresnet_stats.so"
-    assert not any("stats" in h for h in B.HEADERS + B.POST_HEADERS + B.DATA_HEADERS + B.AUG_HEADERS + B.OPT_HEADERS + B.WEIGHT_HEADERS
-                   + B.GROUP_HEADERS + B.EMA_HEADERS + B.ACCUM_HEADERS)
-    assert any("ubresnet_stats.h" in h for h in B.STATS_HEADERS) and "ubr_stats_decide.h" in B.STATS_HEADERS
-    assert "-ffp-contract=off" in B.FLAGS and "--offload-arch=gfx950" in B.FLAGS
-    lines = []
-    old = subprocess.run
-
-    def fake(cmd, **kw):
-        lines.append(cmd)
-        return old(["true"], **kw)
-    subprocess.run = fake
-    try:
-        assert B.build_stats(force=True, verbose=False) == B.STATS_OUT
-        only = list(lines)
-        B.build(force=True, verbose=False)
-    finally:
-        subprocess.run = old
-    mine = [c for c in lines if any("ubr_stats" in a or "libubresnet_stats" in a for a in c)]
-    assert len(mine) == 2 and mine == only, mine                   # build_stats() compiles and links this library and nothing else
-    compile_, link = mine
-    assert all(f in compile_ for f in B.FLAGS), "the statistics library is compiled with the shared FLAGS"
-    assert link[-1].endswith("ubr_stats.o") and B.STATS_OUT in link and sum(a.endswith(".o") for a in link) == 1, "links nothing else"
-    entry = open(os.path.join(REPO, "__graft_entry__.py")).read()
-    assert "_stats.SYMBOLS" in entry and "ubs_version" in entry and "b.build_stats(" in entry
-    main = open(os.path.join(REPO, "ubresnet_amd", "build.py")).read().split('if __name__ == "__main__":')[1]
-    assert "build(" in main and "build_stats(" in main, "the command line builds all ten"
-    import hashlib
-    h = hashlib.sha256()
-    for f in sorted(B.SOURCES) + sorted(B.HEADERS):
-        with open(os.path.join(B.CSRC, f), "rb") as fh:
-            h.update(f.encode() + b"\0" + fh.read())
-    assert B.source_hash() == h.hexdigest()
-    assert not any("stats" in f for f in B.SOURCES + B.HEADERS)
-
-
-def test_stats_binding_does_not_import_torch_and_has_no_fallback():
-    tree = ast.parse(open(os.path.join(REPO, "ubresnet_amd", "_stats.py")).read())
-    names = [a.name for n in ast.walk(tree) if isinstance(n, ast.Import) for a in n.names]
-    names += [n.module for n in ast.walk(tree) if isinstance(n, ast.ImportFrom)]
-    assert "torch" not in [str(n).split(".")[0] for n in names]
-    import importlib.util
-    old = os.environ.get("UBS_LIB")
-    os.environ["UBS_LIB"] = os.path.join(REPO, "no_such_dir", "libubresnet_stats.so")
-    try:
-        fresh = importlib.util.module_from_spec(importlib.util.spec_from_file_location("_stats_missing", os.path.join(REPO, "ubresnet_amd", "_stats.py")))
-        fresh.__spec__.loader.exec_module(fresh)
-        with pytest.raises(RuntimeError, match="is missing"):
-            fresh.lib()
-    finally:
-        if old is None:
-            del os.environ["UBS_LIB"]
-        else:
-            os.environ["UBS_LIB"] = old
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -218,7 +132,7 @@ _ENTRY = dict(init="ubs_ctl_init", scan="ubs_scan", note="ubs_note", decide="ubs
 
 @pytest.mark.parametrize("name", sorted(_BAD))
 def test_argument_refusals_precede_any_launch(name):
-    _need_lib()
+    need_lib(LIB)
     which, change, message = _BAD[name]
     a = dict(_A)
     a.update(change)
@@ -264,7 +178,7 @@ def test_decision_rule_as_a_program_under_the_host_sanitizers(tmp_path):
     process of its own: the full truth table of (flag NULL / 0 / 1) x (check 0 / 1) x (bad_rows 0 / 1 / 3), each alone on a fresh
     block and all in one sequence on one block, against stats_ref"""
     exe = str(tmp_path / "stats_host")
-    r = subprocess.run([_cc(plus=True), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Werror",
+    r = subprocess.run([cc(plus=True), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Werror",
                         "-I", os.path.join(REPO, "ubresnet_amd", "csrc"), os.path.join(REPO, "tests", "stats_host.cpp"), "-o", exe],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr

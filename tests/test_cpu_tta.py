@@ -1,9 +1,7 @@
-"""The test-time-augmentation library without a GPU: libubresnet_tta.so's header is C99; header, binding, reference and library
-agree on the entry points and the geometry; the library stands alone; build.py and the entry point cover it and source_hash()
-does not; the compiled kernels are exactly those the GPU module's case table runs; every argument refusal returns UBT_EINVAL with
-a message before any launch; the numpy reference against numpy.logaddexp and torch.logsumexp, and its edge rules; the refusals of
-WholeViewSegmenter and segment_crops that need no device."""
-import ast
+"""The test-time-augmentation library without a GPU: libubresnet_tta.so's header is C99; header, binding, reference and library agree
+on the entry points and the geometry; the compiled kernels are exactly those the GPU module's case table runs; every argument
+refusal returns UBT_EINVAL with a message before any launch; the numpy reference against numpy.logaddexp and torch.logsumexp, and
+its edge rules; the refusals of WholeViewSegmenter and segment_crops that need no device."""
 import inspect
 import os
 import re
@@ -20,22 +18,12 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "ubresnet_tta.h")
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import kernel_symbols  # noqa: E402
+from cpu_helpers import cc, need_lib  # noqa: E402
 from ubresnet_amd import _tta as T  # noqa: E402
 from ubresnet_amd import build as B  # noqa: E402
 
-LIB = B.TTA_OUT
-LLVM = "/opt/rocm/lib/llvm/bin"
+LIB = B.LIBS["tta"].out
 f32 = np.float32
-
-
-def _need_lib():
-    # (the library is a build product: __graft_entry__.build() makes it; a tree that was never built has nothing to inspect)
-    assert os.path.exists(LIB), "libubresnet_tta.so is not built (python -m ubresnet_amd.build)"
-
-
-def _cc():
-    cc = os.path.join(LLVM, "clang")
-    return cc if os.path.exists(cc) else "cc"
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -51,7 +39,7 @@ def test_header_compiles_as_c99(tmp_path):
                      '  int (*v)(void) = ubt_version;\n'
                      '  return f == 0 || m == 0 || e == 0 || v == 0 || UBT_OK != 0 || UBT_EINVAL != -1 || UBT_ELAUNCH != -2\n'
                      '         || UBT_MAX_VIEWS != 4 || UBT_FLIP_ROWS != 1 || UBT_FLIP_COLS != 2;\n}\n')
-    r = subprocess.run([_cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(proto)],
+    r = subprocess.run([cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(proto)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
 
@@ -60,7 +48,7 @@ def test_header_binding_reference_and_library_agree():
     raw = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
     declared = set(re.findall(r"\b(ubt_[a-z_0-9]+)\s*\(", text))
-    _need_lib()
+    need_lib(LIB)
     assert declared == set(T.SYMBOLS) and len(T.SYMBOLS) == len(set(T.SYMBOLS)) == 4
     geometry = {k: int(v) for k, v in re.findall(r"#define\s+UBT_(BLOCK|UNROLL|MAX_GRID|MAX_VIEWS|FLIP_ROWS|FLIP_COLS)\s+(\d+)", text)}
     assert geometry == dict(BLOCK=T.BLOCK, UNROLL=T.UNROLL, MAX_GRID=T.MAX_GRID, MAX_VIEWS=T.MAX_VIEWS, FLIP_ROWS=T.FLIP_ROWS, FLIP_COLS=T.FLIP_COLS)
@@ -69,22 +57,11 @@ def test_header_binding_reference_and_library_agree():
     # the arithmetic rules are stated in the header
     for phrase in ("32-bit patterns", "lae(a, b)", "log1pf(expf(lo - hi))", "(float)M_LN2", "symmetric", "contracted", "subnormals kept", "payload"):
         assert phrase in raw, phrase
-    lib = T.lib()
-    assert all(hasattr(lib, s) for s in T.SYMBOLS)
-    assert lib.ubt_version() == 1
-    # the exports with the library's prefix are exactly the declared ones, and none has another library's prefix
-    syms = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--dyn-syms", "-W", LIB], capture_output=True, text=True, check=True).stdout
-    defined = [l.split()[-1] for l in syms.split("\n") if len(l.split()) == 8 and l.split()[6] != "UND"]
-    assert set(n for n in defined if n.startswith("ubt_")) == set(T.SYMBOLS)
-    assert not [n for n in defined if re.match(r"ub[rpdaowgecslk]_", n)], "a symbol of another library"
-    # the thirteenth library stands alone: it links against none of the others
-    dyn = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "-d", LIB], capture_output=True, text=True, check=True).stdout
-    assert "libubresnet_" not in dyn.replace("libubresnet_tta", ""), dyn
 
 
 def test_the_compiled_kernels_are_the_case_table():
     """no allow-list: every compiled instantiation is launched by a case of test_gpu_tta_exact.py, and the table names nothing else"""
-    _need_lib()
+    need_lib(LIB)
     compiled = kernel_symbols.kernels(LIB)
     assert compiled == sorted(R.KERNEL_CASES), (compiled, sorted(R.KERNEL_CASES))
     assert len(compiled) == 16                                       # flip in 0..3 x {scalar, vector} x {copy, merge}
@@ -110,65 +87,6 @@ def test_the_shapes_cover_the_paths_of_the_launch():
         fl = R.view_flips(K, first)
         assert len(set(fl)) == K and fl[0] == first                                    # a different flip per view
     assert sorted(set(K for K, _ in R.MERGE_CASES)) == [1, 2, 3, 4] == sorted(K for K, _ in R.merge_cases("second-trip"))
-
-
-def test_build_covers_the_thirteenth_library_and_the_hash_only_the_network():
-    assert B.TTA_SOURCES == ["ubr_tta.hip"]
-    others = (B.SOURCES + B.POST_SOURCES + B.DATA_SOURCES + B.AUG_SOURCES + B.OPT_SOURCES + B.WEIGHT_SOURCES + B.GROUP_SOURCES
-              + B.EMA_SOURCES + B.ACCUM_SOURCES + B.STATS_SOURCES + B.LOSS_SOURCES + B.DICE_SOURCES)
-    assert "ubr_tta.hip" not in others
-    assert os.path.basename(B.TTA_OUT) == "libubresnet_tta.so"
-    assert not any("tta" in h for h in B.HEADERS + B.POST_HEADERS + B.DATA_HEADERS + B.AUG_HEADERS + B.OPT_HEADERS + B.WEIGHT_HEADERS
-                   + B.GROUP_HEADERS + B.EMA_HEADERS + B.ACCUM_HEADERS + B.STATS_HEADERS + B.LOSS_HEADERS + B.DICE_HEADERS)
-    assert any("ubresnet_tta.h" in h for h in B.TTA_HEADERS)
-    assert "-ffp-contract=off" in B.FLAGS and "--offload-arch=gfx950" in B.FLAGS
-    lines = []
-    old = subprocess.run
-
-    def fake(cmd, **kw):
-        lines.append(cmd)
-        return old(["true"], **kw)
-    subprocess.run = fake
-    try:
-        assert B.build_tta(force=True, verbose=False) == B.TTA_OUT
-    finally:
-        subprocess.run = old
-    assert len(lines) == 2, lines
-    compile_, link = lines
-    assert all(f in compile_ for f in B.FLAGS), "the library is compiled with the shared FLAGS"
-    assert compile_[-3].endswith("ubr_tta.hip")
-    assert link[-1].endswith("ubr_tta.o") and B.TTA_OUT in link and sum(a.endswith(".o") for a in link) == 1, "links nothing else"
-    main = open(os.path.join(REPO, "ubresnet_amd", "build.py")).read().split('if __name__ == "__main__":')[1]
-    assert "build_tta(" in main
-    entry = open(os.path.join(REPO, "__graft_entry__.py")).read()
-    assert "b.build_tta(" in entry and "_tta.SYMBOLS" in entry and "ubt_version" in entry
-    import hashlib
-    h = hashlib.sha256()
-    for f in sorted(B.SOURCES) + sorted(B.HEADERS):
-        with open(os.path.join(B.CSRC, f), "rb") as fh:
-            h.update(f.encode() + b"\0" + fh.read())
-    assert B.source_hash() == h.hexdigest()
-    assert not any("tta" in f for f in B.SOURCES + B.HEADERS)
-
-
-def test_tta_binding_does_not_import_torch_and_has_no_fallback():
-    tree = ast.parse(open(os.path.join(REPO, "ubresnet_amd", "_tta.py")).read())
-    names = [a.name for n in ast.walk(tree) if isinstance(n, ast.Import) for a in n.names]
-    names += [n.module for n in ast.walk(tree) if isinstance(n, ast.ImportFrom)]
-    assert "torch" not in [str(n).split(".")[0] for n in names]
-    import importlib.util
-    old = os.environ.get("UBT_LIB")
-    os.environ["UBT_LIB"] = os.path.join(REPO, "no_such_dir", "libubresnet_tta.so")
-    try:
-        fresh = importlib.util.module_from_spec(importlib.util.spec_from_file_location("_tta_missing", os.path.join(REPO, "ubresnet_amd", "_tta.py")))
-        fresh.__spec__.loader.exec_module(fresh)
-        with pytest.raises(RuntimeError, match="is missing"):
-            fresh.lib()
-    finally:
-        if old is None:
-            del os.environ["UBT_LIB"]
-        else:
-            os.environ["UBT_LIB"] = old
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -212,7 +130,7 @@ _ENTRY = dict(flip="ubt_flip_planes", merge="ubt_merge_view")
 
 @pytest.mark.parametrize("name", sorted(_BAD))
 def test_argument_refusals_precede_any_launch(name):
-    _need_lib()
+    need_lib(LIB)
     which, change, message = _BAD[name]
     a = dict(_A)
     a.update(change)

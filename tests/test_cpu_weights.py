@@ -2,7 +2,6 @@
 kernels compiled into it are exactly the ones the case table of tests/test_gpu_weights_exact.py claims, the numpy reference
 those GPU tests compare against follows the rule of include/ubresnet_weight.h on hand-worked examples, every argument refusal
 returns its error before any launch, and PixelWeights / BatchStager refuse bad arguments before any library call."""
-import ast
 import ctypes as C
 import os
 import re
@@ -19,26 +18,19 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "ubresnet_weight.h")
 sys.path.insert(0, os.path.join(REPO, "tools"))
 import kernel_symbols  # noqa: E402
+from cpu_helpers import cc, need_lib, case_ids_run_by_the_gpu_module  # noqa: E402
 from ubresnet_amd import _weight  # noqa: E402
 from ubresnet_amd import build as B  # noqa: E402
 from ubresnet_amd.pixel_weights import PixelWeights  # noqa: E402
 
-LIB = B.WEIGHT_OUT
+LIB = B.LIBS["weight"].out
 INF = float("inf")
-
-
-def _need_lib():
-    # (the library is a build product: __graft_entry__.build() makes it; a tree that was never built has nothing to inspect)
-    assert os.path.exists(LIB), "libubresnet_weight.so is not built (python -m ubresnet_amd.build)"
 
 
 def test_header_compiles_as_c99(tmp_path):
     src = tmp_path / "t.c"
     src.write_text('#include "ubresnet_weight.h"\nint main(void) { int (*f)(const int64_t*, float*, int64_t*, int, int, int, int, float, int, float, int, void*) = ubw_pixel_weights; return f == 0 || UBW_MAX_CLASSES != 16 || UBW_OK != 0; }\n')
-    cc = "/opt/rocm/lib/llvm/bin/clang"
-    if not os.path.exists(cc):
-        cc = "cc"
-    r = subprocess.run([cc, "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(src)],
+    r = subprocess.run([cc(), "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(src)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
 
@@ -56,63 +48,16 @@ def test_header_binding_and_library_agree():
                           BLOCK=_weight.BLOCK, MAX_GRID=_weight.MAX_GRID, TILE_W=_weight.TILE_W, TILE_H=_weight.TILE_H)
     assert consts == dict(MAX_CLASSES=R.MAX_CLASSES, MAX_RADIUS=R.MAX_RADIUS, LANE_PIXELS=R.LANE_PIXELS, BLOCK=R.BLOCK,
                           MAX_GRID=R.MAX_GRID, TILE_W=R.TILE_W, TILE_H=R.TILE_H)
-    _need_lib()
-    lib = _weight.lib()
-    assert all(hasattr(lib, s) for s in _weight.SYMBOLS)
-    assert lib.ubw_version() == 1
-    # the sixth library stands alone: it links against none of the others
-    dyn = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "-d", LIB], capture_output=True, text=True, check=True).stdout
-    assert "libubresnet_" not in dyn.replace("libubresnet_weight", "")
-
-
-def test_build_covers_the_sixth_library_and_the_hash_only_the_network():
-    assert B.WEIGHT_SOURCES == ["ubr_weight.hip"]
-    assert "ubr_weight.hip" not in B.SOURCES + B.POST_SOURCES + B.DATA_SOURCES + B.AUG_SOURCES + B.OPT_SOURCES
-    assert os.path.basename(B.WEIGHT_OUT) == "libubresnet_weight.so" and os.path.dirname(B.WEIGHT_OUT) == os.path.dirname(B.OUT)
-    assert any(h.endswith("ubresnet_weight.h") for h in B.WEIGHT_HEADERS)
-    assert not any("weight" in h for h in B.HEADERS)         # source_hash() walks SOURCES + HEADERS: measurement stamps stay valid
-    assert "-ffp-contract=off" in B.FLAGS
-
-
-def _case_ids_run_by_the_gpu_module():
-    """the ids that the test functions of tests/test_gpu_weights_exact.py pass to _run(), from its syntax tree: a literal first
-    argument, or a parameter whose values the parametrize decorator lists"""
-    tree = ast.parse(open(os.path.join(REPO, "tests", "test_gpu_weights_exact.py")).read())
-    assert any(isinstance(n, ast.Assign) and ast.unparse(n) == "CASES = R.KERNEL_CASES" for n in tree.body)
-    ran = set()
-    for fn in tree.body:
-        if not (isinstance(fn, ast.FunctionDef) and fn.name.startswith("test_")):
-            continue
-        params = {}
-        for d in fn.decorator_list:
-            if isinstance(d, ast.Call) and ast.unparse(d.func).endswith("parametrize"):
-                try:
-                    names, values = ast.literal_eval(d.args[0]), ast.literal_eval(d.args[1])
-                except ValueError:         # computed values (the argument-error names): no case ids there
-                    continue
-                names = [n.strip() for n in names.split(",")] if isinstance(names, str) else list(names)
-                for row in values:
-                    row = row if len(names) > 1 else (row,)
-                    for n, v in zip(names, row):
-                        params.setdefault(n, []).append(v)
-        for call in ast.walk(fn):
-            if isinstance(call, ast.Call) and isinstance(call.func, ast.Name) and call.func.id == "_run":
-                a = call.args[0]
-                if isinstance(a, ast.Constant):
-                    ran.add(a.value)
-                else:
-                    assert isinstance(a, ast.Name) and a.id in params, "cannot tell the case id of %s" % ast.unparse(call)
-                    ran.update(params[a.id])
-    return ran
+    need_lib(LIB)
 
 
 def test_case_table_equals_the_compiled_kernels():
-    _need_lib()
+    need_lib(LIB)
     have = set(kernel_symbols.kernels(LIB))
     claimed = set(R.KERNEL_CASES)
     assert have - claimed == set(), "compiled kernels without a case in tests/test_gpu_weights_exact.py: %s" % sorted(have - claimed)
     assert claimed - have == set(), "cases for kernels that are not compiled: %s" % sorted(claimed - have)
-    assert _case_ids_run_by_the_gpu_module() == set(i for ids in R.KERNEL_CASES.values() for i in ids)
+    assert case_ids_run_by_the_gpu_module(os.path.join(REPO, "tests", "test_gpu_weights_exact.py")) == set(i for ids in R.KERNEL_CASES.values() for i in ids)
     assert all(ids for ids in R.KERNEL_CASES.values())
     assert set(R.KERNEL_CASES) == {"count_kernel"} | {"apply_kernel<%d>" % r for r in range(R.MAX_RADIUS + 1)}
     assert set(R.KERNEL_CASES["count_kernel"]) == set(i for ids in R.KERNEL_CASES.values() for i in ids)     # every call counts
@@ -281,7 +226,7 @@ _BAD = {
 
 @pytest.mark.parametrize("name", sorted(_BAD))
 def test_argument_refusals_precede_any_launch(name):
-    _need_lib()
+    need_lib(LIB)
     a = dict(_GOOD)
     a.update(_BAD[name])
     lib = _weight.lib()

@@ -1,20 +1,16 @@
 """ctypes binding of libubresnet_aug.so (the C ABI in include/ubresnet_aug.h): device-side augmentation of training batches.
 
-A library of its own next to libubresnet_hip.so (ubresnet_amd/_lib.py), libubresnet_post.so (ubresnet_amd/_post.py) and
-libubresnet_data.so (ubresnet_amd/_data.py), with its own error string.  As there, NO fallback: a missing library or a failed
-call is a RuntimeError.  Nothing here imports torch, so the argument checks of the library can be exercised on a machine
+A self-contained library with its own error string, loaded through ubresnet_amd/_binding.py.  NO fallback: a missing library or a
+failed call is a RuntimeError.  Nothing here imports torch, so the argument checks of the library can be exercised on a machine
 without a GPU.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
-import threading
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("UBA_LIB", os.path.join(HERE, "libubresnet_aug.so"))
+from ._binding import Binding
 
 LANE_PIXELS = 4      # UBA_LANE_PIXELS
 BLOCK = 256          # UBA_BLOCK
@@ -22,47 +18,12 @@ MAX_GRID = 1024      # UBA_MAX_GRID
 MAX_BATCH = 256      # UBA_MAX_BATCH
 MAX_PAD = 16383      # UBA_MAX_PAD
 
-# every symbol include/ubresnet_aug.h declares (tests check that all of them are exported)
-SYMBOLS = ["uba_augment_batch", "uba_last_error", "uba_version"]
-
-_lib = None
-_lock = threading.Lock()
 vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
-
-
-def _declare(lib):
-    lib.uba_last_error.restype = C.c_char_p
-    lib.uba_last_error.argtypes = []
-    lib.uba_version.restype = C.c_int
-    lib.uba_version.argtypes = []
-    lib.uba_augment_batch.restype = C.c_int
-    lib.uba_augment_batch.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
-                                      i32, C.c_int, f32, i32, f32, vp]
-
-
-def lib():
-    """Load (once) and return the library; raises RuntimeError if it is not built."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(LIB_PATH):
-                    raise RuntimeError(
-                        "ubresnet_amd: HIP extension %s is missing; build it with "
-                        "`python -m ubresnet_amd.build` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
-                try:
-                    l = C.CDLL(LIB_PATH)
-                except OSError as e:
-                    raise RuntimeError("ubresnet_amd: cannot load %s: %s" % (LIB_PATH, e))
-                _declare(l)
-                _lib = l
-    return _lib
-
-
-def check(rc: int, what: str = ""):
-    if rc != 0:
-        msg = lib().uba_last_error().decode("utf-8", "replace")
-        raise RuntimeError("ubresnet_amd HIP call failed (%d) %s: %s" % (rc, what, msg))
+BINDING = Binding("UBA_LIB", "libubresnet_aug.so", "uba", {
+    "uba_augment_batch": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
+                                    i32, C.c_int, f32, i32, f32, vp]),
+})
+LIB_PATH, SYMBOLS, lib, check = BINDING.path, BINDING.symbols, BINDING.lib, BINDING.check
 
 
 def augment_batch(image: int, label_wire: int, weight, image_out: int, label_out: int, weight_out: int, shape, pad: int,

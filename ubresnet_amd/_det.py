@@ -1,64 +1,26 @@
 """ctypes binding of libubresnet_det.so (the C ABI in include/ubresnet_det.h): detector effects on a prepared training batch.
 
-A library of its own next to libubresnet_aug.so (ubresnet_amd/_aug.py) and the others, with its own error string.  As there, NO
-fallback: a missing library or a failed call is a RuntimeError.  Nothing here imports torch, so the argument checks of the
-library can be exercised on a machine without a GPU.
+A self-contained library with its own error string, loaded through ubresnet_amd/_binding.py.  NO fallback: a missing library or a
+failed call is a RuntimeError.  Nothing here imports torch, so the argument checks of the library can be exercised on a machine
+without a GPU.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
-import threading
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("UBX_LIB", os.path.join(HERE, "libubresnet_det.so"))
+from ._binding import Binding
 
 LANE_PIXELS = 4             # UBX_LANE_PIXELS
 BLOCK = 256                 # UBX_BLOCK
 MAX_GRID = 1024             # UBX_MAX_GRID
 PHILOX_TAG = 0x55425844     # UBX_PHILOX_TAG
 
-# every symbol include/ubresnet_det.h declares (tests check that all of them are exported)
-SYMBOLS = ["ubx_apply", "ubx_last_error", "ubx_version"]
-
-_lib = None
-_lock = threading.Lock()
 vp, u32, i64, f32 = C.c_void_p, C.c_uint32, C.c_int64, C.c_float
-
-
-def _declare(lib):
-    lib.ubx_last_error.restype = C.c_char_p
-    lib.ubx_last_error.argtypes = []
-    lib.ubx_version.restype = C.c_int
-    lib.ubx_version.argtypes = []
-    lib.ubx_apply.restype = C.c_int
-    lib.ubx_apply.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, f32, C.c_int, u32, u32,
-                              C.c_int, i64, C.c_int, f32, vp]
-
-
-def lib():
-    """Load (once) and return the library; raises RuntimeError if it is not built."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(LIB_PATH):
-                    raise RuntimeError(
-                        "ubresnet_amd: HIP extension %s is missing; build it with "
-                        "`python -m ubresnet_amd.build` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
-                try:
-                    l = C.CDLL(LIB_PATH)
-                except OSError as e:
-                    raise RuntimeError("ubresnet_amd: cannot load %s: %s" % (LIB_PATH, e))
-                _declare(l)
-                _lib = l
-    return _lib
-
-
-def check(rc: int, what: str = ""):
-    if rc != 0:
-        msg = lib().ubx_last_error().decode("utf-8", "replace")
-        raise RuntimeError("ubresnet_amd HIP call failed (%d) %s: %s" % (rc, what, msg))
+BINDING = Binding("UBX_LIB", "libubresnet_det.so", "ubx", {
+    "ubx_apply": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, f32, C.c_int, u32, u32,
+                            C.c_int, i64, C.c_int, f32, vp]),
+})
+LIB_PATH, SYMBOLS, lib, check = BINDING.path, BINDING.symbols, BINDING.lib, BINDING.check
 
 
 def row_words(width: int) -> int:

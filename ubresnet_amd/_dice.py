@@ -2,19 +2,16 @@
 -- a streaming pass that leaves one row of per-class partial sums per workgroup, one workgroup that adds them in a fixed order
 into a control block and derives two coefficients per class, and the backward that multiplies with those coefficients.
 
-A library of its own next to the other eleven (ubresnet_amd/_lib.py, _post.py, _data.py, _aug.py, _opt.py, _weight.py, _group.py,
-_ema.py, _accum.py, _stats.py, _loss.py), with its own error string.  As there, NO fallback: a missing library or a failed call is
-a RuntimeError.  Nothing here imports torch, so the argument checks of the library can be exercised on a machine without a GPU.
+A self-contained library with its own error string, loaded through ubresnet_amd/_binding.py.  NO fallback: a missing library or a
+failed call is a RuntimeError.  Nothing here imports torch, so the argument checks of the library can be exercised on a machine
+without a GPU.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
 import struct
-import threading
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("UBK_LIB", os.path.join(HERE, "libubresnet_dice.so"))
+from ._binding import Binding
 
 BLOCK = 256          # UBK_BLOCK
 UNROLL = 2           # UBK_UNROLL
@@ -31,48 +28,12 @@ CTL = dict(TP=0, FP=16, FN=32, PIXELS=48, VALID=64, BAD=65, T=66, K1=82, K0=98, 
 # the words of a workspace row (UBK_ROW_*)
 ROW = dict(TP=0, FP=16, FN=32, PIXELS=48, VALID=64, BAD=65)
 
-# every symbol include/ubresnet_dice.h declares (tests check that all of them are exported)
-SYMBOLS = ["ubk_dice_fwd", "ubk_dice_bwd", "ubk_last_error", "ubk_version"]
-
-_lib = None
-_lock = threading.Lock()
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
-
-
-def _declare(lib):
-    lib.ubk_last_error.restype = C.c_char_p
-    lib.ubk_last_error.argtypes = []
-    lib.ubk_version.restype = C.c_int
-    lib.ubk_version.argtypes = []
-    lib.ubk_dice_fwd.restype = C.c_int
-    lib.ubk_dice_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i64, f32, f32, f32, i32, vp, vp, vp, vp]
-    lib.ubk_dice_bwd.restype = C.c_int
-    lib.ubk_dice_bwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, vp]
-
-
-def lib():
-    """Load (once) and return the library; raises RuntimeError if it is not built."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(LIB_PATH):
-                    raise RuntimeError(
-                        "ubresnet_amd: HIP extension %s is missing; build it with "
-                        "`python -m ubresnet_amd.build` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
-                try:
-                    l = C.CDLL(LIB_PATH)
-                except OSError as e:
-                    raise RuntimeError("ubresnet_amd: cannot load %s: %s" % (LIB_PATH, e))
-                _declare(l)
-                _lib = l
-    return _lib
-
-
-def check(rc: int, what: str = ""):
-    if rc != 0:
-        msg = lib().ubk_last_error().decode("utf-8", "replace")
-        raise RuntimeError("ubresnet_amd HIP call failed (%d) %s: %s" % (rc, what, msg))
+BINDING = Binding("UBK_LIB", "libubresnet_dice.so", "ubk", {
+    "ubk_dice_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i64, f32, f32, f32, i32, vp, vp, vp, vp]),
+    "ubk_dice_bwd": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, vp]),
+})
+LIB_PATH, SYMBOLS, lib, check = BINDING.path, BINDING.symbols, BINDING.lib, BINDING.check
 
 
 def grid(pixels: int) -> int:

@@ -2,20 +2,17 @@
 on the device -- the decision about an update, the streaming update and the in-place exchange over flat buffers, and the same
 two operations over a table of small tensors.
 
-A library of its own next to the other seven (ubresnet_amd/_lib.py, _post.py, _data.py, _aug.py, _opt.py, _weight.py,
-_group.py), with its own error string.  As there, NO fallback: a missing library or a failed call is a RuntimeError.  Nothing
-here imports torch, so the argument checks of the library can be exercised on a machine without a GPU.
+A self-contained library with its own error string, loaded through ubresnet_amd/_binding.py.  NO fallback: a missing library or a
+failed call is a RuntimeError.  Nothing here imports torch, so the argument checks of the library can be exercised on a machine
+without a GPU.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
-import threading
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("UBE_LIB", os.path.join(HERE, "libubresnet_ema.so"))
+from ._binding import Binding
 
 BLOCK = 256          # UBE_BLOCK
 UNROLL = 4           # UBE_UNROLL
@@ -23,9 +20,6 @@ MAX_GRID = 1024      # UBE_MAX_GRID
 SEG_GRID = 256       # UBE_SEG_GRID
 CTL_BYTES = 32       # UBE_CTL_BYTES
 APPLY_OFFSET = 20    # byte offset of `apply` in ubo_ctl and in ubg_ctl: what ube_advance takes as apply_flag
-
-# every symbol include/ubresnet_ema.h declares (tests check that all of them are exported)
-SYMBOLS = ["ube_ctl_init", "ube_advance", "ube_update", "ube_swap", "ube_update_segs", "ube_swap_segs", "ube_last_error", "ube_version"]
 
 # one row of the table of ube_update_segs / ube_swap_segs as a numpy dtype (host copy of the device array)
 SEG = np.dtype([("shadow", "<u8"), ("live", "<u8"), ("count", "<i8"), ("reserved", "<i8")])
@@ -37,53 +31,16 @@ class Ctl(C.Structure):
                 ("held", C.c_int64)]
 
 
-_lib = None
-_lock = threading.Lock()
 vp, i64, f32 = C.c_void_p, C.c_int64, C.c_float
-
-
-def _declare(lib):
-    lib.ube_last_error.restype = C.c_char_p
-    lib.ube_last_error.argtypes = []
-    lib.ube_version.restype = C.c_int
-    lib.ube_version.argtypes = []
-    lib.ube_ctl_init.restype = C.c_int
-    lib.ube_ctl_init.argtypes = [vp, i64, vp]
-    lib.ube_advance.restype = C.c_int
-    lib.ube_advance.argtypes = [vp, vp, f32, i64, vp]
-    lib.ube_update.restype = C.c_int
-    lib.ube_update.argtypes = [vp, vp, i64, vp, vp]
-    lib.ube_swap.restype = C.c_int
-    lib.ube_swap.argtypes = [vp, vp, i64, vp]
-    lib.ube_update_segs.restype = C.c_int
-    lib.ube_update_segs.argtypes = [vp, i64, vp, vp]
-    lib.ube_swap_segs.restype = C.c_int
-    lib.ube_swap_segs.argtypes = [vp, i64, vp]
-
-
-def lib():
-    """Load (once) and return the library; raises RuntimeError if it is not built."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(LIB_PATH):
-                    raise RuntimeError(
-                        "ubresnet_amd: HIP extension %s is missing; build it with "
-                        "`python -m ubresnet_amd.build` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
-                try:
-                    l = C.CDLL(LIB_PATH)
-                except OSError as e:
-                    raise RuntimeError("ubresnet_amd: cannot load %s: %s" % (LIB_PATH, e))
-                _declare(l)
-                _lib = l
-    return _lib
-
-
-def check(rc: int, what: str = ""):
-    if rc != 0:
-        msg = lib().ube_last_error().decode("utf-8", "replace")
-        raise RuntimeError("ubresnet_amd HIP call failed (%d) %s: %s" % (rc, what, msg))
+BINDING = Binding("UBE_LIB", "libubresnet_ema.so", "ube", {
+    "ube_ctl_init": (C.c_int, [vp, i64, vp]),
+    "ube_advance": (C.c_int, [vp, vp, f32, i64, vp]),
+    "ube_update": (C.c_int, [vp, vp, i64, vp, vp]),
+    "ube_swap": (C.c_int, [vp, vp, i64, vp]),
+    "ube_update_segs": (C.c_int, [vp, i64, vp, vp]),
+    "ube_swap_segs": (C.c_int, [vp, i64, vp]),
+})
+LIB_PATH, SYMBOLS, lib, check = BINDING.path, BINDING.symbols, BINDING.lib, BINDING.check
 
 
 def read_ctl(raw: bytes) -> Ctl:

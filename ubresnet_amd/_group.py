@@ -1,20 +1,17 @@
 """ctypes binding of libubresnet_group.so (the C ABI in include/ubresnet_group.h): flat optimizer steps with parameter groups
 and frozen parameters -- per-segment learning rate, weight decay, on/off switch and step count in one launch.
 
-A library of its own next to the other six (ubresnet_amd/_lib.py, _post.py, _data.py, _aug.py, _opt.py, _weight.py), with its
-own error string.  As there, NO fallback: a missing library or a failed call is a RuntimeError.  Nothing here imports torch, so
-the tile planner (pure host code) and the argument checks of the library can be exercised on a machine without a GPU.
+A self-contained library with its own error string, loaded through ubresnet_amd/_binding.py.  NO fallback: a missing library or a
+failed call is a RuntimeError.  Nothing here imports torch, so the tile planner (pure host code) and the argument checks of the
+library can be exercised on a machine without a GPU.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
-import threading
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("UBG_LIB", os.path.join(HERE, "libubresnet_group.so"))
+from ._binding import Binding
 
 BLOCK = 256          # UBG_BLOCK
 TILE_UNITS = 1024    # UBG_TILE_UNITS
@@ -22,10 +19,6 @@ MAX_GRID = 1024      # UBG_MAX_GRID
 STEP_GRID = 2048     # UBG_STEP_GRID
 CTL_HEAD_BYTES = 80  # UBG_CTL_HEAD_BYTES
 CTL_BYTES = CTL_HEAD_BYTES + 8 * MAX_GRID   # UBG_CTL_BYTES
-
-# every symbol include/ubresnet_group.h declares (tests check that all of them are exported)
-SYMBOLS = ["ubg_plan_tiles", "ubg_state_set", "ubg_state_get", "ubg_grad_norm", "ubg_advance", "ubg_adam_step", "ubg_sgd_step",
-           "ubg_last_error", "ubg_version"]
 
 # the three 16-byte records as numpy dtypes (host copies of the device arrays)
 TILE = np.dtype([("unit0", "<i8"), ("units", "<i4"), ("seg", "<i4")])
@@ -40,55 +33,17 @@ class Ctl(C.Structure):
                 ("applied", C.c_int64), ("skipped", C.c_int64), ("clipped_total", C.c_int64), ("row", C.c_float * 4)]
 
 
-_lib = None
-_lock = threading.Lock()
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-
-
-def _declare(lib):
-    lib.ubg_last_error.restype = C.c_char_p
-    lib.ubg_last_error.argtypes = []
-    lib.ubg_version.restype = C.c_int
-    lib.ubg_version.argtypes = []
-    lib.ubg_plan_tiles.restype = i64
-    lib.ubg_plan_tiles.argtypes = [vp, vp, i64, vp, i64]
-    lib.ubg_state_set.restype = C.c_int
-    lib.ubg_state_set.argtypes = [vp, i64, i64, i64, vp, vp, i64, vp]
-    lib.ubg_state_get.restype = C.c_int
-    lib.ubg_state_get.argtypes = [vp, i64, vp, vp]
-    lib.ubg_grad_norm.restype = C.c_int
-    lib.ubg_grad_norm.argtypes = [vp, i64, vp, i64, vp, vp, i64, f32, f32, C.c_int, vp, i64, vp, vp]
-    lib.ubg_advance.restype = C.c_int
-    lib.ubg_advance.argtypes = [vp, vp, i64, f32, vp, i64, vp, vp]
-    lib.ubg_adam_step.restype = C.c_int
-    lib.ubg_adam_step.argtypes = [vp, vp, vp, vp, i64, vp, i64, vp, vp, i64, f32, f32, f32, vp, vp]
-    lib.ubg_sgd_step.restype = C.c_int
-    lib.ubg_sgd_step.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, i64, f32, f32, C.c_int, vp, vp]
-
-
-def lib():
-    """Load (once) and return the library; raises RuntimeError if it is not built."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(LIB_PATH):
-                    raise RuntimeError(
-                        "ubresnet_amd: HIP extension %s is missing; build it with "
-                        "`python -m ubresnet_amd.build` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
-                try:
-                    l = C.CDLL(LIB_PATH)
-                except OSError as e:
-                    raise RuntimeError("ubresnet_amd: cannot load %s: %s" % (LIB_PATH, e))
-                _declare(l)
-                _lib = l
-    return _lib
-
-
-def check(rc: int, what: str = ""):
-    if rc != 0:
-        msg = lib().ubg_last_error().decode("utf-8", "replace")
-        raise RuntimeError("ubresnet_amd HIP call failed (%d) %s: %s" % (rc, what, msg))
+BINDING = Binding("UBG_LIB", "libubresnet_group.so", "ubg", {
+    "ubg_plan_tiles": (i64, [vp, vp, i64, vp, i64]),
+    "ubg_state_set": (C.c_int, [vp, i64, i64, i64, vp, vp, i64, vp]),
+    "ubg_state_get": (C.c_int, [vp, i64, vp, vp]),
+    "ubg_grad_norm": (C.c_int, [vp, i64, vp, i64, vp, vp, i64, f32, f32, C.c_int, vp, i64, vp, vp]),
+    "ubg_advance": (C.c_int, [vp, vp, i64, f32, vp, i64, vp, vp]),
+    "ubg_adam_step": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, vp, vp, i64, f32, f32, f32, vp, vp]),
+    "ubg_sgd_step": (C.c_int, [vp, vp, vp, i64, vp, i64, vp, vp, i64, f32, f32, C.c_int, vp, vp]),
+})
+LIB_PATH, SYMBOLS, lib, check = BINDING.path, BINDING.symbols, BINDING.lib, BINDING.check
 
 
 def read_ctl(raw: bytes) -> Ctl:

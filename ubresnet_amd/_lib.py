@@ -1,19 +1,16 @@
 """ctypes binding of libubresnet_hip.so (the C ABI in include/ubresnet_hip.h).
 
-There is deliberately NO fallback: if the shared library is missing or a call fails, a
-RuntimeError is raised (callers in the reference catch ``Exception`` and break their loop,
+Loaded through ubresnet_amd/_binding.py.  There is deliberately NO fallback: if the shared library
+is missing or a call fails, a RuntimeError is raised (callers in the reference catch ``Exception`` and break their loop,
 training/train_ubresnet2018_wlarcv2.py:230-239, so errors must be exceptions, never aborts).
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
-import threading
 
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("UBR_LIB", os.path.join(HERE, "libubresnet_hip.so"))     # UBR_LIB: A/B builds of the same ABI (tools)
+from ._binding import Binding
 
 F32, BF16, F16 = 0, 1, 2
 MAX_TAPS = 64
@@ -181,115 +178,65 @@ class WgradDesc(C.Structure):
     ]
 
 
-# every symbol include/ubresnet_hip.h declares (tests check that all of them are exported)
-SYMBOLS = [
-    "ubr_conv", "ubr_conv_last_config", "ubr_conv_last_kernel", "ubr_pack_weights", "ubr_pack_weights_batched", "ubr_bn_fold_batched", "ubr_aspp_front", "ubr_wgrad_plan", "ubr_wgrad", "ubr_wgrad_last_config", "ubr_wgrad_last_pc", "ubr_wgrad_reduce", "ubr_wgrad_reduce_batched",
-    "ubr_stem_forward", "ubr_stem_wgrad", "ubr_stem_wgrad_workspace", "ubr_stem_expand",
-    "ubr_bn_finalize", "ubr_bn_eval_affine", "ubr_bn_bwd_finalize", "ubr_bn_bwd_finalize_frozen",
-    "ubr_bn_bwd", "ubr_block_tail_fwd", "ubr_block_tail_bwd",
-    "ubr_maxpool_fwd", "ubr_maxpool_bwd",
-    "ubr_logsoftmax_bwd", "ubr_pixelwise_nll_fwd", "ubr_pixelwise_nll_bwd", "ubr_confusion",
-    "ubr_channel_sum", "ubr_cast_f64_to_f32", "ubr_zero", "ubr_adam_step", "ubr_sgd_step", "ubr_crop_tiles", "ubr_stitch_tiles", "ubr_last_error", "ubr_version",
-    "ubr_tape_create", "ubr_tape_destroy", "ubr_tape_begin", "ubr_tape_end", "ubr_tape_pause", "ubr_tape_fork", "ubr_tape_mark",
-    "ubr_tape_wait_mark", "ubr_tape_size", "ubr_tape_replay", "ubr_tape_set_label", "ubr_tape_replay_timed",
-    "ubr_launch_log", "ubr_launch_log_read",
-]
-
-_lib = None
-_lock = threading.Lock()
 vp, i32, i64, f32, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
-
-
-def _declare(lib):
-    lib.ubr_last_error.restype = C.c_char_p
-    lib.ubr_version.restype = C.c_int
-    lib.ubr_stem_wgrad_workspace.restype = C.c_int64
-    lib.ubr_stem_wgrad_workspace.argtypes = [i32] * 5
-    lib.ubr_conv.argtypes = [C.POINTER(ConvDesc), vp]
-    lib.ubr_conv_last_config.argtypes = [C.POINTER(C.c_int)] * 4
-    lib.ubr_conv_last_kernel.argtypes = [C.c_char_p, i32]
-    lib.ubr_conv_last_config.restype = None
-    lib.ubr_wgrad_last_config.argtypes = [C.POINTER(C.c_int)] * 5
-    lib.ubr_wgrad_last_config.restype = None
-    lib.ubr_wgrad_last_pc.argtypes = []
-    lib.ubr_wgrad_last_pc.restype = C.c_int
-    lib.ubr_pack_weights.argtypes = [i32, vp, vp, i32, i32, i32, i32, i64, i64, i32, C.POINTER(C.c_int32), vp]
-    lib.ubr_pack_weights_batched.argtypes = [i32, vp, i32, vp]
-    lib.ubr_bn_fold_batched.argtypes = [vp, i32, vp]
-    lib.ubr_aspp_front.argtypes = [C.POINTER(AsppFrontDesc), vp]
-    lib.ubr_wgrad_plan.argtypes = [C.POINTER(WgradDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
-    lib.ubr_wgrad.argtypes = [C.POINTER(WgradDesc), vp]
-    lib.ubr_wgrad_reduce.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, i64, i64, C.POINTER(C.c_int32), i32, vp]
-    lib.ubr_wgrad_reduce_batched.argtypes = [C.POINTER(WgradReduceItem), i32, vp]
-    lib.ubr_stem_forward.argtypes = [i32, vp, i32, i32, i32, i32, vp, vp, i32, Tensor, vp, vp]
-    lib.ubr_stem_wgrad.argtypes = [i32, vp, i32, i32, i32, i32, Tensor, i32, vp, i64, vp, vp, i32, vp]
-    lib.ubr_stem_expand.argtypes = [i32, vp, i32, i32, i32, i32, vp, i64, vp]
-    lib.ubr_bn_finalize.argtypes = [vp, f64, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp, vp]
-    lib.ubr_bn_eval_affine.argtypes = [vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp]
-    lib.ubr_bn_bwd_finalize.argtypes = [vp, f64, i32, vp, vp, i32, vp, vp, vp]
-    lib.ubr_bn_bwd_finalize_frozen.argtypes = [vp, i32, vp, vp, vp, vp, vp]
-    lib.ubr_bn_bwd.argtypes = [C.POINTER(BnBwdDesc), vp]
-    lib.ubr_block_tail_fwd.argtypes = [C.POINTER(BlockTailFwdDesc), vp]
-    lib.ubr_block_tail_bwd.argtypes = [C.POINTER(BlockTailBwdDesc), vp]
-    lib.ubr_maxpool_fwd.argtypes = [i32, i32, i32, i32, i32, i32, vp, i64, ChanAffine, vp, i64, vp, i64, vp, vp]
-    lib.ubr_maxpool_bwd.argtypes = [i32, i32, i32, i32, i32, i32, vp, i64, ChanAffine, vp, i64, vp, i64, vp, i64, vp, vp]
-    lib.ubr_logsoftmax_bwd.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, i64, vp]
-    lib.ubr_pixelwise_nll_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, vp, vp]
-    lib.ubr_pixelwise_nll_bwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, vp]
-    lib.ubr_confusion.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
-    lib.ubr_channel_sum.argtypes = [i32, i64, i32, vp, i64, vp, vp]
-    lib.ubr_cast_f64_to_f32.argtypes = [vp, i32, i32, vp, i32, f64, i32, vp]
-    lib.ubr_zero.argtypes = [vp, i64, vp]
-    lib.ubr_adam_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i64, f32, vp]
-    lib.ubr_sgd_step.argtypes = [vp, vp, vp, i64, f32, f32, f32, f32, i32, i32, f32, vp]
-    lib.ubr_crop_tiles.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, i32, vp, vp]
-    lib.ubr_stitch_tiles.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_int32), i32, vp, i32, i32, i32, vp]
-    lib.ubr_tape_create.argtypes = []
-    lib.ubr_tape_create.restype = vp
-    lib.ubr_tape_destroy.argtypes = [vp]
-    lib.ubr_tape_destroy.restype = None
-    lib.ubr_tape_begin.argtypes = [vp, i32, C.POINTER(vp)]
-    lib.ubr_tape_end.argtypes = [vp]
-    lib.ubr_tape_pause.argtypes = [vp, i32]
-    lib.ubr_tape_fork.argtypes = [vp, i32, i32]
-    lib.ubr_tape_mark.argtypes = [vp, i32]
-    lib.ubr_tape_wait_mark.argtypes = [vp, i32, vp]
-    lib.ubr_tape_size.argtypes = [vp]
-    lib.ubr_tape_replay.argtypes = [vp, i32, C.POINTER(vp)]
-    lib.ubr_tape_set_label.argtypes = [vp, i32]
-    lib.ubr_tape_replay_timed.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(C.c_float), C.POINTER(C.c_int32), i32]
-    lib.ubr_launch_log.argtypes = [i32]
-    lib.ubr_launch_log_read.argtypes = [C.c_char_p, i32]
-    for name in SYMBOLS:
-        fn = getattr(lib, name)
-        if name not in ("ubr_last_error", "ubr_version", "ubr_stem_wgrad_workspace", "ubr_conv_last_config", "ubr_wgrad_last_config",
-                        "ubr_tape_create", "ubr_tape_destroy"):
-            fn.restype = C.c_int
-
-
-def lib():
-    """Load (once) and return the C-ABI library; raises RuntimeError if it is not built."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(LIB_PATH):
-                    raise RuntimeError(
-                        "ubresnet_amd: HIP extension %s is missing; build it with "
-                        "`python -m ubresnet_amd.build` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
-                try:
-                    l = C.CDLL(LIB_PATH)
-                except OSError as e:
-                    raise RuntimeError("ubresnet_amd: cannot load %s: %s" % (LIB_PATH, e))
-                _declare(l)
-                _lib = l
-    return _lib
-
-
-def check(rc: int, what: str = ""):
-    if rc != 0:
-        msg = lib().ubr_last_error().decode("utf-8", "replace")
-        raise RuntimeError("ubresnet_amd HIP call failed (%d) %s: %s" % (rc, what, msg))
+I, P = C.c_int, C.POINTER
+# every symbol include/ubresnet_hip.h declares, with its signature (tests check that all of them are exported)
+BINDING = Binding("UBR_LIB", "libubresnet_hip.so", "ubr", {     # UBR_LIB: A/B builds of the same ABI (tools)
+    "ubr_conv": (I, [P(ConvDesc), vp]),
+    "ubr_conv_last_config": (None, [P(C.c_int)] * 4),
+    "ubr_conv_last_kernel": (I, [C.c_char_p, i32]),
+    "ubr_pack_weights": (I, [i32, vp, vp, i32, i32, i32, i32, i64, i64, i32, P(C.c_int32), vp]),
+    "ubr_pack_weights_batched": (I, [i32, vp, i32, vp]),
+    "ubr_bn_fold_batched": (I, [vp, i32, vp]),
+    "ubr_aspp_front": (I, [P(AsppFrontDesc), vp]),
+    "ubr_wgrad_plan": (I, [P(WgradDesc), P(C.c_int32), P(C.c_int64)]),
+    "ubr_wgrad": (I, [P(WgradDesc), vp]),
+    "ubr_wgrad_last_config": (None, [P(C.c_int)] * 5),
+    "ubr_wgrad_last_pc": (I, []),
+    "ubr_wgrad_reduce": (I, [vp, i32, i32, i32, i32, i32, i32, vp, i64, i64, P(C.c_int32), i32, vp]),
+    "ubr_wgrad_reduce_batched": (I, [P(WgradReduceItem), i32, vp]),
+    "ubr_stem_forward": (I, [i32, vp, i32, i32, i32, i32, vp, vp, i32, Tensor, vp, vp]),
+    "ubr_stem_wgrad": (I, [i32, vp, i32, i32, i32, i32, Tensor, i32, vp, i64, vp, vp, i32, vp]),
+    "ubr_stem_wgrad_workspace": (i64, [i32] * 5),
+    "ubr_stem_expand": (I, [i32, vp, i32, i32, i32, i32, vp, i64, vp]),
+    "ubr_bn_finalize": (I, [vp, f64, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp, vp]),
+    "ubr_bn_eval_affine": (I, [vp, vp, vp, vp, f32, i32, vp, vp, vp, vp, vp]),
+    "ubr_bn_bwd_finalize": (I, [vp, f64, i32, vp, vp, i32, vp, vp, vp]),
+    "ubr_bn_bwd_finalize_frozen": (I, [vp, i32, vp, vp, vp, vp, vp]),
+    "ubr_bn_bwd": (I, [P(BnBwdDesc), vp]),
+    "ubr_block_tail_fwd": (I, [P(BlockTailFwdDesc), vp]),
+    "ubr_block_tail_bwd": (I, [P(BlockTailBwdDesc), vp]),
+    "ubr_maxpool_fwd": (I, [i32, i32, i32, i32, i32, i32, vp, i64, ChanAffine, vp, i64, vp, i64, vp, vp]),
+    "ubr_maxpool_bwd": (I, [i32, i32, i32, i32, i32, i32, vp, i64, ChanAffine, vp, i64, vp, i64, vp, i64, vp, vp]),
+    "ubr_logsoftmax_bwd": (I, [i32, i32, i32, i32, i32, vp, vp, vp, i64, vp]),
+    "ubr_pixelwise_nll_fwd": (I, [vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, vp, vp]),
+    "ubr_pixelwise_nll_bwd": (I, [vp, vp, vp, vp, i32, i32, i32, i32, i64, vp, vp]),
+    "ubr_confusion": (I, [vp, vp, i32, i32, i32, i32, vp, vp]),
+    "ubr_channel_sum": (I, [i32, i64, i32, vp, i64, vp, vp]),
+    "ubr_cast_f64_to_f32": (I, [vp, i32, i32, vp, i32, f64, i32, vp]),
+    "ubr_zero": (I, [vp, i64, vp]),
+    "ubr_adam_step": (I, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i64, f32, vp]),
+    "ubr_sgd_step": (I, [vp, vp, vp, i64, f32, f32, f32, f32, i32, i32, f32, vp]),
+    "ubr_crop_tiles": (I, [vp, i32, i32, i32, P(C.c_int32), i32, i32, i32, vp, vp]),
+    "ubr_stitch_tiles": (I, [vp, i32, i32, i32, P(C.c_int32), i32, vp, i32, i32, i32, vp]),
+    "ubr_last_error": (C.c_char_p, []),
+    "ubr_version": (I, []),
+    "ubr_tape_create": (vp, []),
+    "ubr_tape_destroy": (None, [vp]),
+    "ubr_tape_begin": (I, [vp, i32, P(vp)]),
+    "ubr_tape_end": (I, [vp]),
+    "ubr_tape_pause": (I, [vp, i32]),
+    "ubr_tape_fork": (I, [vp, i32, i32]),
+    "ubr_tape_mark": (I, [vp, i32]),
+    "ubr_tape_wait_mark": (I, [vp, i32, vp]),
+    "ubr_tape_size": (I, [vp]),
+    "ubr_tape_replay": (I, [vp, i32, P(vp)]),
+    "ubr_tape_set_label": (I, [vp, i32]),
+    "ubr_tape_replay_timed": (I, [vp, i32, P(vp), P(C.c_float), P(C.c_int32), i32]),
+    "ubr_launch_log": (I, [i32]),
+    "ubr_launch_log_read": (I, [C.c_char_p, i32]),
+})
+LIB_PATH, SYMBOLS, lib, check = BINDING.path, BINDING.symbols, BINDING.lib, BINDING.check
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)

@@ -2,19 +2,16 @@
 means on the device -- a streaming pass that leaves one row of partials per workgroup, one workgroup that adds them in a fixed
 order into a control block, and the backward that reads the reciprocal of the denominator from that block.
 
-A library of its own next to the other ten (ubresnet_amd/_lib.py, _post.py, _data.py, _aug.py, _opt.py, _weight.py, _group.py,
-_ema.py, _accum.py, _stats.py), with its own error string.  As there, NO fallback: a missing library or a failed call is a
-RuntimeError.  Nothing here imports torch, so the argument checks of the library can be exercised on a machine without a GPU.
+A self-contained library with its own error string, loaded through ubresnet_amd/_binding.py.  NO fallback: a missing library or a
+failed call is a RuntimeError.  Nothing here imports torch, so the argument checks of the library can be exercised on a machine
+without a GPU.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
 import struct
-import threading
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("UBL_LIB", os.path.join(HERE, "libubresnet_loss.so"))
+from ._binding import Binding
 
 BLOCK = 256          # UBL_BLOCK
 UNROLL = 2           # UBL_UNROLL
@@ -32,48 +29,12 @@ CTL = dict(LOSS_SUM=0, WEIGHT_SUM=1, VALID=2, BAD=3, DENOM=4, INV_DENOM=5, LOSS=
 # the words of a workspace row (UBL_ROW_*)
 ROW = dict(LOSS_SUM=0, WEIGHT_SUM=1, VALID=2, BAD=3, CLASS_LOSS=4, CLASS_PIXELS=20)
 
-# every symbol include/ubresnet_loss.h declares (tests check that all of them are exported)
-SYMBOLS = ["ubl_focal_fwd", "ubl_focal_bwd", "ubl_last_error", "ubl_version"]
-
-_lib = None
-_lock = threading.Lock()
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
-
-
-def _declare(lib):
-    lib.ubl_last_error.restype = C.c_char_p
-    lib.ubl_last_error.argtypes = []
-    lib.ubl_version.restype = C.c_int
-    lib.ubl_version.argtypes = []
-    lib.ubl_focal_fwd.restype = C.c_int
-    lib.ubl_focal_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i64, f32, i32, vp, vp, vp, vp]
-    lib.ubl_focal_bwd.restype = C.c_int
-    lib.ubl_focal_bwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, f32, vp, vp]
-
-
-def lib():
-    """Load (once) and return the library; raises RuntimeError if it is not built."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(LIB_PATH):
-                    raise RuntimeError(
-                        "ubresnet_amd: HIP extension %s is missing; build it with "
-                        "`python -m ubresnet_amd.build` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
-                try:
-                    l = C.CDLL(LIB_PATH)
-                except OSError as e:
-                    raise RuntimeError("ubresnet_amd: cannot load %s: %s" % (LIB_PATH, e))
-                _declare(l)
-                _lib = l
-    return _lib
-
-
-def check(rc: int, what: str = ""):
-    if rc != 0:
-        msg = lib().ubl_last_error().decode("utf-8", "replace")
-        raise RuntimeError("ubresnet_amd HIP call failed (%d) %s: %s" % (rc, what, msg))
+BINDING = Binding("UBL_LIB", "libubresnet_loss.so", "ubl", {
+    "ubl_focal_fwd": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i64, f32, i32, vp, vp, vp, vp]),
+    "ubl_focal_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, f32, vp, vp]),
+})
+LIB_PATH, SYMBOLS, lib, check = BINDING.path, BINDING.symbols, BINDING.lib, BINDING.check
 
 
 def grid(pixels: int) -> int:

@@ -1,22 +1,18 @@
 """ctypes binding of libubresnet_opt.so (the C ABI in include/ubresnet_opt.h): the guarded flat optimizer step -- global
 gradient norm, clipping by it and the skip of a non-finite step, decided on the device.
 
-A library of its own next to libubresnet_hip.so (ubresnet_amd/_lib.py), libubresnet_post.so (ubresnet_amd/_post.py),
-libubresnet_data.so (ubresnet_amd/_data.py) and libubresnet_aug.so (ubresnet_amd/_aug.py), with its own error string.  As
-there, NO fallback: a missing library or a failed call is a RuntimeError.  Nothing here imports torch, so the argument checks
-of the library and the bias-correction table can be exercised on a machine without a GPU.
+A self-contained library with its own error string, loaded through ubresnet_amd/_binding.py.  NO fallback: a missing library or a
+failed call is a RuntimeError.  Nothing here imports torch, so the argument checks of the library and the bias-correction table
+can be exercised on a machine without a GPU.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
-import os
-import threading
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("UBO_LIB", os.path.join(HERE, "libubresnet_opt.so"))
+from ._binding import Binding
 
 BLOCK = 256          # UBO_BLOCK
 UNROLL = 4           # UBO_UNROLL
@@ -24,9 +20,6 @@ MAX_GRID = 1024      # UBO_MAX_GRID
 CTL_HEAD_BYTES = 80  # UBO_CTL_HEAD_BYTES
 CTL_BYTES = CTL_HEAD_BYTES + 8 * MAX_GRID   # UBO_CTL_BYTES
 MAX_TABLE = 4 << 20  # rows of a bias-correction table; more is refused
-
-# every symbol include/ubresnet_opt.h declares (tests check that all of them are exported)
-SYMBOLS = ["ubo_ctl_init", "ubo_grad_norm", "ubo_adam_step", "ubo_sgd_step", "ubo_last_error", "ubo_version"]
 
 
 class Ctl(C.Structure):
@@ -36,49 +29,14 @@ class Ctl(C.Structure):
                 ("applied", C.c_int64), ("skipped", C.c_int64), ("clipped_total", C.c_int64), ("row", C.c_float * 4)]
 
 
-_lib = None
-_lock = threading.Lock()
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-
-
-def _declare(lib):
-    lib.ubo_last_error.restype = C.c_char_p
-    lib.ubo_last_error.argtypes = []
-    lib.ubo_version.restype = C.c_int
-    lib.ubo_version.argtypes = []
-    lib.ubo_ctl_init.restype = C.c_int
-    lib.ubo_ctl_init.argtypes = [vp, i64, vp]
-    lib.ubo_grad_norm.restype = C.c_int
-    lib.ubo_grad_norm.argtypes = [vp, i64, f32, f32, C.c_int, vp, i64, vp, vp]
-    lib.ubo_adam_step.restype = C.c_int
-    lib.ubo_adam_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, vp]
-    lib.ubo_sgd_step.restype = C.c_int
-    lib.ubo_sgd_step.argtypes = [vp, vp, vp, i64, f32, f32, f32, f32, C.c_int, vp, vp]
-
-
-def lib():
-    """Load (once) and return the library; raises RuntimeError if it is not built."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(LIB_PATH):
-                    raise RuntimeError(
-                        "ubresnet_amd: HIP extension %s is missing; build it with "
-                        "`python -m ubresnet_amd.build` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
-                try:
-                    l = C.CDLL(LIB_PATH)
-                except OSError as e:
-                    raise RuntimeError("ubresnet_amd: cannot load %s: %s" % (LIB_PATH, e))
-                _declare(l)
-                _lib = l
-    return _lib
-
-
-def check(rc: int, what: str = ""):
-    if rc != 0:
-        msg = lib().ubo_last_error().decode("utf-8", "replace")
-        raise RuntimeError("ubresnet_amd HIP call failed (%d) %s: %s" % (rc, what, msg))
+BINDING = Binding("UBO_LIB", "libubresnet_opt.so", "ubo", {
+    "ubo_ctl_init": (C.c_int, [vp, i64, vp]),
+    "ubo_grad_norm": (C.c_int, [vp, i64, f32, f32, C.c_int, vp, i64, vp, vp]),
+    "ubo_adam_step": (C.c_int, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, vp]),
+    "ubo_sgd_step": (C.c_int, [vp, vp, vp, i64, f32, f32, f32, f32, C.c_int, vp, vp]),
+})
+LIB_PATH, SYMBOLS, lib, check = BINDING.path, BINDING.symbols, BINDING.lib, BINDING.check
 
 
 def bias_table(beta1: float, beta2: float) -> np.ndarray:

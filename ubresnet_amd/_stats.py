@@ -2,29 +2,23 @@
 on the device -- the scan of the live statistics for non-finite values, the decision between commit and restore, and the move of
 every row of a table of small tensors in the decided direction.
 
-A library of its own next to the other nine (ubresnet_amd/_lib.py, _post.py, _data.py, _aug.py, _opt.py, _weight.py, _group.py,
-_ema.py, _accum.py), with its own error string.  As there, NO fallback: a missing library or a failed call is a RuntimeError.
-Nothing here imports torch, so the argument checks of the library can be exercised on a machine without a GPU.
+A self-contained library with its own error string, loaded through ubresnet_amd/_binding.py.  NO fallback: a missing library or a
+failed call is a RuntimeError.  Nothing here imports torch, so the argument checks of the library can be exercised on a machine
+without a GPU.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
-import threading
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("UBS_LIB", os.path.join(HERE, "libubresnet_stats.so"))
+from ._binding import Binding
 
 BLOCK = 256          # UBS_BLOCK
 SEG_GRID = 256       # UBS_SEG_GRID
 CTL_BYTES = 32       # UBS_CTL_BYTES
 KIND_F32 = 0         # UBS_KIND_F32: fp32 values, scanned
 KIND_RAW = 1         # UBS_KIND_RAW: raw 4-byte units, never scanned
-
-# every symbol include/ubresnet_stats.h declares (tests check that all of them are exported)
-SYMBOLS = ["ubs_ctl_init", "ubs_scan", "ubs_note", "ubs_decide", "ubs_resolve", "ubs_last_error", "ubs_version"]
 
 # one row of the table as a numpy dtype (host copy of the device array)
 SEG = np.dtype([("shadow", "<u8"), ("live", "<u8"), ("count", "<i8"), ("kind", "<i8")])
@@ -38,51 +32,15 @@ class Ctl(C.Structure):
                 ("restored_for_stats", C.c_int64)]
 
 
-_lib = None
-_lock = threading.Lock()
 vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int32
-
-
-def _declare(lib):
-    lib.ubs_last_error.restype = C.c_char_p
-    lib.ubs_last_error.argtypes = []
-    lib.ubs_version.restype = C.c_int
-    lib.ubs_version.argtypes = []
-    lib.ubs_ctl_init.restype = C.c_int
-    lib.ubs_ctl_init.argtypes = [vp, vp]
-    lib.ubs_scan.restype = C.c_int
-    lib.ubs_scan.argtypes = [vp, i64, vp, vp]
-    lib.ubs_note.restype = C.c_int
-    lib.ubs_note.argtypes = [vp, vp, i64, vp]
-    lib.ubs_decide.restype = C.c_int
-    lib.ubs_decide.argtypes = [vp, vp, i64, vp, i32, vp]
-    lib.ubs_resolve.restype = C.c_int
-    lib.ubs_resolve.argtypes = [vp, i64, vp, vp]
-
-
-def lib():
-    """Load (once) and return the library; raises RuntimeError if it is not built."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(LIB_PATH):
-                    raise RuntimeError(
-                        "ubresnet_amd: HIP extension %s is missing; build it with "
-                        "`python -m ubresnet_amd.build` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
-                try:
-                    l = C.CDLL(LIB_PATH)
-                except OSError as e:
-                    raise RuntimeError("ubresnet_amd: cannot load %s: %s" % (LIB_PATH, e))
-                _declare(l)
-                _lib = l
-    return _lib
-
-
-def check(rc: int, what: str = ""):
-    if rc != 0:
-        msg = lib().ubs_last_error().decode("utf-8", "replace")
-        raise RuntimeError("ubresnet_amd HIP call failed (%d) %s: %s" % (rc, what, msg))
+BINDING = Binding("UBS_LIB", "libubresnet_stats.so", "ubs", {
+    "ubs_ctl_init": (C.c_int, [vp, vp]),
+    "ubs_scan": (C.c_int, [vp, i64, vp, vp]),
+    "ubs_note": (C.c_int, [vp, vp, i64, vp]),
+    "ubs_decide": (C.c_int, [vp, vp, i64, vp, i32, vp]),
+    "ubs_resolve": (C.c_int, [vp, i64, vp, vp]),
+})
+LIB_PATH, SYMBOLS, lib, check = BINDING.path, BINDING.symbols, BINDING.lib, BINDING.check
 
 
 def read_ctl(raw: bytes) -> Ctl:

@@ -2,19 +2,16 @@
 device -- write a batch of input planes flipped, read the network's log-probabilities back un-flipped into a running merge that
 ends as the log of the mean of the views' probabilities.
 
-A library of its own next to the other twelve (ubresnet_amd/_lib.py, _post.py, ...), with its own error string.  As there, NO
-fallback: a missing library or a failed call is a RuntimeError.  Nothing here imports torch, so the argument checks of the library
-can be exercised on a machine without a GPU.
+A self-contained library with its own error string, loaded through ubresnet_amd/_binding.py.  NO fallback: a missing library or a
+failed call is a RuntimeError.  Nothing here imports torch, so the argument checks of the library can be exercised on a machine
+without a GPU.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
-import os
-import threading
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("UBT_LIB", os.path.join(HERE, "libubresnet_tta.so"))
+from ._binding import Binding
 
 BLOCK = 256          # UBT_BLOCK
 UNROLL = 2           # UBT_UNROLL
@@ -24,48 +21,12 @@ FLIP_ROWS, FLIP_COLS = 1, 2
 # the names deploy.py takes for the views after the identity
 FLIPS = {"rows": FLIP_ROWS, "cols": FLIP_COLS, "both": FLIP_ROWS | FLIP_COLS}
 
-# every symbol include/ubresnet_tta.h declares (tests check that all of them are exported)
-SYMBOLS = ["ubt_flip_planes", "ubt_merge_view", "ubt_last_error", "ubt_version"]
-
-_lib = None
-_lock = threading.Lock()
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-
-
-def _declare(lib):
-    lib.ubt_last_error.restype = C.c_char_p
-    lib.ubt_last_error.argtypes = []
-    lib.ubt_version.restype = C.c_int
-    lib.ubt_version.argtypes = []
-    lib.ubt_flip_planes.restype = C.c_int
-    lib.ubt_flip_planes.argtypes = [vp, vp, i64, i32, i32, i32, vp]
-    lib.ubt_merge_view.restype = C.c_int
-    lib.ubt_merge_view.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, f32, vp]
-
-
-def lib():
-    """Load (once) and return the library; raises RuntimeError if it is not built."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(LIB_PATH):
-                    raise RuntimeError(
-                        "ubresnet_amd: HIP extension %s is missing; build it with "
-                        "`python -m ubresnet_amd.build` (hipcc, gfx950). There is no CPU fallback." % LIB_PATH)
-                try:
-                    l = C.CDLL(LIB_PATH)
-                except OSError as e:
-                    raise RuntimeError("ubresnet_amd: cannot load %s: %s" % (LIB_PATH, e))
-                _declare(l)
-                _lib = l
-    return _lib
-
-
-def check(rc: int, what: str = ""):
-    if rc != 0:
-        msg = lib().ubt_last_error().decode("utf-8", "replace")
-        raise RuntimeError("ubresnet_amd HIP call failed (%d) %s: %s" % (rc, what, msg))
+BINDING = Binding("UBT_LIB", "libubresnet_tta.so", "ubt", {
+    "ubt_flip_planes": (C.c_int, [vp, vp, i64, i32, i32, i32, vp]),
+    "ubt_merge_view": (C.c_int, [vp, vp, i64, i32, i32, i32, i32, i32, f32, vp]),
+})
+LIB_PATH, SYMBOLS, lib, check = BINDING.path, BINDING.symbols, BINDING.lib, BINDING.check
 
 
 def parse_views(tta):

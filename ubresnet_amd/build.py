@@ -1,21 +1,16 @@
-"""Build libubresnet_hip.so (all HIP kernels of the network + the C ABI), libubresnet_post.so (event products of
-whole-view inference), libubresnet_data.so (device-side batch preparation of the loader), libubresnet_aug.so (device-side
-augmentation of training batches), libubresnet_opt.so (the guarded flat optimizer step), libubresnet_weight.so (device-side
-pixel weights of the loss), libubresnet_group.so (flat optimizer steps with parameter groups), libubresnet_ema.so (the
-exponential moving average of the parameters), libubresnet_accum.so (gradient accumulation over the flat gradient buffer),
-libubresnet_stats.so (the guard of the BatchNorm running statistics), libubresnet_loss.so (the pixel-wise focal loss and its
-normalised means), libubresnet_dice.so (the soft Dice / Tversky region loss), libubresnet_tta.so (flip test-time augmentation
-of inference) and libubresnet_det.so (detector effects on training batches), the latter thirteen self-contained libraries of
-their own, with hipcc for gfx950, in-tree.
+"""Build the package's shared libraries with hipcc for gfx950, in-tree.
 
     python -m ubresnet_amd.build [--force]
 
-The shared libraries have NO PyTorch dependency: they are plain HIP behind include/ubresnet_hip.h,
-include/ubresnet_post.h, include/ubresnet_data.h, include/ubresnet_aug.h, include/ubresnet_opt.h, include/ubresnet_weight.h, include/ubresnet_group.h, include/ubresnet_ema.h, include/ubresnet_accum.h, include/ubresnet_stats.h, include/ubresnet_loss.h, include/ubresnet_dice.h, include/ubresnet_tta.h and include/ubresnet_det.h.  Objects are compiled in parallel, one per translation unit, with the same flags.
+LIBS is the table of them, in build order: name -> (out, sources, headers, binding).  `hip` is libubresnet_hip.so, all HIP kernels
+of the network and its C ABI; every other entry is a self-contained library of one .hip file that links against none of the
+others, and whose purpose the docstring of its binding module states.  `sources` and `headers` are relative to csrc/, `headers`
+being every file the sources reach through quoted #includes; `binding` names the ctypes module of ubresnet_amd that loads `out`.
 
-build() makes the first nine, build_stats() the tenth, build_loss() the eleventh, build_dice() the twelfth, build_tta() the
-thirteenth and build_det() the fourteenth by the same steps; the command line and the driver entry point call all six.
+The shared libraries have NO PyTorch dependency: they are plain HIP behind the public headers in include/.  Objects are compiled
+in parallel, one per translation unit, with the same flags.  source_hash() covers the network's library only.
 """
+from collections import namedtuple
 import os
 import subprocess
 import sys
@@ -26,58 +21,40 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libubresnet_hip.so")
 SOURCES = ["ubr_conv.hip", "ubr_aspp.hip", "ubr_wgrad.hip", "ubr_elem.hip", "ubr_head.hip", "ubr_tape.hip"]
 HEADERS = ["ubr_common.h", "ubr_host.h", os.path.join("..", "..", "include", "ubresnet_hip.h")]
-# the second library: not linked against the first; source_hash() covers the network sources only
-POST_OUT = os.path.join(HERE, "libubresnet_post.so")
-POST_SOURCES = ["ubr_post.hip"]
-POST_HEADERS = [os.path.join("..", "..", "include", "ubresnet_post.h")]
-# the third library: like the second, it links against neither of the others
-DATA_OUT = os.path.join(HERE, "libubresnet_data.so")
-DATA_SOURCES = ["ubr_data.hip"]
-DATA_HEADERS = [os.path.join("..", "..", "include", "ubresnet_data.h")]
-# the fourth library: it links against none of the others either
-AUG_OUT = os.path.join(HERE, "libubresnet_aug.so")
-AUG_SOURCES = ["ubr_aug.hip"]
-AUG_HEADERS = [os.path.join("..", "..", "include", "ubresnet_aug.h")]
-# the fifth library: it links against none of the others either
-OPT_OUT = os.path.join(HERE, "libubresnet_opt.so")
-OPT_SOURCES = ["ubr_opt.hip"]
-OPT_HEADERS = [os.path.join("..", "..", "include", "ubresnet_opt.h")]
-# the sixth library: it links against none of the others either
-WEIGHT_OUT = os.path.join(HERE, "libubresnet_weight.so")
-WEIGHT_SOURCES = ["ubr_weight.hip"]
-WEIGHT_HEADERS = ["ubr_weight_tile.h", os.path.join("..", "..", "include", "ubresnet_weight.h")]
-# the seventh library: it links against none of the others either
-GROUP_OUT = os.path.join(HERE, "libubresnet_group.so")
-GROUP_SOURCES = ["ubr_group.hip"]
-GROUP_HEADERS = ["ubr_group_plan.h", os.path.join("..", "..", "include", "ubresnet_group.h")]
-# the eighth library: it links against none of the others either
-EMA_OUT = os.path.join(HERE, "libubresnet_ema.so")
-EMA_SOURCES = ["ubr_ema.hip"]
-EMA_HEADERS = ["ubr_ema_sched.h", os.path.join("..", "..", "include", "ubresnet_ema.h")]
-# the ninth library: it links against none of the others either
-ACCUM_OUT = os.path.join(HERE, "libubresnet_accum.so")
-ACCUM_SOURCES = ["ubr_accum.hip"]
-ACCUM_HEADERS = [os.path.join("..", "..", "include", "ubresnet_accum.h")]
-# the tenth library: it links against none of the others either
-STATS_OUT = os.path.join(HERE, "libubresnet_stats.so")
-STATS_SOURCES = ["ubr_stats.hip"]
-STATS_HEADERS = ["ubr_stats_decide.h", os.path.join("..", "..", "include", "ubresnet_stats.h")]
-# the eleventh library: it links against none of the others either
-LOSS_OUT = os.path.join(HERE, "libubresnet_loss.so")
-LOSS_SOURCES = ["ubr_loss.hip"]
-LOSS_HEADERS = ["ubr_loss_term.h", os.path.join("..", "..", "include", "ubresnet_loss.h")]
-# the twelfth library: it links against none of the others either
-DICE_OUT = os.path.join(HERE, "libubresnet_dice.so")
-DICE_SOURCES = ["ubr_dice.hip"]
-DICE_HEADERS = ["ubr_dice_term.h", os.path.join("..", "..", "include", "ubresnet_dice.h")]
-# the thirteenth library: it links against none of the others either
-TTA_OUT = os.path.join(HERE, "libubresnet_tta.so")
-TTA_SOURCES = ["ubr_tta.hip"]
-TTA_HEADERS = [os.path.join("..", "..", "include", "ubresnet_tta.h")]
-# the fourteenth library: it links against none of the others either
-DET_OUT = os.path.join(HERE, "libubresnet_det.so")
-DET_SOURCES = ["ubr_det.hip"]
-DET_HEADERS = ["ubr_det_rule.h", os.path.join("..", "..", "include", "ubresnet_det.h")]
+Lib = namedtuple("Lib", "out sources headers binding")
+
+
+def _satellite(name, *csrc_headers):
+    return Lib(os.path.join(HERE, "libubresnet_%s.so" % name), ["ubr_%s.hip" % name],
+               list(csrc_headers) + [os.path.join("..", "..", "include", "ubresnet_%s.h" % name)], "_" + name)
+
+
+LIBS = {
+    "hip": Lib(OUT, SOURCES, HEADERS, "_lib"),
+    "post": _satellite("post"),
+    "data": _satellite("data"),
+    "aug": _satellite("aug"),
+    "opt": _satellite("opt"),
+    "weight": _satellite("weight", "ubr_weight_tile.h"),
+    "group": _satellite("group", "ubr_group_plan.h"),
+    "ema": _satellite("ema", "ubr_ema_sched.h"),
+    "accum": _satellite("accum"),
+    "stats": _satellite("stats", "ubr_stats_decide.h"),
+    "loss": _satellite("loss", "ubr_loss_term.h"),
+    "dice": _satellite("dice", "ubr_dice_term.h"),
+    "tta": _satellite("tta"),
+    "det": _satellite("det", "ubr_det_rule.h"),
+}
+
+
+def __getattr__(name):
+    """POST_OUT .. DET_OUT were public constants of this module; they read LIBS[name].out, so that code outside this tree that
+    imports them (the suite of an earlier commit run against this build reads them at import) keeps loading.  New code uses LIBS."""
+    if name.endswith("_OUT") and name[:-4].lower() in LIBS:
+        return LIBS[name[:-4].lower()].out
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-ffp-contract=off"]
@@ -100,50 +77,14 @@ def _newer(target, deps):
     return all(os.path.getmtime(d) <= t for d in deps)
 
 
-def build(force=False, verbose=True):
-    """compile what is out of date and link the nine libraries; -> path of the main library"""
-    libs = [(OUT, SOURCES, HEADERS), (POST_OUT, POST_SOURCES, POST_HEADERS),
-            (DATA_OUT, DATA_SOURCES, DATA_HEADERS), (AUG_OUT, AUG_SOURCES, AUG_HEADERS),
-            (OPT_OUT, OPT_SOURCES, OPT_HEADERS), (WEIGHT_OUT, WEIGHT_SOURCES, WEIGHT_HEADERS),
-            (GROUP_OUT, GROUP_SOURCES, GROUP_HEADERS), (EMA_OUT, EMA_SOURCES, EMA_HEADERS),
-            (ACCUM_OUT, ACCUM_SOURCES, ACCUM_HEADERS)]
-    _build(libs, force, verbose)
-    return OUT
-
-
-def build_stats(force=False, verbose=True):
-    """the tenth library by the same steps: one more (OUT, SOURCES, HEADERS) tuple; -> its path"""
-    _build([(STATS_OUT, STATS_SOURCES, STATS_HEADERS)], force, verbose)
-    return STATS_OUT
-
-
-def build_loss(force=False, verbose=True):
-    """the eleventh library by the same steps; -> its path"""
-    _build([(LOSS_OUT, LOSS_SOURCES, LOSS_HEADERS)], force, verbose)
-    return LOSS_OUT
-
-
-def build_dice(force=False, verbose=True):
-    """the twelfth library by the same steps; -> its path"""
-    _build([(DICE_OUT, DICE_SOURCES, DICE_HEADERS)], force, verbose)
-    return DICE_OUT
-
-
-def build_tta(force=False, verbose=True):
-    """the thirteenth library by the same steps; -> its path"""
-    _build([(TTA_OUT, TTA_SOURCES, TTA_HEADERS)], force, verbose)
-    return TTA_OUT
-
-
-def build_det(force=False, verbose=True):
-    """the fourteenth library by the same steps; -> its path"""
-    _build([(DET_OUT, DET_SOURCES, DET_HEADERS)], force, verbose)
-    return DET_OUT
-
-
-def _build(libs, force, verbose):
+def build(force=False, verbose=True, only=None):
+    """compile what is out of date and link every library of LIBS, or those named in `only`; -> their paths, in table order"""
+    unknown = [n for n in only or () if n not in LIBS]
+    if unknown:
+        raise ValueError("build: no library named %s; the libraries are %s" % (unknown, list(LIBS)))
+    libs = [lib for name, lib in LIBS.items() if only is None or name in only]
     jobs, links = [], []
-    for out, sources, headers in libs:
+    for out, sources, headers, _ in libs:
         hdrs = [os.path.join(CSRC, h) for h in headers]
         objs, stale = [], False
         for s in sources:
@@ -176,12 +117,8 @@ def _build(libs, force, verbose):
             if r.returncode != 0:
                 sys.stderr.write(r.stdout + r.stderr)
                 raise RuntimeError("link failed")
+    return [lib.out for lib in libs]
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv))
-    print(build_stats(force="--force" in sys.argv))
-    print(build_loss(force="--force" in sys.argv))
-    print(build_dice(force="--force" in sys.argv))
-    print(build_tta(force="--force" in sys.argv))
-    print(build_det(force="--force" in sys.argv))
+    print("\n".join(build(force="--force" in sys.argv)))
