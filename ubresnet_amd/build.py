@@ -1,6 +1,6 @@
 """Build the package's shared libraries with hipcc for gfx950, in-tree.
 
-    python -m ubresnet_amd.build [--force]
+    python -m ubresnet_amd.build [--force] [--extras]
 
 LIBS is the table of them, in build order: name -> (out, sources, headers, binding).  `hip` is libubresnet_hip.so, all HIP kernels
 of the network and its C ABI; every other entry is a self-contained library of one .hip file that links against none of the
@@ -9,6 +9,9 @@ being every file the sources reach through quoted #includes; `binding` names the
 
 The shared libraries have NO PyTorch dependency: they are plain HIP behind the public headers in include/.  Objects are compiled
 in parallel, one per translation unit, with the same flags.  source_hash() covers the network's library only.
+
+EXTRAS is a second table of the same tuples, for libraries whose sources live under csrc/extra/: build_extras() builds it with the
+same compiler, flags and commands, `--extras` builds it after LIBS.  (Why there are two tables: DESIGN.md, "Two build tables".)
 """
 from collections import namedtuple
 import os
@@ -46,6 +49,11 @@ LIBS = {
     "det": _satellite("det", "ubr_det_rule.h"),
 }
 
+EXTRAS = {
+    "score": Lib(os.path.join(HERE, "libubresnet_score.so"), [os.path.join("extra", "ubr_score.hip")],
+                 [os.path.join("..", "..", "include", "ubresnet_score.h")], "_score"),
+}
+
 
 def __getattr__(name):
     """POST_OUT .. DET_OUT were public constants of this module; they read LIBS[name].out, so that code outside this tree that
@@ -77,12 +85,12 @@ def _newer(target, deps):
     return all(os.path.getmtime(d) <= t for d in deps)
 
 
-def build(force=False, verbose=True, only=None):
-    """compile what is out of date and link every library of LIBS, or those named in `only`; -> their paths, in table order"""
-    unknown = [n for n in only or () if n not in LIBS]
+def _build(table, what, force, verbose, only, echo):
+    """compile what is out of date and link every library of `table`, or those named in `only`; -> their paths, in table order"""
+    unknown = [n for n in only or () if n not in table]
     if unknown:
-        raise ValueError("build: no library named %s; the libraries are %s" % (unknown, list(LIBS)))
-    libs = [lib for name, lib in LIBS.items() if only is None or name in only]
+        raise ValueError("%s: no library named %s; the libraries are %s" % (what, unknown, list(table)))
+    libs = [lib for name, lib in table.items() if only is None or name in only]
     jobs, links = [], []
     for out, sources, headers, _ in libs:
         hdrs = [os.path.join(CSRC, h) for h in headers]
@@ -98,7 +106,7 @@ def build(force=False, verbose=True, only=None):
 
     def run(cmd):
         if verbose:
-            print(" ".join(cmd), flush=True)
+            print(" ".join(cmd), file=echo(), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)
         return cmd, r
 
@@ -120,5 +128,18 @@ def build(force=False, verbose=True, only=None):
     return [lib.out for lib in libs]
 
 
+def build(force=False, verbose=True, only=None):
+    """compile what is out of date and link every library of LIBS, or those named in `only`; -> their paths, in table order"""
+    return _build(LIBS, "build", force, verbose, only, lambda: sys.stdout)
+
+
+def build_extras(force=False, verbose=True, only=None):
+    """the same for EXTRAS; the commands are echoed to stderr, so that a caller's stdout carries what it carried before EXTRAS"""
+    return _build(EXTRAS, "build_extras", force, verbose, only, lambda: sys.stderr)
+
+
 if __name__ == "__main__":
-    print("\n".join(build(force="--force" in sys.argv)))
+    paths = build(force="--force" in sys.argv)
+    if "--extras" in sys.argv:
+        paths += build_extras(force="--force" in sys.argv)
+    print("\n".join(paths))
