@@ -1,11 +1,13 @@
 """Reference of ubo_grad_norm's decision (include/ubresnet_opt.h) in fp64 / numpy, written from the header's rule, the
 bias-correction table from ubr_adam_step's formula, and the table of cases that tests/test_gpu_opt_exact.py runs -- one entry per
 kernel compiled into libubresnet_opt.so, which tests/test_cpu_opt.py holds against the library's symbol table.  No GPU and no
-torch here.
+torch here.  Further down: the Adam and SGD steps of one element in numpy fp32, operation by operation, with the one fused
+multiply-add of each rounded once from exact rational arithmetic -- what tests/opt_rule_host.cpp is held against.
 
 Acceptance: sumsq, norm and everything a step writes are equal to the reference bit for bit; `scale` (one fp32 division on the
 device) is within one fp32 ulp of the numpy fp32 formula and exactly 1.0 where nothing is clipped."""
 import math
+from fractions import Fraction
 
 import numpy as np
 
@@ -78,3 +80,46 @@ def decide(sumsq, grad_scale, max_norm, skip_nonfinite, state, table):
     else:
         state["skipped"] += 1
     return dict(sumsq=sumsq, norm=f(norm), scale=f(scale), gscale=f(gscale), apply=int(apply), clipped=int(clipped), **state)
+
+
+def fma32(a, b, c):
+    """a * b + c of three finite float32 values, rounded to float32 ONCE (ties to even), as fmaf does: the sum is formed in
+    exact rational arithmetic.  (An fp64 multiply-add would round twice.)  Results in the normal or subnormal range only."""
+    x = Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c))
+    if x == 0:
+        return np.float32(0.0)
+    e = max(math.floor(math.log2(abs(x))), -126)
+    while Fraction(2) ** e > abs(x) and e > -126:          # log2 of a value next to a power of two may land on the wrong side
+        e -= 1
+    while Fraction(2) ** (e + 1) <= abs(x):
+        e += 1
+    q = Fraction(2) ** (e - 23)                                # the spacing of float32 in [2^e, 2^(e+1))
+    n = x / q
+    r = math.floor(n)
+    if n - r > Fraction(1, 2) or (n - r == Fraction(1, 2) and r % 2 == 1):
+        r += 1
+    out = np.float32(float(r * q))                             # r * q has at most 25 bits: exact in fp64, and a float32 by construction
+    assert Fraction(float(out)) == r * q and np.isfinite(out)
+    return out
+
+
+def adam_element(p, g, m, v, gscale, wd, b1, b2, eps, lr, bc1, sqrt_bc2):
+    """one element of ubo_adam_step / ubg_adam_step; every argument a np.float32 -> (p, m, v)"""
+    one = np.float32(1.0)
+    step_size = lr / bc1
+    gr = fma32(wd, p, g * gscale)
+    m = m + (one - b1) * (gr - m)
+    v = b2 * v + (one - b2) * gr * gr
+    denom = np.sqrt(v) / sqrt_bc2 + eps
+    p = p - step_size * (m / denom)
+    return p, m, v
+
+
+def sgd_element(p, g, b, gscale, wd, lr, momentum, dampening, has_buf, first, nesterov):
+    """one element of ubo_sgd_step / ubg_sgd_step -> (p, b); b comes back unchanged without a momentum buffer"""
+    one = np.float32(1.0)
+    gr = fma32(wd, p, g * gscale)
+    if has_buf:
+        b = gr if first else momentum * b + (one - dampening) * gr
+        gr = fma32(momentum, b, gr) if nesterov else b
+    return p - lr * gr, b

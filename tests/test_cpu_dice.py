@@ -70,8 +70,11 @@ def test_header_binding_reference_and_library_agree():
     want = ["dice_fwd_kernel<%d, %s>" % (c, v) for c in range(K.REG_CLASSES + 1) for v in ("false", "true")]
     want += ["dice_bwd_kernel<false>", "dice_bwd_kernel<true>", "dice_finish_kernel"]
     assert sorted(kernel_symbols.kernels(LIB)) == sorted(want)
-    # no atomic operation anywhere in the source
-    assert "atomic" not in re.sub(r"//.*", "", open(os.path.join(B.CSRC, "ubr_dice.hip")).read())
+    # no atomic operation anywhere in the source, nor in any header of csrc/ that it includes
+    files = [os.path.join(B.CSRC, f) for f in B.LIBS["dice"].sources + B.LIBS["dice"].headers if not f.startswith("..")]
+    assert sorted(os.path.basename(f) for f in files) == ["ubr_dice.hip", "ubr_dice_term.h", "ubr_rows.h", "ubr_sat.h"]
+    for f in files:
+        assert "atomic" not in re.sub(r"//.*", "", open(f).read()), f
 
 
 def test_read_ctl_unpacks_the_words():

@@ -69,8 +69,11 @@ def test_header_binding_reference_and_library_agree():
     # five kernels: both forms of the two streaming passes, and the finish
     assert sorted(kernel_symbols.kernels(LIB)) == ["focal_bwd_kernel<false>", "focal_bwd_kernel<true>", "focal_finish_kernel",
                                                    "focal_fwd_kernel<false>", "focal_fwd_kernel<true>"]
-    # no atomic operation anywhere in the source
-    assert "atomic" not in re.sub(r"//.*", "", open(os.path.join(B.CSRC, "ubr_loss.hip")).read())
+    # no atomic operation anywhere in the source, nor in any header of csrc/ that it includes
+    files = [os.path.join(B.CSRC, f) for f in B.LIBS["loss"].sources + B.LIBS["loss"].headers if not f.startswith("..")]
+    assert sorted(os.path.basename(f) for f in files) == ["ubr_loss.hip", "ubr_loss_term.h", "ubr_rows.h", "ubr_sat.h"]
+    for f in files:
+        assert "atomic" not in re.sub(r"//.*", "", open(f).read()), f
 
 
 def test_read_ctl_unpacks_the_words():

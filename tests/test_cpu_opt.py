@@ -1,7 +1,8 @@
 """The guarded optimizer step without a GPU: libubresnet_opt.so's header is C99; header, binding and library agree on the entry
 points and on the control block; the kernels compiled into it are exactly the ones the case table of tests/test_gpu_opt_exact.py
-claims; the bias-correction table against kref.adam_ref's rounded corrections; opt_ref's decision rule by hand; every argument
-refusal returns its error before any launch."""
+claims; the bias-correction table against kref.adam_ref's rounded corrections; opt_ref's decision rule by hand; the rule header
+that ubr_opt.hip and ubr_group.hip share as a program of its own against opt_ref, bit for bit; every argument refusal returns its
+error before any launch."""
 import ctypes as C
 import math
 import os
@@ -172,6 +173,80 @@ def test_decide_reference_by_hand():
     assert d["apply"] == 1 and d["scale"] == 1.0 and d["applied"] == 3 and math.isnan(d["norm"])
     d = R.decide(4.0, 1.0, -1.0, True, st, tab[:2])                    # past the table's end: its last row
     assert d["applied"] == 4 and d["bc1"] == tab[1, 0] and d["scale"] == 1.0
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the rule header as a program
+# ------------------------------------------------------------------------------------------------------------------------
+def _f32(s):
+    return np.array([int(s, 16)], np.uint32).view(np.float32)[0]
+
+
+def _f64(s):
+    return float(np.array([int(s, 16)], np.uint64).view(np.float64)[0])
+
+
+def _b32(x):
+    return int(np.array([x], np.float32).view(np.uint32)[0])
+
+
+def test_rule_as_a_program_under_the_host_sanitizers(tmp_path):
+    """tests/opt_rule_host.cpp has its own main and includes ubr_opt_rule.h; built with -fsanitize=address,undefined and
+    -ffp-contract=off (as the libraries are) and run as a process of its own.  Everything is compared bit for bit: the sum of
+    squares against fp64 (the square of a float32 is exact there); fourteen decisions of one control block in sequence against
+    opt_ref.decide -- clipped, not clipped, max_norm < 0 and 0, a sum of 0, inf and NaN with the guard on and off, tables shorter
+    than the applied count; 54 Adam elements at t = 1, inside and past the table's end, and 216 SGD elements -- plain, momentum
+    first and later step, nesterov -- against numpy fp32 with the fused multiply-add rounded once (opt_ref.fma32)"""
+    exe = str(tmp_path / "opt_rule_host")
+    r = subprocess.run([cc(plus=True), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-ffp-contract=off",
+                        "-Wall", "-Werror", "-I", os.path.join(REPO, "ubresnet_amd", "csrc"), os.path.join(REPO, "tests", "opt_rule_host.cpp"), "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    p = subprocess.run([exe], capture_output=True, text=True)
+    assert p.returncode == 0, "sanitizer or program failure:\n" + p.stderr[-2000:]
+    rows = [l.replace("|", " ").split() for l in p.stdout.strip().split("\n")]
+    by = {k: [row[1:] for row in rows if row[0] == k] for k in "TQDAS"}
+    assert [len(by[k]) for k in "TQDAS"] == [4, 16, 14, 54, 216] and len(rows) == 304
+    # fma32 itself: where a * b + c is a float32 it is that; where fp64 rounds twice it differs from the fp64 emulation
+    assert R.fma32(np.float32(0.0625), np.float32(1.5), np.float32(0.375)) == np.float32(0.46875)
+    a, b, c = np.float32(1 + 2.0 ** -12), np.float32(1 + 2.0 ** -12), np.float32(2.0 ** -53)      # 1 + 2^-11 + 2^-24 (a tie) + 2^-53
+    assert R.fma32(a, b, c) == np.float32(1 + 2.0 ** -11 + 2.0 ** -23) != np.float32(float(a) * float(b) + float(c))
+    table = np.array([[_f32(x), _f32(y)] for _, x, y in by["T"]], np.float32)
+    assert np.array_equal(table, R.bias_table(0.9, 0.999)[:4])
+    with np.errstate(all="ignore"):
+        for acc, x, y, z, w, got in by["Q"]:
+            want = _f64(acc)
+            for v in (x, y, z, w):
+                want = want + float(_f32(v)) * float(_f32(v))
+            assert int(got, 16) == int(np.array([want]).view(np.uint64)[0]) or (math.isnan(want) and math.isnan(_f64(got))), (acc, x, y, z, w)
+        # the decisions
+        st = dict(applied=0, skipped=0, clipped_total=0, bc1=np.float32(0), sqrt_bc2=np.float32(0))
+        seen = set()
+        for sumsq, gs, mn, skip, bc_len, norm, scale, gscale, apply, clipped, bc1, sbc2, applied, skipped, ctotal, r0, r1, r2, r3 in by["D"]:
+            what = (sumsq, gs, mn, skip, bc_len)
+            d = R.decide(_f64(sumsq), float(_f32(gs)), float(_f32(mn)), bool(int(skip)), st, table[:int(bc_len)])
+            same = lambda got, want: int(got, 16) == _b32(want) or (np.isnan(want) and np.isnan(_f32(got)))
+            assert same(norm, d["norm"]) and same(scale, d["scale"]) and same(gscale, d["gscale"]), what
+            assert (int(apply), int(clipped)) == (d["apply"], d["clipped"]), what
+            assert (int(applied), int(skipped), int(ctotal)) == (d["applied"], d["skipped"], d["clipped_total"]), what
+            assert int(bc1, 16) == _b32(d["bc1"]) and int(sbc2, 16) == _b32(d["sqrt_bc2"]), what
+            assert (r0, r1, r3) == (norm, scale, gscale) and _f32(r2) == float(d["apply"]), what
+            seen.add((d["apply"], d["clipped"], bool(_f32(mn) < 0), d["apply"] == 1 and int(bc_len) < d["applied"]))
+        assert st["applied"] == 12 and st["skipped"] == 2 and st["clipped_total"] >= 3      # the guard skips the inf and the NaN only
+        assert {(1, 0, False, False), (1, 1, False, False), (1, 0, True, False), (0, 0, False, False), (1, 1, False, True)} <= seen
+        # the elements
+        for p0, g, m, v, gs, wd, b1, b2, eps, lr, t, bc_len, p1, m1, v1 in by["A"]:
+            row = table[min(int(t), int(bc_len)) - 1]
+            want = R.adam_element(*(_f32(x) for x in (p0, g, m, v, gs, wd, b1, b2, eps, lr)), row[0], row[1])
+            assert [int(x, 16) for x in (p1, m1, v1)] == [_b32(x) for x in want], (p0, g, m, v, gs, wd, t)
+        assert {int(a[10]) for a in by["A"]} == {1, 3, 9}
+        forms = set()
+        for p0, g, b, gs, wd, lr, mom, damp, has_buf, first, nesterov, p1, b1 in by["S"]:
+            form = (int(has_buf), int(first), int(nesterov))
+            want = R.sgd_element(*(_f32(x) for x in (p0, g, b, gs, wd, lr, mom, damp)), *form)
+            assert [int(x, 16) for x in (p1, b1)] == [_b32(x) for x in want], (p0, g, b, gs, wd, damp, form)
+            forms.add(form)
+        assert forms == {(0, 0, 0), (0, 1, 0), (1, 1, 0), (1, 0, 0), (1, 1, 1), (1, 0, 1)}
 
 
 # ------------------------------------------------------------------------------------------------------------------------

@@ -3,8 +3,8 @@
     python -m ubresnet_amd.build [--force] [--extras]
 
 LIBS is the table of them, in build order: name -> (out, sources, headers, binding).  `hip` is libubresnet_hip.so, all HIP kernels
-of the network and its C ABI; every other entry is a self-contained library of one .hip file that links against none of the
-others, and whose purpose the docstring of its binding module states.  `sources` and `headers` are relative to csrc/, `headers`
+of the network and its C ABI; every other entry is a library of one .hip file that links against none of the
+others (csrc/ubr_sat.h is the support header they all include), and whose purpose the docstring of its binding module states.  `sources` and `headers` are relative to csrc/, `headers`
 being every file the sources reach through quoted #includes; `binding` names the ctypes module of ubresnet_amd that loads `out`.
 
 The shared libraries have NO PyTorch dependency: they are plain HIP behind the public headers in include/.  Objects are compiled
@@ -28,8 +28,9 @@ Lib = namedtuple("Lib", "out sources headers binding")
 
 
 def _satellite(name, *csrc_headers):
+    """every satellite source includes ubr_sat.h and its public header; `csrc_headers` are the other headers of csrc/ it reaches"""
     return Lib(os.path.join(HERE, "libubresnet_%s.so" % name), ["ubr_%s.hip" % name],
-               list(csrc_headers) + [os.path.join("..", "..", "include", "ubresnet_%s.h" % name)], "_" + name)
+               ["ubr_sat.h"] + list(csrc_headers) + [os.path.join("..", "..", "include", "ubresnet_%s.h" % name)], "_" + name)
 
 
 LIBS = {
@@ -37,21 +38,21 @@ LIBS = {
     "post": _satellite("post"),
     "data": _satellite("data"),
     "aug": _satellite("aug"),
-    "opt": _satellite("opt"),
+    "opt": _satellite("opt", "ubr_opt_rule.h"),
     "weight": _satellite("weight", "ubr_weight_tile.h"),
-    "group": _satellite("group", "ubr_group_plan.h"),
+    "group": _satellite("group", "ubr_group_plan.h", "ubr_opt_rule.h"),
     "ema": _satellite("ema", "ubr_ema_sched.h"),
     "accum": _satellite("accum"),
     "stats": _satellite("stats", "ubr_stats_decide.h"),
-    "loss": _satellite("loss", "ubr_loss_term.h"),
-    "dice": _satellite("dice", "ubr_dice_term.h"),
+    "loss": _satellite("loss", "ubr_loss_term.h", "ubr_rows.h"),
+    "dice": _satellite("dice", "ubr_dice_term.h", "ubr_rows.h"),
     "tta": _satellite("tta"),
     "det": _satellite("det", "ubr_det_rule.h"),
 }
 
 EXTRAS = {
     "score": Lib(os.path.join(HERE, "libubresnet_score.so"), [os.path.join("extra", "ubr_score.hip")],
-                 [os.path.join("..", "..", "include", "ubresnet_score.h")], "_score"),
+                 ["ubr_sat.h", "ubr_rows.h", os.path.join("..", "..", "include", "ubresnet_score.h")], "_score"),
 }
 
 

@@ -1,30 +1,16 @@
-// libubresnet_score.so: event products scored against a truth image (include/ubresnet_score.h).  Self-contained: nothing of
-// the other libraries is linked or included, the launch is a plain <<<>>> on the caller's stream.
+// libubresnet_score.so: event products scored against a truth image (include/ubresnet_score.h).  It links against none of the
+// other libraries and shares ubr_sat.h with them and ubr_rows.h with the loss libraries; the launch is a plain <<<>>> on the
+// caller's stream.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "../../../include/ubresnet_score.h"
+#include "../ubr_rows.h"
+#include "../ubr_sat.h"
 
 #define UBQ_VERSION 1
 
-static thread_local char g_ubq_err[512] = "";
-
-static void ubq_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_ubq_err, sizeof(g_ubq_err), fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* ubq_last_error(void) { return g_ubq_err; }
-extern "C" int ubq_version(void) { return UBQ_VERSION; }
-
-#define UBQ_CHECK(cond, ...)     \
-  do {                           \
-    if (!(cond)) {               \
-      ubq_set_error(__VA_ARGS__);\
-      return UBQ_EINVAL;         \
-    }                            \
-  } while (0)
+SAT_RETURN_CODES(UBQ);
+SAT_EXPORTS(ubq, UBQ_VERSION)
+using namespace sat;
 
 namespace {
 
@@ -53,17 +39,6 @@ struct ScoreK {
 // the class of a truth value, NONE if it is none: compared on the full width of its type, then narrowed
 __device__ __forceinline__ unsigned class_of(uint8_t v, int C) { return (int)v < C ? (unsigned)v : NONE; }
 __device__ __forceinline__ unsigned class_of(long long v, int C) { return (v >= 0ll && v < (long long)C) ? (unsigned)v : NONE; }
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-  unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const unsigned long long o = ((unsigned long long)(unsigned)__shfl_xor((int)hi, d) << 32) | (unsigned)__shfl_xor((int)lo, d);
-    v += o;
-    lo = (unsigned)v; hi = (unsigned)(v >> 32);
-  }
-  return v;
-}
 
 // grid (x: at most GRID_X workgroups that walk the tiles of a plane, row-major, GRID_X apart; y: plane).  The fewer workgroups,
 // the fewer global atomics on the same few words at the end (step 4), which is what a launch of one workgroup per tile spent
@@ -226,7 +201,7 @@ __global__ __launch_bounds__(BLOCK) void score_kernel(const ScoreK k) {
           const unsigned long long m = __ballot(member);
           const unsigned n = (unsigned)__popcll(m);
           unsigned long long sum = member ? fx : 0ull;
-          if (n > 1u) sum = wave_sum(sum);
+          if (n > 1u) sum = rowsum::wave_sum_all(sum);
           if (lane == leader) {
             const unsigned s = kk >> 14, tt = (kk >> 10) & 15u, ll = (kk >> 6) & 15u, b = kk & 63u;
             atomicAdd(&tab[(s * C + tt) * C + ll], (unsigned long long)n);
@@ -258,18 +233,16 @@ __global__ __launch_bounds__(BLOCK) void score_kernel(const ScoreK k) {
   }
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 inline long long table_words(int P, int C, int bins) { return (long long)P * (2 * C * C + 6 * bins + 4); }
 
 }  // namespace
 
 extern "C" int ubq_table_words(int P, int C, int bins) {
-  UBQ_CHECK(P >= 1, "ubq_table_words: P=%d must be >= 1", P);
-  UBQ_CHECK(C >= 1 && C <= UBQ_MAX_CLASSES, "ubq_table_words: C=%d must be 1..%d", C, UBQ_MAX_CLASSES);
-  UBQ_CHECK(bins >= 1 && bins <= UBQ_MAX_BINS, "ubq_table_words: bins=%d must be 1..%d", bins, UBQ_MAX_BINS);
+  SAT_CHECK(P >= 1, "ubq_table_words: P=%d must be >= 1", P);
+  SAT_CHECK(C >= 1 && C <= UBQ_MAX_CLASSES, "ubq_table_words: C=%d must be 1..%d", C, UBQ_MAX_CLASSES);
+  SAT_CHECK(bins >= 1 && bins <= UBQ_MAX_BINS, "ubq_table_words: bins=%d must be 1..%d", bins, UBQ_MAX_BINS);
   const long long w = table_words(P, C, bins);
-  UBQ_CHECK(w <= 0x7FFFFFFFll, "ubq_table_words: %lld words do not fit an int", w);
+  SAT_CHECK(w <= 0x7FFFFFFFll, "ubq_table_words: %lld words do not fit an int", w);
   return (int)w;
 }
 
@@ -278,29 +251,29 @@ extern "C" int ubq_score_event(const uint8_t* label, const uint16_t* confidence,
                                const uint16_t* edges_host, int bins,
                                unsigned long long* table, int P, int rows, int cols, void* stream) {
   // the scalar arguments first, the pointers last: a refusal names the first thing that is wrong with the call
-  UBQ_CHECK(truth_kind == UBQ_TRUTH_U8 || truth_kind == UBQ_TRUTH_I64, "ubq_score_event: truth_kind=%d must be %d (uint8) or %d (int64)",
+  SAT_CHECK(truth_kind == UBQ_TRUTH_U8 || truth_kind == UBQ_TRUTH_I64, "ubq_score_event: truth_kind=%d must be %d (uint8) or %d (int64)",
             truth_kind, UBQ_TRUTH_U8, UBQ_TRUTH_I64);
-  UBQ_CHECK(C >= 1 && C <= UBQ_MAX_CLASSES, "ubq_score_event: C=%d must be 1..%d", C, UBQ_MAX_CLASSES);
-  UBQ_CHECK(fill_label >= 0 && fill_label <= 255, "ubq_score_event: fill_label=%d must be 0..255", fill_label);
-  UBQ_CHECK(radius >= 0 && radius <= UBQ_MAX_RADIUS, "ubq_score_event: radius=%d must be 0..%d", radius, UBQ_MAX_RADIUS);
-  UBQ_CHECK(interface_from >= 0 && interface_from <= C, "ubq_score_event: interface_from=%d must be 0..C=%d", interface_from, C);
-  UBQ_CHECK(bins >= 1 && bins <= UBQ_MAX_BINS, "ubq_score_event: bins=%d must be 1..%d", bins, UBQ_MAX_BINS);
-  UBQ_CHECK(P >= 1 && P <= 65535 && rows >= 1 && cols >= 1, "ubq_score_event: P=%d must be 1..65535, rows=%d and cols=%d >= 1", P, rows, cols);
-  UBQ_CHECK(bins == 1 || edges_host, "ubq_score_event: edges_host is null with bins=%d", bins);
+  SAT_CHECK(C >= 1 && C <= UBQ_MAX_CLASSES, "ubq_score_event: C=%d must be 1..%d", C, UBQ_MAX_CLASSES);
+  SAT_CHECK(fill_label >= 0 && fill_label <= 255, "ubq_score_event: fill_label=%d must be 0..255", fill_label);
+  SAT_CHECK(radius >= 0 && radius <= UBQ_MAX_RADIUS, "ubq_score_event: radius=%d must be 0..%d", radius, UBQ_MAX_RADIUS);
+  SAT_CHECK(interface_from >= 0 && interface_from <= C, "ubq_score_event: interface_from=%d must be 0..C=%d", interface_from, C);
+  SAT_CHECK(bins >= 1 && bins <= UBQ_MAX_BINS, "ubq_score_event: bins=%d must be 1..%d", bins, UBQ_MAX_BINS);
+  SAT_CHECK(P >= 1 && P <= 65535 && rows >= 1 && cols >= 1, "ubq_score_event: P=%d must be 1..65535, rows=%d and cols=%d >= 1", P, rows, cols);
+  SAT_CHECK(bins == 1 || edges_host, "ubq_score_event: edges_host is null with bins=%d", bins);
   ScoreK k{};
   for (int e = 0; e < bins - 1; ++e) {
     const unsigned h = edges_host[e];
-    UBQ_CHECK(h >= 0x0001u && h <= 0x7BFFu, "ubq_score_event: edge %d (0x%04X) is not a positive finite half", e, h);
-    UBQ_CHECK(e == 0 || h > edges_host[e - 1], "ubq_score_event: edges not strictly ascending at %d (0x%04X after 0x%04X)", e, h,
+    SAT_CHECK(h >= 0x0001u && h <= 0x7BFFu, "ubq_score_event: edge %d (0x%04X) is not a positive finite half", e, h);
+    SAT_CHECK(e == 0 || h > edges_host[e - 1], "ubq_score_event: edges not strictly ascending at %d (0x%04X after 0x%04X)", e, h,
               (unsigned)edges_host[e - 1]);
     k.edges[e] = (uint16_t)h;
   }
   const long long tiles_x = ((long long)cols + TW - 1) / TW, tiles_y = ((long long)rows + TH - 1) / TH;
-  UBQ_CHECK(tiles_x * tiles_y <= 0x7FFFFFFFll, "ubq_score_event: %lld x %lld tiles exceed the grid", tiles_y, tiles_x);
-  UBQ_CHECK(table_words(P, C, bins) <= 0x7FFFFFFFll, "ubq_score_event: the table does not fit an int of words");
-  UBQ_CHECK(label && confidence && truth && table, "ubq_score_event: null pointer (label %p, confidence %p, truth %p, table %p)",
+  SAT_CHECK(tiles_x * tiles_y <= 0x7FFFFFFFll, "ubq_score_event: %lld x %lld tiles exceed the grid", tiles_y, tiles_x);
+  SAT_CHECK(table_words(P, C, bins) <= 0x7FFFFFFFll, "ubq_score_event: the table does not fit an int of words");
+  SAT_CHECK(label && confidence && truth && table, "ubq_score_event: null pointer (label %p, confidence %p, truth %p, table %p)",
             (const void*)label, (const void*)confidence, truth, (void*)table);
-  UBQ_CHECK(aligned(confidence, 2) && aligned(table, 8) && (truth_kind == UBQ_TRUTH_U8 || aligned(truth, 8)),
+  SAT_CHECK(aligned(confidence, 2) && aligned(table, 8) && (truth_kind == UBQ_TRUTH_U8 || aligned(truth, 8)),
             "ubq_score_event: a pointer lacks its natural alignment (2 bytes for a half, 8 for a 64-bit integer)");
   k.label = label; k.conf = confidence; k.truth = truth; k.table = table;
   k.rows = rows; k.cols = cols; k.C = C; k.fill = fill_label; k.R = radius; k.lo = interface_from; k.bins = bins;
@@ -314,10 +287,6 @@ extern "C" int ubq_score_event(const uint8_t* label, const uint16_t* confidence,
     score_kernel<uint8_t><<<grid, block, 0, (hipStream_t)stream>>>(k);
   else
     score_kernel<long long><<<grid, block, 0, (hipStream_t)stream>>>(k);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    ubq_set_error("ubq_score_event: launch failed: %s", hipGetErrorString(e));
-    return UBQ_ELAUNCH;
-  }
+  SAT_LAUNCH_CHECK("ubq_score_event");
   return UBQ_OK;
 }

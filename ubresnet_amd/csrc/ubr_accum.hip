@@ -1,41 +1,16 @@
-// libubresnet_accum.so: gradient accumulation over the flat gradient buffer (include/ubresnet_accum.h).  Self-contained: nothing
-// of the other eight libraries is linked or included, the launches are plain <<<>>> on the caller's stream.
+// libubresnet_accum.so: gradient accumulation over the flat gradient buffer (include/ubresnet_accum.h).  It links against none of
+// the other libraries and shares ubr_sat.h with them; the launches are plain <<<>>> on the caller's stream.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "../../include/ubresnet_accum.h"
+#include "ubr_sat.h"
 
 #define UBC_VERSION 1
 #define UBC_TRIP (UBC_BLOCK * UBC_UNROLL)
 
-static thread_local char g_ubc_err[512] = "";
-
-static void ubc_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_ubc_err, sizeof(g_ubc_err), fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* ubc_last_error(void) { return g_ubc_err; }
-extern "C" int ubc_version(void) { return UBC_VERSION; }
-
-#define UBC_CHECK(cond, ...)     \
-  do {                           \
-    if (!(cond)) {               \
-      ubc_set_error(__VA_ARGS__);\
-      return UBC_EINVAL;         \
-    }                            \
-  } while (0)
-
-#define UBC_LAUNCH_CHECK(name)                                              \
-  do {                                                                      \
-    hipError_t e_ = hipGetLastError();                                      \
-    if (e_ != hipSuccess) {                                                 \
-      ubc_set_error(name ": launch failed: %s", hipGetErrorString(e_));     \
-      return UBC_ELAUNCH;                                                   \
-    }                                                                       \
-  } while (0)
+SAT_RETURN_CODES(UBC);
+SAT_EXPORTS(ubc, UBC_VERSION)
+using namespace sat;
 
 namespace {
 
@@ -111,13 +86,6 @@ __global__ __launch_bounds__(UBC_BLOCK) void finish_kernel(float4* __restrict__ 
   }
 }
 
-inline bool aligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) == 0; }
-
-inline bool overlap(const void* a, unsigned long long abytes, const void* b, unsigned long long bbytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x != 0 && y != 0 && x < y + bbytes && y < x + abytes;
-}
-
 inline unsigned flat_grid(long n4) {
   long grid = (n4 + UBC_TRIP - 1) / UBC_TRIP;
   return (unsigned)(grid > UBC_MAX_GRID ? UBC_MAX_GRID : grid);
@@ -127,16 +95,16 @@ inline unsigned flat_grid(long n4) {
 
 // the checks the three calls share; `name` starts the message
 #define UBC_CHECK_PAIR(name, acc, grad, n)                                                                                    \
-  UBC_CHECK((acc) && (grad), name ": null pointer (acc, grad)");                                                             \
-  UBC_CHECK((n) > 0 && (n) % 4 == 0, name ": n=%lld must be positive and a multiple of 4", (long long)(n));                  \
-  UBC_CHECK(aligned((acc), 16) && aligned((grad), 16), name ": acc and grad must be 16-byte aligned");                       \
-  UBC_CHECK(!overlap((acc), 4ull * (unsigned long long)(n), (grad), 4ull * (unsigned long long)(n)), name ": acc overlaps grad")
+  SAT_CHECK((acc) && (grad), name ": null pointer (acc, grad)");                                                             \
+  SAT_CHECK((n) > 0 && (n) % 4 == 0, name ": n=%lld must be positive and a multiple of 4", (long long)(n));                  \
+  SAT_CHECK(aligned((acc), 16) && aligned((grad), 16), name ": acc and grad must be 16-byte aligned");                       \
+  SAT_CHECK(!overlap((acc), 4ull * (unsigned long long)(n), (grad), 4ull * (unsigned long long)(n)), name ": acc overlaps grad")
 
 extern "C" int ubc_set(float* acc, const float* grad, int64_t n, void* stream) {
   UBC_CHECK_PAIR("ubc_set", acc, grad, n);
   const long n4 = (long)(n / 4);
   set_kernel<<<dim3(flat_grid(n4)), dim3(UBC_BLOCK), 0, (hipStream_t)stream>>>((uint4*)acc, (const uint4*)grad, n4);
-  UBC_LAUNCH_CHECK("ubc_set");
+  SAT_LAUNCH_CHECK("ubc_set");
   return UBC_OK;
 }
 
@@ -144,16 +112,16 @@ extern "C" int ubc_add(float* acc, const float* grad, int64_t n, void* stream) {
   UBC_CHECK_PAIR("ubc_add", acc, grad, n);
   const long n4 = (long)(n / 4);
   add_kernel<<<dim3(flat_grid(n4)), dim3(UBC_BLOCK), 0, (hipStream_t)stream>>>((float4*)acc, (const float4*)grad, n4);
-  UBC_LAUNCH_CHECK("ubc_add");
+  SAT_LAUNCH_CHECK("ubc_add");
   return UBC_OK;
 }
 
 extern "C" int ubc_finish(float* grad, const float* acc, int64_t n, float scale, void* stream) {
   UBC_CHECK_PAIR("ubc_finish", acc, grad, n);
-  UBC_CHECK(scale == scale, "ubc_finish: scale is NaN");
-  UBC_CHECK(scale > 0.f && scale < INFINITY, "ubc_finish: scale=%g must be finite and > 0", (double)scale);
+  SAT_CHECK(scale == scale, "ubc_finish: scale is NaN");
+  SAT_CHECK(scale > 0.f && scale < INFINITY, "ubc_finish: scale=%g must be finite and > 0", (double)scale);
   const long n4 = (long)(n / 4);
   finish_kernel<<<dim3(flat_grid(n4)), dim3(UBC_BLOCK), 0, (hipStream_t)stream>>>((float4*)grad, (const float4*)acc, n4, scale);
-  UBC_LAUNCH_CHECK("ubc_finish");
+  SAT_LAUNCH_CHECK("ubc_finish");
   return UBC_OK;
 }

@@ -1,31 +1,15 @@
-// libubresnet_aug.so: device-side augmentation of training batches (include/ubresnet_aug.h).  Self-contained: nothing of the
-// other three libraries is linked or included, the launch is a plain <<<>>> on the caller's stream.
+// libubresnet_aug.so: device-side augmentation of training batches (include/ubresnet_aug.h).  It links against none of the other
+// libraries and shares ubr_sat.h with them; the launch is a plain <<<>>> on the caller's stream.
 #include <hip/hip_runtime.h>
 #include <limits.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "../../include/ubresnet_aug.h"
+#include "ubr_sat.h"
 
 #define UBA_VERSION 1
 
-static thread_local char g_uba_err[512] = "";
-
-static void uba_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_uba_err, sizeof(g_uba_err), fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* uba_last_error(void) { return g_uba_err; }
-extern "C" int uba_version(void) { return UBA_VERSION; }
-
-#define UBA_CHECK(cond, ...)     \
-  do {                           \
-    if (!(cond)) {               \
-      uba_set_error(__VA_ARGS__);\
-      return UBA_EINVAL;         \
-    }                            \
-  } while (0)
+SAT_RETURN_CODES(UBA);
+SAT_EXPORTS(uba, UBA_VERSION)
+using namespace sat;
 
 namespace {
 
@@ -142,8 +126,6 @@ __global__ __launch_bounds__(UBA_BLOCK) void augment_batch_kernel(const AugK k) 
   }
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 struct Region {
   const char* name;
   uintptr_t lo;
@@ -161,23 +143,23 @@ extern "C" int uba_augment_batch(const float* image, const float* label_wire, co
                                  int B, int P, int H, int W, int pad, const int32_t* params,
                                  int32_t label_offset, int use_threshold, float threshold,
                                  int32_t pad_label, float pad_weight, void* stream) {
-  UBA_CHECK(image && label_wire, "uba_augment_batch: null source pointer (image, label_wire)");
-  UBA_CHECK(image_out && label_out && weight_out, "uba_augment_batch: null destination pointer (image_out, label_out, weight_out)");
-  UBA_CHECK(params, "uba_augment_batch: null params");
-  UBA_CHECK(B >= 1 && P >= 1 && H >= 1 && W >= 1, "uba_augment_batch: B=%d P=%d H=%d W=%d must all be >= 1", B, P, H, W);
-  UBA_CHECK(B <= UBA_MAX_BATCH, "uba_augment_batch: B=%d exceeds UBA_MAX_BATCH=%d", B, UBA_MAX_BATCH);
+  SAT_CHECK(image && label_wire, "uba_augment_batch: null source pointer (image, label_wire)");
+  SAT_CHECK(image_out && label_out && weight_out, "uba_augment_batch: null destination pointer (image_out, label_out, weight_out)");
+  SAT_CHECK(params, "uba_augment_batch: null params");
+  SAT_CHECK(B >= 1 && P >= 1 && H >= 1 && W >= 1, "uba_augment_batch: B=%d P=%d H=%d W=%d must all be >= 1", B, P, H, W);
+  SAT_CHECK(B <= UBA_MAX_BATCH, "uba_augment_batch: B=%d exceeds UBA_MAX_BATCH=%d", B, UBA_MAX_BATCH);
   const long long npix = (long long)B * H * W;
-  UBA_CHECK(npix < (1ll << 31), "uba_augment_batch: B*H*W=%lld must be below 2^31", npix);
-  UBA_CHECK(pad >= 0 && pad <= UBA_MAX_PAD, "uba_augment_batch: pad=%d must be 0..%d", pad, UBA_MAX_PAD);
-  UBA_CHECK(aligned(image, 4) && aligned(label_wire, 4) && aligned(weight, 4) && aligned(image_out, 4) &&
+  SAT_CHECK(npix < (1ll << 31), "uba_augment_batch: B*H*W=%lld must be below 2^31", npix);
+  SAT_CHECK(pad >= 0 && pad <= UBA_MAX_PAD, "uba_augment_batch: pad=%d must be 0..%d", pad, UBA_MAX_PAD);
+  SAT_CHECK(aligned(image, 4) && aligned(label_wire, 4) && aligned(weight, 4) && aligned(image_out, 4) &&
                 aligned(label_out, 8) && aligned(weight_out, 4),
             "uba_augment_batch: a pointer lacks its natural alignment (4 bytes for float, 8 for int64_t)");
   AugK k{};
   for (int b = 0; b < B; ++b) {
     const int32_t* q = params + 4 * b;
-    UBA_CHECK((q[0] == 0 || q[0] == 1) && (q[1] == 0 || q[1] == 1),
+    SAT_CHECK((q[0] == 0 || q[0] == 1) && (q[1] == 0 || q[1] == 1),
               "uba_augment_batch: image %d: flips (%d, %d) must be 0 or 1", b, (int)q[0], (int)q[1]);
-    UBA_CHECK(q[2] >= 0 && q[2] <= 2 * pad && q[3] >= 0 && q[3] <= 2 * pad,
+    SAT_CHECK(q[2] >= 0 && q[2] <= 2 * pad && q[3] >= 0 && q[3] <= 2 * pad,
               "uba_augment_batch: image %d: offsets (%d, %d) must be 0..2*pad=%d", b, (int)q[2], (int)q[3], 2 * pad);
     k.par[b] = (unsigned)q[0] | (unsigned)q[1] << 1 | (unsigned)q[2] << 2 | (unsigned)q[3] << 17;
   }
@@ -188,9 +170,9 @@ extern "C" int uba_augment_batch(const float* image, const float* label_wire, co
                          {"weight_out", (uintptr_t)weight_out, pix4}};
   for (int d = 0; d < 3; ++d) {
     for (int s = 0; s < 3; ++s)
-      UBA_CHECK(!overlap(src[s], dst[d]), "uba_augment_batch: %s overlaps %s (the call works out of place)", src[s].name, dst[d].name);
+      SAT_CHECK(!overlap(src[s], dst[d]), "uba_augment_batch: %s overlaps %s (the call works out of place)", src[s].name, dst[d].name);
     for (int e = d + 1; e < 3; ++e)
-      UBA_CHECK(!overlap(dst[d], dst[e]), "uba_augment_batch: %s overlaps %s", dst[d].name, dst[e].name);
+      SAT_CHECK(!overlap(dst[d], dst[e]), "uba_augment_batch: %s overlaps %s", dst[d].name, dst[e].name);
   }
   k.img = image; k.lab = label_wire; k.wgt = weight;
   k.oimg = image_out; k.olab = (long long*)label_out; k.owgt = weight_out;
@@ -205,10 +187,6 @@ extern "C" int uba_augment_batch(const float* image, const float* label_wire, co
     augment_batch_kernel<true><<<dim3((unsigned)blocks), dim3(UBA_BLOCK), 0, (hipStream_t)stream>>>(k);
   else
     augment_batch_kernel<false><<<dim3((unsigned)blocks), dim3(UBA_BLOCK), 0, (hipStream_t)stream>>>(k);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    uba_set_error("uba_augment_batch: launch failed: %s", hipGetErrorString(e));
-    return UBA_ELAUNCH;
-  }
+  SAT_LAUNCH_CHECK("uba_augment_batch");
   return UBA_OK;
 }

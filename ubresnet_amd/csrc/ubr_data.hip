@@ -1,31 +1,15 @@
-// libubresnet_data.so: device-side batch preparation of the training loader (include/ubresnet_data.h).  Self-contained:
-// nothing of the other two libraries is linked or included, launches are plain <<<>>> on the caller's stream.
+// libubresnet_data.so: device-side batch preparation of the training loader (include/ubresnet_data.h).  It links against none of
+// the other libraries and shares ubr_sat.h with them; launches are plain <<<>>> on the caller's stream.
 #include <hip/hip_runtime.h>
 #include <limits.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "../../include/ubresnet_data.h"
+#include "ubr_sat.h"
 
 #define UBD_VERSION 1
 
-static thread_local char g_ubd_err[512] = "";
-
-static void ubd_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_ubd_err, sizeof(g_ubd_err), fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* ubd_last_error(void) { return g_ubd_err; }
-extern "C" int ubd_version(void) { return UBD_VERSION; }
-
-#define UBD_CHECK(cond, ...)     \
-  do {                           \
-    if (!(cond)) {               \
-      ubd_set_error(__VA_ARGS__);\
-      return UBD_EINVAL;         \
-    }                            \
-  } while (0)
+SAT_RETURN_CODES(UBD);
+SAT_EXPORTS(ubd, UBD_VERSION)
+using namespace sat;
 
 namespace {
 
@@ -133,21 +117,19 @@ __global__ __launch_bounds__(UBD_BLOCK) void prep_batch_kernel(const PrepK k) {
   }
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int ubd_prep_batch(const float* label_wire, int64_t* label, int64_t n, int32_t label_offset,
                               float* image, int planes, int64_t hw, int use_threshold, float threshold,
                               float* weight_fill, void* stream) {
-  UBD_CHECK(label_wire && label, "ubd_prep_batch: null label pointer");
-  UBD_CHECK(n >= 1 && n < (1ll << 31), "ubd_prep_batch: n=%lld must be 1..2^31-1", (long long)n);
-  UBD_CHECK(planes >= 1, "ubd_prep_batch: planes=%d must be >= 1", planes);
-  UBD_CHECK(aligned(label_wire, 4) && aligned(label, 8) && aligned(image, 4) && aligned(weight_fill, 4),
+  SAT_CHECK(label_wire && label, "ubd_prep_batch: null label pointer");
+  SAT_CHECK(n >= 1 && n < (1ll << 31), "ubd_prep_batch: n=%lld must be 1..2^31-1", (long long)n);
+  SAT_CHECK(planes >= 1, "ubd_prep_batch: planes=%d must be >= 1", planes);
+  SAT_CHECK(aligned(label_wire, 4) && aligned(label, 8) && aligned(image, 4) && aligned(weight_fill, 4),
             "ubd_prep_batch: a pointer lacks its natural alignment (4 bytes for float, 8 for int64_t)");
   if (use_threshold) {
-    UBD_CHECK(image, "ubd_prep_batch: the threshold is on and image is null");
-    UBD_CHECK(hw >= 1 && hw <= n && n % hw == 0, "ubd_prep_batch: hw=%lld must be >= 1 and divide n=%lld", (long long)hw, (long long)n);
+    SAT_CHECK(image, "ubd_prep_batch: the threshold is on and image is null");
+    SAT_CHECK(hw >= 1 && hw <= n && n % hw == 0, "ubd_prep_batch: hw=%lld must be >= 1 and divide n=%lld", (long long)hw, (long long)n);
   }
   PrepK k{};
   k.lab = label_wire; k.out = (long long*)label; k.img = use_threshold ? image : nullptr; k.wgt = weight_fill;
@@ -162,10 +144,6 @@ extern "C" int ubd_prep_batch(const float* label_wire, int64_t* label, int64_t n
     prep_batch_kernel<true><<<dim3((unsigned)blocks), dim3(UBD_BLOCK), 0, (hipStream_t)stream>>>(k);
   else
     prep_batch_kernel<false><<<dim3((unsigned)blocks), dim3(UBD_BLOCK), 0, (hipStream_t)stream>>>(k);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    ubd_set_error("ubd_prep_batch: launch failed: %s", hipGetErrorString(e));
-    return UBD_ELAUNCH;
-  }
+  SAT_LAUNCH_CHECK("ubd_prep_batch");
   return UBD_OK;
 }

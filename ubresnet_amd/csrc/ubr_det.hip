@@ -1,32 +1,16 @@
-// libubresnet_det.so: detector effects on a prepared training batch, in place (include/ubresnet_det.h).  Self-contained:
-// nothing of the other libraries is linked or included, the launch is a plain <<<>>> on the caller's stream.
+// libubresnet_det.so: detector effects on a prepared training batch, in place (include/ubresnet_det.h).  It links against none of
+// the other libraries and shares ubr_sat.h with them; the launch is a plain <<<>>> on the caller's stream.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "../../include/ubresnet_det.h"
 #include "ubr_det_rule.h"
+#include "ubr_sat.h"
 
 #define UBX_VERSION 1
 
-static thread_local char g_ubx_err[512] = "";
-
-static void ubx_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_ubx_err, sizeof(g_ubx_err), fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* ubx_last_error(void) { return g_ubx_err; }
-extern "C" int ubx_version(void) { return UBX_VERSION; }
-
-#define UBX_CHECK(cond, ...)     \
-  do {                           \
-    if (!(cond)) {               \
-      ubx_set_error(__VA_ARGS__);\
-      return UBX_EINVAL;         \
-    }                            \
-  } while (0)
+SAT_RETURN_CODES(UBX);
+SAT_EXPORTS(ubx, UBX_VERSION)
+using namespace sat;
 
 namespace {
 
@@ -123,8 +107,6 @@ __global__ __launch_bounds__(UBX_BLOCK) void detector_kernel(const DetK k) {
   }
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 struct Region {
   const char* name;
   uintptr_t lo;
@@ -140,15 +122,15 @@ inline bool overlap(const Region& a, const Region& b) {
 extern "C" int ubx_apply(float* image, int64_t* label, float* weight, int B, int P, int H, int W, const uint32_t* table,
                          float sigma, int noise_all, uint32_t seed, uint32_t seq,
                          int set_label, int64_t dead_label, int set_weight, float dead_weight, void* stream) {
-  UBX_CHECK(image && table, "ubx_apply: null pointer (image, table)");
-  UBX_CHECK(label || !set_label, "ubx_apply: null label with set_label");
-  UBX_CHECK(weight || !set_weight, "ubx_apply: null weight with set_weight");
-  UBX_CHECK(B >= 1 && P >= 1 && H >= 1 && W >= 1, "ubx_apply: B=%d P=%d H=%d W=%d must all be >= 1", B, P, H, W);
+  SAT_CHECK(image && table, "ubx_apply: null pointer (image, table)");
+  SAT_CHECK(label || !set_label, "ubx_apply: null label with set_label");
+  SAT_CHECK(weight || !set_weight, "ubx_apply: null weight with set_weight");
+  SAT_CHECK(B >= 1 && P >= 1 && H >= 1 && W >= 1, "ubx_apply: B=%d P=%d H=%d W=%d must all be >= 1", B, P, H, W);
   const long long npix = (long long)B * H * W;
-  UBX_CHECK(npix < (1ll << 31), "ubx_apply: B*H*W=%lld must be below 2^31", npix);
-  UBX_CHECK(isfinite(sigma) && sigma >= 0.0f, "ubx_apply: sigma=%g must be finite and >= 0", (double)sigma);
-  UBX_CHECK(isfinite(dead_weight), "ubx_apply: dead_weight=%g must be finite", (double)dead_weight);
-  UBX_CHECK(aligned(image, 4) && aligned(label, 8) && aligned(weight, 4) && aligned(table, 4),
+  SAT_CHECK(npix < (1ll << 31), "ubx_apply: B*H*W=%lld must be below 2^31", npix);
+  SAT_CHECK(isfinite(sigma) && sigma >= 0.0f, "ubx_apply: sigma=%g must be finite and >= 0", (double)sigma);
+  SAT_CHECK(isfinite(dead_weight), "ubx_apply: dead_weight=%g must be finite", (double)dead_weight);
+  SAT_CHECK(aligned(image, 4) && aligned(label, 8) && aligned(weight, 4) && aligned(table, 4),
             "ubx_apply: a pointer lacks its natural alignment (4 bytes for float and uint32, 8 for int64_t)");
   const int rowwords = 1 + (W + 31) / 32;
   const unsigned long long pix4 = 4ull * (unsigned long long)npix;
@@ -156,7 +138,7 @@ extern "C" int ubx_apply(float* image, int64_t* label, float* weight, int B, int
                          {"weight", (uintptr_t)weight, pix4}, {"table", (uintptr_t)table, 4ull * B * P * rowwords}};
   for (int d = 0; d < 4; ++d)
     for (int e = d + 1; e < 4; ++e)
-      UBX_CHECK(!overlap(reg[d], reg[e]), "ubx_apply: %s overlaps %s", reg[d].name, reg[e].name);
+      SAT_CHECK(!overlap(reg[d], reg[e]), "ubx_apply: %s overlaps %s", reg[d].name, reg[e].name);
   DetK k{};
   k.img = image; k.lab = (long long*)label; k.wgt = weight; k.tab = table;
   k.P = P; k.H = H; k.W = W;
@@ -174,10 +156,6 @@ extern "C" int ubx_apply(float* image, int64_t* label, float* weight, int B, int
     detector_kernel<true><<<dim3((unsigned)blocks), dim3(UBX_BLOCK), 0, (hipStream_t)stream>>>(k);
   else
     detector_kernel<false><<<dim3((unsigned)blocks), dim3(UBX_BLOCK), 0, (hipStream_t)stream>>>(k);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    ubx_set_error("ubx_apply: launch failed: %s", hipGetErrorString(e));
-    return UBX_ELAUNCH;
-  }
+  SAT_LAUNCH_CHECK("ubx_apply");
   return UBX_OK;
 }

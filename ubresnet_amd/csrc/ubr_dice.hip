@@ -1,16 +1,16 @@
-// libubresnet_dice.so: the soft Dice / Tversky region loss (include/ubresnet_dice.h).  Self-contained: nothing of the other eleven
-// libraries is linked or included, the launches are plain <<<>>> on the caller's stream, and there is no atomic operation: the
-// forward's streaming pass leaves one row of partials per workgroup, one workgroup adds the rows in a fixed order and derives the
-// two coefficients per class that the backward multiplies with.
+// libubresnet_dice.so: the soft Dice / Tversky region loss (include/ubresnet_dice.h).  It links against none of the other
+// libraries and shares ubr_sat.h with them, and ubr_rows.h with ubr_loss.hip; the launches are plain <<<>>> on the caller's
+// stream, and there is no atomic operation: the forward's streaming pass leaves one row of partials per workgroup, one workgroup
+// adds the rows in a fixed order and derives the two coefficients per class that the backward multiplies with.
 //
 // The class of every addend is a channel index, not the data-dependent target: FP_c always, TP_c and FN_c by a select on t == c.
 // So a lane keeps its 3 C fp64 sums and C counts in registers; the forward is instantiated for C = 1 .. UBK_REG_CLASSES, and once
 // with the class loop bounded by the runtime C for the rest (up to 16: the same code, more registers, fewer waves).
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "ubr_dice_term.h"
+#include "ubr_rows.h"
+#include "ubr_sat.h"
 
 #define UBK_VERSION 1
 #define UBK_TRIP_UNITS (UBK_BLOCK * UBK_UNROLL)
@@ -19,54 +19,12 @@
 #define UBK_FINISH_LANES (UBK_FINISH_SUB * UBK_ROW_WORDS)  /* 528: one per (sequence, word) */
 #define UBK_FINISH_BLOCK 576                               /* the next multiple of the wave */
 
-static thread_local char g_ubk_err[512] = "";
-
-static void ubk_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_ubk_err, sizeof(g_ubk_err), fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* ubk_last_error(void) { return g_ubk_err; }
-extern "C" int ubk_version(void) { return UBK_VERSION; }
-
-#define UBK_CHECK(cond, ...)     \
-  do {                           \
-    if (!(cond)) {               \
-      ubk_set_error(__VA_ARGS__);\
-      return UBK_EINVAL;         \
-    }                            \
-  } while (0)
-
-#define UBK_LAUNCH_CHECK(name)                                              \
-  do {                                                                      \
-    hipError_t e_ = hipGetLastError();                                      \
-    if (e_ != hipSuccess) {                                                 \
-      ubk_set_error(name ": launch failed: %s", hipGetErrorString(e_));     \
-      return UBK_ELAUNCH;                                                   \
-    }                                                                       \
-  } while (0)
+SAT_RETURN_CODES(UBK);
+SAT_EXPORTS(ubk, UBK_VERSION)
+using namespace sat;
+using namespace rowsum;
 
 namespace {
-
-typedef long long ll2 __attribute__((ext_vector_type(2)));
-typedef unsigned long long u64;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  return v;
-}
-
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  return v;
-}
-
-__device__ __forceinline__ bool contributes(long long t, int C, long long ignore_index) {
-  return t != ignore_index && t >= 0 && t < C;
-}
 
 // what a lane keeps over its trips; CM is the bound of the unrolled class loops, so every index is a constant
 template <int CM>
@@ -204,18 +162,8 @@ __global__ __launch_bounds__(UBK_BLOCK) void dice_fwd_kernel(const float* __rest
     wave_row[wave][UBK_ROW_BAD] = bad;
   }
   __syncthreads();
-  if (lane < UBK_ROW_WORDS) {
-    u64 out;
-    if (lane >= UBK_ROW_PIXELS) {
-      out = 0ull;
-      for (int w = 0; w < UBK_BLOCK / 64; ++w) out += wave_row[w][lane];
-    } else {
-      double d = 0.0;
-      for (int w = 0; w < UBK_BLOCK / 64; ++w) d += __longlong_as_double((long long)wave_row[w][lane]);
-      out = (u64)__double_as_longlong(d);
-    }
-    rows[(long)blockIdx.x * UBK_ROW_WORDS + lane] = out;
-  }
+  if (lane < UBK_ROW_WORDS)
+    rows[(long)blockIdx.x * UBK_ROW_WORDS + lane] = add_wave_rows(wave_row, lane, lane >= UBK_ROW_PIXELS);
 }
 
 // One workgroup: lane (q, word) adds word `word` of the rows q, q + 8, q + 16, .. in that order; then lane `word` adds the 8
@@ -230,27 +178,10 @@ __global__ __launch_bounds__(UBK_FINISH_BLOCK) void dice_finish_kernel(const u64
   const int tid = threadIdx.x;
   const int word = tid % UBK_ROW_WORDS, q = tid / UBK_ROW_WORDS;
   const bool integer = word >= UBK_ROW_PIXELS;
-  u64 ai = 0ull;
-  double ad = 0.0;
-  if (tid < UBK_FINISH_LANES) {
-#pragma unroll 8
-    for (int r = q; r < nrows; r += UBK_FINISH_SUB) {
-      const u64 v = rows[(long)r * UBK_ROW_WORDS + word];
-      ai += integer ? v : 0ull;
-      ad += integer ? 0.0 : __longlong_as_double((long long)v);
-    }
-    sub[q][word] = integer ? ai : (u64)__double_as_longlong(ad);
-  }
+  if (tid < UBK_FINISH_LANES) sub[q][word] = sequence_sum<UBK_FINISH_SUB, UBK_ROW_WORDS>(rows, nrows, q, word, integer);
   __syncthreads();
   if (tid < UBK_ROW_WORDS) {
-    ai = 0ull;
-    ad = 0.0;
-    for (int k = 0; k < UBK_FINISH_SUB; ++k) {
-      const u64 v = sub[k][word];
-      ai += integer ? v : 0ull;
-      ad += integer ? 0.0 : __longlong_as_double((long long)v);
-    }
-    const u64 out = integer ? ai : (u64)__double_as_longlong(ad);
+    const u64 out = sequences_sum(sub, word, integer);
     tot[word] = out;
     ctl[word] = out;          // ctl words 0 .. 65 are the row words
   }
@@ -375,13 +306,6 @@ __global__ __launch_bounds__(UBK_BLOCK) void dice_bwd_kernel(const float* __rest
   }
 }
 
-inline bool aligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) == 0; }
-
-inline bool overlap(const void* a, unsigned long long abytes, const void* b, unsigned long long bbytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x != 0 && y != 0 && x < y + bbytes && y < x + abytes;
-}
-
 inline unsigned grid_of(long total) {
   long grid = (total + UBK_TRIP_PIXELS - 1) / UBK_TRIP_PIXELS;
   return (unsigned)(grid > UBK_MAX_GRID ? UBK_MAX_GRID : grid);
@@ -402,27 +326,27 @@ void launch_fwd(bool vec, unsigned grid, hipStream_t stream, const float* predic
 
 // the checks the two calls share; `name` starts the message
 #define UBK_CHECK_OPERANDS(name, predict, target, pixelweights, N, C, H, W)                                                      \
-  UBK_CHECK((predict) && (target) && (pixelweights), name ": null pointer (predict, target, pixelweights)");                     \
-  UBK_CHECK((N) > 0 && (H) > 0 && (W) > 0, name ": bad extents N=%d H=%d W=%d", (N), (H), (W));                                   \
-  UBK_CHECK((C) >= 1 && (C) <= UBK_MAX_CLASSES, name ": C=%d must be in [1, %d]", (C), UBK_MAX_CLASSES);                          \
-  UBK_CHECK(aligned((predict), 4) && aligned((pixelweights), 4) && aligned((target), 8),                                         \
+  SAT_CHECK((predict) && (target) && (pixelweights), name ": null pointer (predict, target, pixelweights)");                     \
+  SAT_CHECK((N) > 0 && (H) > 0 && (W) > 0, name ": bad extents N=%d H=%d W=%d", (N), (H), (W));                                   \
+  SAT_CHECK((C) >= 1 && (C) <= UBK_MAX_CLASSES, name ": C=%d must be in [1, %d]", (C), UBK_MAX_CLASSES);                          \
+  SAT_CHECK(aligned((predict), 4) && aligned((pixelweights), 4) && aligned((target), 8),                                         \
             name ": predict and pixelweights must be 4-byte aligned, target 8-byte aligned")
 
 extern "C" int ubk_dice_fwd(const float* predict, const int64_t* target, const float* pixelweights, const float* classw,
                             int N, int C, int H, int W, int64_t ignore_index, float alpha, float beta, float eps, int present_only,
                             void* workspace, void* ctl, float* loss, void* stream) {
   UBK_CHECK_OPERANDS("ubk_dice_fwd", predict, target, pixelweights, N, C, H, W);
-  UBK_CHECK(workspace && ctl && loss, "ubk_dice_fwd: null pointer (workspace, ctl, loss)");
-  UBK_CHECK(finite_nonneg(alpha), "ubk_dice_fwd: alpha=%g must be finite and >= 0", (double)alpha);
-  UBK_CHECK(finite_nonneg(beta), "ubk_dice_fwd: beta=%g must be finite and >= 0", (double)beta);
-  UBK_CHECK(finite_nonneg(eps), "ubk_dice_fwd: eps=%g must be finite and >= 0", (double)eps);
-  UBK_CHECK(present_only == 0 || present_only == 1, "ubk_dice_fwd: present_only=%d must be 0 or 1", present_only);
-  UBK_CHECK(aligned(classw, 4), "ubk_dice_fwd: classw must be 4-byte aligned");
-  UBK_CHECK(aligned(workspace, 16), "ubk_dice_fwd: workspace must be 16-byte aligned");
-  UBK_CHECK(aligned(ctl, 8) && aligned(loss, 4), "ubk_dice_fwd: ctl must be 8-byte aligned, loss 4-byte aligned");
-  UBK_CHECK(!overlap(workspace, UBK_WORKSPACE_BYTES, ctl, UBK_CTL_BYTES), "ubk_dice_fwd: ctl overlaps workspace");
-  UBK_CHECK(!overlap(workspace, UBK_WORKSPACE_BYTES, loss, 4), "ubk_dice_fwd: loss inside workspace");
-  UBK_CHECK(!overlap(ctl, UBK_CTL_BYTES, loss, 4), "ubk_dice_fwd: loss inside ctl");
+  SAT_CHECK(workspace && ctl && loss, "ubk_dice_fwd: null pointer (workspace, ctl, loss)");
+  SAT_CHECK(finite_nonneg(alpha), "ubk_dice_fwd: alpha=%g must be finite and >= 0", (double)alpha);
+  SAT_CHECK(finite_nonneg(beta), "ubk_dice_fwd: beta=%g must be finite and >= 0", (double)beta);
+  SAT_CHECK(finite_nonneg(eps), "ubk_dice_fwd: eps=%g must be finite and >= 0", (double)eps);
+  SAT_CHECK(present_only == 0 || present_only == 1, "ubk_dice_fwd: present_only=%d must be 0 or 1", present_only);
+  SAT_CHECK(aligned(classw, 4), "ubk_dice_fwd: classw must be 4-byte aligned");
+  SAT_CHECK(aligned(workspace, 16), "ubk_dice_fwd: workspace must be 16-byte aligned");
+  SAT_CHECK(aligned(ctl, 8) && aligned(loss, 4), "ubk_dice_fwd: ctl must be 8-byte aligned, loss 4-byte aligned");
+  SAT_CHECK(!overlap(workspace, UBK_WORKSPACE_BYTES, ctl, UBK_CTL_BYTES), "ubk_dice_fwd: ctl overlaps workspace");
+  SAT_CHECK(!overlap(workspace, UBK_WORKSPACE_BYTES, loss, 4), "ubk_dice_fwd: loss inside workspace");
+  SAT_CHECK(!overlap(ctl, UBK_CTL_BYTES, loss, 4), "ubk_dice_fwd: loss inside ctl");
   const long hw = (long)H * W, total = (long)N * hw;
   const unsigned grid = grid_of(total);
   const bool vec = hw % 4 == 0 && aligned(predict, 16) && aligned(target, 16) && aligned(pixelweights, 16);
@@ -435,26 +359,26 @@ extern "C" int ubk_dice_fwd(const float* predict, const int64_t* target, const f
     case 4: launch_fwd<4>(vec, grid, s, predict, t, pixelweights, C, hw, total, (long long)ignore_index, (u64*)workspace); break;
     default: launch_fwd<0>(vec, grid, s, predict, t, pixelweights, C, hw, total, (long long)ignore_index, (u64*)workspace); break;
   }
-  UBK_LAUNCH_CHECK("ubk_dice_fwd");
+  SAT_LAUNCH_CHECK("ubk_dice_fwd");
   dice_finish_kernel<<<dim3(1), dim3(UBK_FINISH_BLOCK), 0, s>>>((const u64*)workspace, (int)grid, classw, C, alpha, beta, eps, present_only,
                                                                (u64*)ctl, loss);
-  UBK_LAUNCH_CHECK("ubk_dice_fwd (finish)");
+  SAT_LAUNCH_CHECK("ubk_dice_fwd (finish)");
   return UBK_OK;
 }
 
 extern "C" int ubk_dice_bwd(const float* g_loss, const void* ctl, const float* predict, const int64_t* target, const float* pixelweights,
                             int N, int C, int H, int W, int64_t ignore_index, float* g_predict, void* stream) {
   UBK_CHECK_OPERANDS("ubk_dice_bwd", predict, target, pixelweights, N, C, H, W);
-  UBK_CHECK(g_loss && ctl && g_predict, "ubk_dice_bwd: null pointer (g_loss, ctl, g_predict)");
-  UBK_CHECK(aligned(ctl, 8) && aligned(g_loss, 4) && aligned(g_predict, 4),
+  SAT_CHECK(g_loss && ctl && g_predict, "ubk_dice_bwd: null pointer (g_loss, ctl, g_predict)");
+  SAT_CHECK(aligned(ctl, 8) && aligned(g_loss, 4) && aligned(g_predict, 4),
             "ubk_dice_bwd: ctl must be 8-byte aligned, g_loss and g_predict 4-byte aligned");
   const long hw = (long)H * W, total = (long)N * hw;
   const unsigned long long gbytes = 4ull * (unsigned long long)total * (unsigned long long)C;
-  UBK_CHECK(!overlap(g_predict, gbytes, predict, gbytes), "ubk_dice_bwd: g_predict overlaps predict");
-  UBK_CHECK(!overlap(g_predict, gbytes, target, 8ull * (unsigned long long)total), "ubk_dice_bwd: g_predict overlaps target");
-  UBK_CHECK(!overlap(g_predict, gbytes, pixelweights, 4ull * (unsigned long long)total), "ubk_dice_bwd: g_predict overlaps pixelweights");
-  UBK_CHECK(!overlap(g_predict, gbytes, ctl, UBK_CTL_BYTES), "ubk_dice_bwd: g_predict overlaps ctl");
-  UBK_CHECK(!overlap(g_predict, gbytes, g_loss, 4), "ubk_dice_bwd: g_predict overlaps g_loss");
+  SAT_CHECK(!overlap(g_predict, gbytes, predict, gbytes), "ubk_dice_bwd: g_predict overlaps predict");
+  SAT_CHECK(!overlap(g_predict, gbytes, target, 8ull * (unsigned long long)total), "ubk_dice_bwd: g_predict overlaps target");
+  SAT_CHECK(!overlap(g_predict, gbytes, pixelweights, 4ull * (unsigned long long)total), "ubk_dice_bwd: g_predict overlaps pixelweights");
+  SAT_CHECK(!overlap(g_predict, gbytes, ctl, UBK_CTL_BYTES), "ubk_dice_bwd: g_predict overlaps ctl");
+  SAT_CHECK(!overlap(g_predict, gbytes, g_loss, 4), "ubk_dice_bwd: g_predict overlaps g_loss");
   const unsigned grid = grid_of(total);
   const bool vec = hw % 4 == 0 && aligned(predict, 16) && aligned(target, 16) && aligned(pixelweights, 16) && aligned(g_predict, 16);
   if (vec)
@@ -463,6 +387,6 @@ extern "C" int ubk_dice_bwd(const float* g_loss, const void* ctl, const float* p
   else
     dice_bwd_kernel<false><<<dim3(grid), dim3(UBK_BLOCK), 0, (hipStream_t)stream>>>(g_loss, (const float*)ctl, predict, (const long long*)target,
                                                                                    pixelweights, C, hw, total, (long long)ignore_index, g_predict);
-  UBK_LAUNCH_CHECK("ubk_dice_bwd");
+  SAT_LAUNCH_CHECK("ubk_dice_bwd");
   return UBK_OK;
 }

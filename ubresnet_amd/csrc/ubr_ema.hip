@@ -1,11 +1,10 @@
-// libubresnet_ema.so: the exponential moving average of the parameters (include/ubresnet_ema.h).  Self-contained: nothing of
-// the other seven libraries is linked or included, the launches are plain <<<>>> on the caller's stream.
+// libubresnet_ema.so: the exponential moving average of the parameters (include/ubresnet_ema.h).  It links against none of the
+// other libraries and shares ubr_sat.h with them; the launches are plain <<<>>> on the caller's stream.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stddef.h>
-#include <stdio.h>
 #include "../../include/ubresnet_ema.h"
 #include "ubr_ema_sched.h"
+#include "ubr_sat.h"
 
 #define UBE_VERSION 1
 
@@ -15,33 +14,9 @@ static_assert(offsetof(ube_ctl, apply) == 0 && offsetof(ube_ctl, w) == 4 && offs
               "ube_ctl layout");
 static_assert(sizeof(ube_seg) == 32 && offsetof(ube_seg, live) == 8 && offsetof(ube_seg, count) == 16, "ube_seg layout");
 
-static thread_local char g_ube_err[512] = "";
-
-static void ube_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_ube_err, sizeof(g_ube_err), fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* ube_last_error(void) { return g_ube_err; }
-extern "C" int ube_version(void) { return UBE_VERSION; }
-
-#define UBE_CHECK(cond, ...)     \
-  do {                           \
-    if (!(cond)) {               \
-      ube_set_error(__VA_ARGS__);\
-      return UBE_EINVAL;         \
-    }                            \
-  } while (0)
-
-#define UBE_LAUNCH_CHECK(name)                                              \
-  do {                                                                      \
-    hipError_t e_ = hipGetLastError();                                      \
-    if (e_ != hipSuccess) {                                                 \
-      ube_set_error(name ": launch failed: %s", hipGetErrorString(e_));     \
-      return UBE_ELAUNCH;                                                   \
-    }                                                                       \
-  } while (0)
+SAT_RETURN_CODES(UBE);
+SAT_EXPORTS(ube, UBE_VERSION)
+using namespace sat;
 
 namespace {
 
@@ -150,13 +125,6 @@ __global__ __launch_bounds__(UBE_BLOCK) void swap_segs_kernel(const ube_seg* __r
   }
 }
 
-inline bool aligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) == 0; }
-
-inline bool overlap(const void* a, unsigned long long abytes, const void* b, unsigned long long bbytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x != 0 && y != 0 && x < y + bbytes && y < x + abytes;
-}
-
 inline unsigned flat_grid(long n4) {
   long grid = (n4 + UBE_BLOCK * UBE_UNROLL - 1) / (UBE_BLOCK * UBE_UNROLL);
   return (unsigned)(grid > UBE_MAX_GRID ? UBE_MAX_GRID : grid);
@@ -167,70 +135,70 @@ inline unsigned seg_grid(int64_t nseg) { return (unsigned)(nseg > UBE_SEG_GRID ?
 }  // namespace
 
 extern "C" int ube_ctl_init(void* ctl, int64_t updates, void* stream) {
-  UBE_CHECK(ctl, "ube_ctl_init: null ctl");
-  UBE_CHECK(aligned(ctl, 16), "ube_ctl_init: ctl must be 16-byte aligned");
-  UBE_CHECK(updates >= 0, "ube_ctl_init: updates=%lld must be >= 0", (long long)updates);
+  SAT_CHECK(ctl, "ube_ctl_init: null ctl");
+  SAT_CHECK(aligned(ctl, 16), "ube_ctl_init: ctl must be 16-byte aligned");
+  SAT_CHECK(updates >= 0, "ube_ctl_init: updates=%lld must be >= 0", (long long)updates);
   ctl_init_kernel<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>((ube_ctl*)ctl, (long long)updates);
-  UBE_LAUNCH_CHECK("ube_ctl_init");
+  SAT_LAUNCH_CHECK("ube_ctl_init");
   return UBE_OK;
 }
 
 extern "C" int ube_advance(void* ctl, const int32_t* apply_flag, float decay, int64_t warmup, void* stream) {
-  UBE_CHECK(ctl, "ube_advance: null ctl");
-  UBE_CHECK(aligned(ctl, 16), "ube_advance: ctl must be 16-byte aligned");
-  UBE_CHECK(aligned(apply_flag, 4), "ube_advance: apply_flag must be 4-byte aligned");
-  UBE_CHECK(!overlap(ctl, UBE_CTL_BYTES, apply_flag, 4), "ube_advance: apply_flag lies inside ctl");
-  UBE_CHECK(decay == decay, "ube_advance: decay is NaN");
-  UBE_CHECK(decay >= 0.f && decay < 1.f, "ube_advance: decay=%g must lie in [0, 1)", (double)decay);
-  UBE_CHECK(warmup >= 0 && warmup <= (INT64_MAX >> 2), "ube_advance: warmup=%lld must be >= 0", (long long)warmup);
+  SAT_CHECK(ctl, "ube_advance: null ctl");
+  SAT_CHECK(aligned(ctl, 16), "ube_advance: ctl must be 16-byte aligned");
+  SAT_CHECK(aligned(apply_flag, 4), "ube_advance: apply_flag must be 4-byte aligned");
+  SAT_CHECK(!overlap(ctl, UBE_CTL_BYTES, apply_flag, 4), "ube_advance: apply_flag lies inside ctl");
+  SAT_CHECK(decay == decay, "ube_advance: decay is NaN");
+  SAT_CHECK(decay >= 0.f && decay < 1.f, "ube_advance: decay=%g must lie in [0, 1)", (double)decay);
+  SAT_CHECK(warmup >= 0 && warmup <= (INT64_MAX >> 2), "ube_advance: warmup=%lld must be >= 0", (long long)warmup);
   advance_kernel<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>((ube_ctl*)ctl, apply_flag, decay, (long long)warmup);
-  UBE_LAUNCH_CHECK("ube_advance");
+  SAT_LAUNCH_CHECK("ube_advance");
   return UBE_OK;
 }
 
 extern "C" int ube_update(float* shadow, const float* param, int64_t n, const void* ctl, void* stream) {
-  UBE_CHECK(shadow && param && ctl, "ube_update: null pointer (shadow, param, ctl)");
-  UBE_CHECK(n > 0 && n % 4 == 0, "ube_update: n=%lld must be positive and a multiple of 4", (long long)n);
-  UBE_CHECK(aligned(shadow, 16) && aligned(param, 16) && aligned(ctl, 16), "ube_update: shadow, param and ctl must be 16-byte aligned");
+  SAT_CHECK(shadow && param && ctl, "ube_update: null pointer (shadow, param, ctl)");
+  SAT_CHECK(n > 0 && n % 4 == 0, "ube_update: n=%lld must be positive and a multiple of 4", (long long)n);
+  SAT_CHECK(aligned(shadow, 16) && aligned(param, 16) && aligned(ctl, 16), "ube_update: shadow, param and ctl must be 16-byte aligned");
   const unsigned long long bytes = 4ull * (unsigned long long)n;
-  UBE_CHECK(!overlap(shadow, bytes, param, bytes), "ube_update: shadow overlaps param");
-  UBE_CHECK(!overlap(ctl, UBE_CTL_BYTES, shadow, bytes), "ube_update: ctl overlaps shadow");
-  UBE_CHECK(!overlap(ctl, UBE_CTL_BYTES, param, bytes), "ube_update: ctl overlaps param");
+  SAT_CHECK(!overlap(shadow, bytes, param, bytes), "ube_update: shadow overlaps param");
+  SAT_CHECK(!overlap(ctl, UBE_CTL_BYTES, shadow, bytes), "ube_update: ctl overlaps shadow");
+  SAT_CHECK(!overlap(ctl, UBE_CTL_BYTES, param, bytes), "ube_update: ctl overlaps param");
   const long n4 = (long)(n / 4);
   update_kernel<<<dim3(flat_grid(n4)), dim3(UBE_BLOCK), 0, (hipStream_t)stream>>>((float4*)shadow, (const float4*)param, n4,
                                                                                  (const ube_ctl*)ctl);
-  UBE_LAUNCH_CHECK("ube_update");
+  SAT_LAUNCH_CHECK("ube_update");
   return UBE_OK;
 }
 
 extern "C" int ube_swap(float* a, float* b, int64_t n, void* stream) {
-  UBE_CHECK(a && b, "ube_swap: null pointer (a, b)");
-  UBE_CHECK(n > 0 && n % 4 == 0, "ube_swap: n=%lld must be positive and a multiple of 4", (long long)n);
-  UBE_CHECK(aligned(a, 16) && aligned(b, 16), "ube_swap: a and b must be 16-byte aligned");
+  SAT_CHECK(a && b, "ube_swap: null pointer (a, b)");
+  SAT_CHECK(n > 0 && n % 4 == 0, "ube_swap: n=%lld must be positive and a multiple of 4", (long long)n);
+  SAT_CHECK(aligned(a, 16) && aligned(b, 16), "ube_swap: a and b must be 16-byte aligned");
   const unsigned long long bytes = 4ull * (unsigned long long)n;
-  UBE_CHECK(!overlap(a, bytes, b, bytes), "ube_swap: a overlaps b");
+  SAT_CHECK(!overlap(a, bytes, b, bytes), "ube_swap: a overlaps b");
   const long n4 = (long)(n / 4);
   swap_kernel<<<dim3(flat_grid(n4)), dim3(UBE_BLOCK), 0, (hipStream_t)stream>>>((uint4*)a, (uint4*)b, n4);
-  UBE_LAUNCH_CHECK("ube_swap");
+  SAT_LAUNCH_CHECK("ube_swap");
   return UBE_OK;
 }
 
 extern "C" int ube_update_segs(const void* table, int64_t nseg, const void* ctl, void* stream) {
-  UBE_CHECK(table && ctl, "ube_update_segs: null pointer (table, ctl)");
-  UBE_CHECK(nseg >= 1 && nseg <= (INT64_MAX >> 6), "ube_update_segs: nseg=%lld must be >= 1", (long long)nseg);
-  UBE_CHECK(aligned(table, 8) && aligned(ctl, 16), "ube_update_segs: table must be 8-byte and ctl 16-byte aligned");
-  UBE_CHECK(!overlap(ctl, UBE_CTL_BYTES, table, 32ull * (unsigned long long)nseg), "ube_update_segs: ctl overlaps table");
+  SAT_CHECK(table && ctl, "ube_update_segs: null pointer (table, ctl)");
+  SAT_CHECK(nseg >= 1 && nseg <= (INT64_MAX >> 6), "ube_update_segs: nseg=%lld must be >= 1", (long long)nseg);
+  SAT_CHECK(aligned(table, 8) && aligned(ctl, 16), "ube_update_segs: table must be 8-byte and ctl 16-byte aligned");
+  SAT_CHECK(!overlap(ctl, UBE_CTL_BYTES, table, 32ull * (unsigned long long)nseg), "ube_update_segs: ctl overlaps table");
   update_segs_kernel<<<dim3(seg_grid(nseg)), dim3(UBE_BLOCK), 0, (hipStream_t)stream>>>((const ube_seg*)table, (long)nseg,
                                                                                        (const ube_ctl*)ctl);
-  UBE_LAUNCH_CHECK("ube_update_segs");
+  SAT_LAUNCH_CHECK("ube_update_segs");
   return UBE_OK;
 }
 
 extern "C" int ube_swap_segs(const void* table, int64_t nseg, void* stream) {
-  UBE_CHECK(table, "ube_swap_segs: null pointer (table)");
-  UBE_CHECK(nseg >= 1 && nseg <= (INT64_MAX >> 6), "ube_swap_segs: nseg=%lld must be >= 1", (long long)nseg);
-  UBE_CHECK(aligned(table, 8), "ube_swap_segs: table must be 8-byte aligned");
+  SAT_CHECK(table, "ube_swap_segs: null pointer (table)");
+  SAT_CHECK(nseg >= 1 && nseg <= (INT64_MAX >> 6), "ube_swap_segs: nseg=%lld must be >= 1", (long long)nseg);
+  SAT_CHECK(aligned(table, 8), "ube_swap_segs: table must be 8-byte aligned");
   swap_segs_kernel<<<dim3(seg_grid(nseg)), dim3(UBE_BLOCK), 0, (hipStream_t)stream>>>((const ube_seg*)table, (long)nseg);
-  UBE_LAUNCH_CHECK("ube_swap_segs");
+  SAT_LAUNCH_CHECK("ube_swap_segs");
   return UBE_OK;
 }

@@ -1,12 +1,13 @@
-// libubresnet_group.so: flat optimizer steps with parameter groups and frozen parameters (include/ubresnet_group.h).
-// Self-contained: nothing of the other six libraries is linked or included, the launches are plain <<<>>> on the caller's stream.
+// libubresnet_group.so: flat optimizer steps with parameter groups and frozen parameters (include/ubresnet_group.h).  It links
+// against none of the other libraries; it shares ubr_sat.h with every satellite source and ubr_opt_rule.h, the step's arithmetic,
+// with ubr_opt.hip.  The launches are plain <<<>>> on the caller's stream.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stddef.h>
-#include <stdio.h>
 #include "../../include/ubresnet_group.h"
 #include "ubr_group_plan.h"
+#include "ubr_opt_rule.h"
+#include "ubr_sat.h"
 
 #define UBG_VERSION 1
 
@@ -17,33 +18,9 @@ static_assert(offsetof(ubg_ctl, norm) == 8 && offsetof(ubg_ctl, apply) == 20 && 
 static_assert(sizeof(ubg_tile) == 16 && sizeof(ubg_hyper) == 16 && sizeof(ubg_state) == 16, "16-byte records");
 static_assert(UBG_TILE_UNITS == 4 * UBG_BLOCK, "a lane takes four units of a tile");
 
-static thread_local char g_ubg_err[512] = "";
-
-static void ubg_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_ubg_err, sizeof(g_ubg_err), fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* ubg_last_error(void) { return g_ubg_err; }
-extern "C" int ubg_version(void) { return UBG_VERSION; }
-
-#define UBG_CHECK(cond, ...)     \
-  do {                           \
-    if (!(cond)) {               \
-      ubg_set_error(__VA_ARGS__);\
-      return UBG_EINVAL;         \
-    }                            \
-  } while (0)
-
-#define UBG_LAUNCH_CHECK(name)                                              \
-  do {                                                                      \
-    hipError_t e_ = hipGetLastError();                                      \
-    if (e_ != hipSuccess) {                                                 \
-      ubg_set_error(name ": launch failed: %s", hipGetErrorString(e_));     \
-      return UBG_ELAUNCH;                                                   \
-    }                                                                       \
-  } while (0)
+SAT_RETURN_CODES(UBG);
+SAT_EXPORTS(ubg, UBG_VERSION)
+using namespace sat;
 
 namespace {
 
@@ -60,12 +37,6 @@ __device__ inline bool tile_ok(const ubg_tile& t, long n4, int nseg) {
   return t.seg >= 0 && t.seg < nseg && t.units >= 1 && t.units <= UBG_TILE_UNITS && t.unit0 >= 0 && t.unit0 <= n4 - t.units;
 }
 
-__device__ inline void bc_row(const float* __restrict__ bc_table, long bc_len, long long t, float& bc1, float& sqrt_bc2) {
-  const long row = (t < (long long)bc_len ? (long)t : bc_len) - 1;
-  bc1 = bc_table[2 * row];
-  sqrt_bc2 = bc_table[2 * row + 1];
-}
-
 __global__ __launch_bounds__(UBG_BLOCK) void group_state_set_kernel(ubg_state* __restrict__ state, long seg0, long count,
                                                                     const long long* __restrict__ applied,
                                                                     const float* __restrict__ bc_table, long bc_len) {
@@ -75,15 +46,14 @@ __global__ __launch_bounds__(UBG_BLOCK) void group_state_set_kernel(ubg_state* _
     st.applied = a;
     st.bc1 = 0.f;
     st.sqrt_bc2 = 0.f;
-    if (a > 0) bc_row(bc_table, bc_len, a, st.bc1, st.sqrt_bc2);
+    if (a > 0) optrule::bc_row(bc_table, bc_len, a, st.bc1, st.sqrt_bc2);
     state[seg0 + i] = st;
   }
 }
 
 // Sum of squares of the active segments, first launch: the order is the one include/ubresnet_group.h states.  The tile record
 // and the segment's switch are the same for the whole workgroup (uniform reads); the four units of a lane are loaded before
-// any is used.  A unit past the tile's end counts as zeros: acc + 0.0 is acc (acc is never -0.0).  The square of an fp32 value
-// is exact in fp64, so fma(x, x, acc) rounds once, as x * x + acc does.
+// any is used.  A unit past the tile's end counts as zeros: acc + 0.0 is acc (acc is never -0.0).
 __global__ __launch_bounds__(UBG_BLOCK) void group_sumsq_kernel(const float4* __restrict__ g, long n4, const ubg_tile* __restrict__ tiles,
                                                                 int ntiles, const ubg_hyper* __restrict__ hyper, int nseg,
                                                                 Ctl* __restrict__ ctl) {
@@ -100,19 +70,9 @@ __global__ __launch_bounds__(UBG_BLOCK) void group_sumsq_kernel(const float4* __
       v[u] = i < tl.units ? g[tl.unit0 + i] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      acc = fma((double)v[u].x, (double)v[u].x, acc);
-      acc = fma((double)v[u].y, (double)v[u].y, acc);
-      acc = fma((double)v[u].z, (double)v[u].z, acc);
-      acc = fma((double)v[u].w, (double)v[u].w, acc);
-    }
+    for (int u = 0; u < 4; ++u) acc = optrule::sumsq4(acc, v[u].x, v[u].y, v[u].z, v[u].w);
   }
-  s[threadIdx.x] = acc;
-  __syncthreads();
-  for (int w = UBG_BLOCK / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-    __syncthreads();
-  }
+  optrule::block_tree_sum<UBG_BLOCK>(s, acc);
   if (threadIdx.x == 0) ctl->partial[blockIdx.x] = s[0];
 }
 
@@ -129,28 +89,9 @@ __global__ __launch_bounds__(UBG_BLOCK) void group_decide_kernel(Ctl* __restrict
   if (threadIdx.x == 0) {
     double sumsq = 0.0;
     for (int i = 0; i < grid; ++i) sumsq += s[i];
-    const float norm = (float)(fabs((double)grad_scale) * sqrt(sumsq));
-    const float scale = max_norm < 0.f ? 1.0f : fminf(max_norm / (norm + 1e-6f), 1.0f);
-    const int apply = !(skip_nonfinite && !isfinite(sumsq));
-    const int clipped = apply && scale < 1.0f;
-    ubg_ctl& h = ctl->h;
-    h.sumsq = sumsq;
-    h.norm = norm;
-    h.scale = scale;
-    h.gscale = grad_scale * scale;
-    h.apply = apply;
-    h.clipped = clipped;
-    if (apply) {
-      h.applied += 1;
-      h.clipped_total += clipped;
-    } else {
-      h.skipped += 1;
-    }
-    h.row[0] = norm;
-    h.row[1] = scale;
-    h.row[2] = apply ? 1.0f : 0.0f;
-    h.row[3] = grad_scale * scale;
-    s_apply = apply;
+    const optrule::Decision d = optrule::decide(sumsq, grad_scale, max_norm, skip_nonfinite);
+    optrule::record(ctl->h, sumsq, d);
+    s_apply = d.apply;
   }
   __syncthreads();
   if (!s_apply) return;
@@ -158,13 +99,13 @@ __global__ __launch_bounds__(UBG_BLOCK) void group_decide_kernel(Ctl* __restrict
     if (hyper[seg].active == 0) continue;
     ubg_state st = state[seg];
     st.applied += 1;
-    bc_row(bc_table, bc_len, st.applied, st.bc1, st.sqrt_bc2);
+    optrule::bc_row(bc_table, bc_len, st.applied, st.bc1, st.sqrt_bc2);
     state[seg] = st;
   }
 }
 
-// The two step kernels are guarded_adam_kernel and guarded_sgd_kernel of libubresnet_opt.so (csrc/ubr_opt.hip) operation for
-// operation; what those take as launch arguments or from the control block's head comes from the tile's segment here.  A
+// The two step kernels apply the rule of guarded_adam_kernel and guarded_sgd_kernel of libubresnet_opt.so (ubr_opt_rule.h, one
+// text for both); what those take as launch arguments or from the control block's head comes from the tile's segment here.  A
 // workgroup takes whole tiles; lane l the units l, l + 256, l + 512, l + 768 of a tile, all loaded before the arithmetic.  A
 // segment that was never advanced (applied < 1: its bias corrections are zero) is passed over like an inactive one.
 __global__ __launch_bounds__(UBG_BLOCK) void group_adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -203,14 +144,7 @@ __global__ __launch_bounds__(UBG_BLOCK) void group_adam_kernel(float* __restrict
         float pp[4] = {P[u].x, P[u].y, P[u].z, P[u].w}, gg[4] = {G[u].x, G[u].y, G[u].z, G[u].w};
         float mm[4] = {M[u].x, M[u].y, M[u].z, M[u].w}, vv[4] = {V[u].x, V[u].y, V[u].z, V[u].w};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float gr = gg[e] * gscale;
-          gr = fmaf(wd, pp[e], gr);                                  // grad.add(param, alpha=weight_decay)
-          mm[e] = mm[e] + (1.f - b1) * (gr - mm[e]);                 // exp_avg.lerp_(grad, 1 - beta1)
-          vv[e] = b2 * vv[e] + (1.f - b2) * gr * gr;                 // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-          const float denom = sqrtf(vv[e]) / sqrt_bc2 + eps;
-          pp[e] = pp[e] - step_size * (mm[e] / denom);               // param.addcdiv_(exp_avg, denom, value=-step_size)
-        }
+        for (int e = 0; e < 4; ++e) optrule::adam_element(pp[e], gg[e], mm[e], vv[e], gscale, wd, b1, b2, eps, step_size, sqrt_bc2);
         reinterpret_cast<float4*>(p)[j] = make_float4(pp[0], pp[1], pp[2], pp[3]);
         reinterpret_cast<float4*>(m)[j] = make_float4(mm[0], mm[1], mm[2], mm[3]);
         reinterpret_cast<float4*>(v)[j] = make_float4(vv[0], vv[1], vv[2], vv[3]);
@@ -254,14 +188,8 @@ __global__ __launch_bounds__(UBG_BLOCK) void group_sgd_kernel(float* __restrict_
         const long j = tl.unit0 + i;
         float pp[4] = {P[u].x, P[u].y, P[u].z, P[u].w}, gg[4] = {G[u].x, G[u].y, G[u].z, G[u].w}, bb[4] = {B[u].x, B[u].y, B[u].z, B[u].w};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float gr = fmaf(wd, pp[e], gg[e] * gscale);
-          if (buf != nullptr) {
-            bb[e] = first ? gr : momentum * bb[e] + (1.f - dampening) * gr;   // torch.optim.SGD: first step clones the gradient
-            gr = nesterov ? fmaf(momentum, bb[e], gr) : bb[e];
-          }
-          pp[e] = pp[e] - lr * gr;
-        }
+        for (int e = 0; e < 4; ++e)
+          optrule::sgd_element(pp[e], gg[e], bb[e], gscale, wd, lr, momentum, dampening, buf != nullptr, first, nesterov);
         reinterpret_cast<float4*>(p)[j] = make_float4(pp[0], pp[1], pp[2], pp[3]);
         if (buf != nullptr) reinterpret_cast<float4*>(buf)[j] = make_float4(bb[0], bb[1], bb[2], bb[3]);
       }
@@ -269,53 +197,46 @@ __global__ __launch_bounds__(UBG_BLOCK) void group_sgd_kernel(float* __restrict_
   }
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-inline bool overlap(const void* a, unsigned long long abytes, const void* b, unsigned long long bbytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x != 0 && y != 0 && x < y + bbytes && y < x + abytes;
-}
-
 // the checks every call with segment records and a control block shares; 0 or UBG_EINVAL with the message set
 int check_segments(const char* fn, const void* hyper, const void* state, int64_t nseg, const void* ctl) {
-  UBG_CHECK(hyper && state && ctl, "%s: null pointer (hyper, state, ctl)", fn);
-  UBG_CHECK(nseg >= 1 && nseg <= INT32_MAX, "%s: nseg=%lld must be in [1, 2^31)", fn, (long long)nseg);
-  UBG_CHECK(aligned16(hyper) && aligned16(state) && aligned16(ctl), "%s: hyper, state and ctl must be 16-byte aligned", fn);
+  SAT_CHECK(hyper && state && ctl, "%s: null pointer (hyper, state, ctl)", fn);
+  SAT_CHECK(nseg >= 1 && nseg <= INT32_MAX, "%s: nseg=%lld must be in [1, 2^31)", fn, (long long)nseg);
+  SAT_CHECK(aligned16(hyper) && aligned16(state) && aligned16(ctl), "%s: hyper, state and ctl must be 16-byte aligned", fn);
   const unsigned long long segbytes = 16ull * (unsigned long long)nseg;
-  UBG_CHECK(!overlap(ctl, UBG_CTL_BYTES, hyper, segbytes), "%s: ctl overlaps hyper", fn);
-  UBG_CHECK(!overlap(ctl, UBG_CTL_BYTES, state, segbytes), "%s: ctl overlaps state", fn);
-  UBG_CHECK(!overlap(hyper, segbytes, state, segbytes), "%s: hyper overlaps state", fn);
+  SAT_CHECK(!overlap(ctl, UBG_CTL_BYTES, hyper, segbytes), "%s: ctl overlaps hyper", fn);
+  SAT_CHECK(!overlap(ctl, UBG_CTL_BYTES, state, segbytes), "%s: ctl overlaps state", fn);
+  SAT_CHECK(!overlap(hyper, segbytes, state, segbytes), "%s: hyper overlaps state", fn);
   return UBG_OK;
 }
 
 // and those of a call that also takes a tile table (after check_segments)
 int check_tiles(const char* fn, const void* tiles, int64_t ntiles, const void* state, int64_t nseg, const void* ctl) {
-  UBG_CHECK(tiles, "%s: null pointer (tiles)", fn);
-  UBG_CHECK(ntiles >= 1 && ntiles <= INT32_MAX, "%s: tile table empty or too long (ntiles=%lld)", fn, (long long)ntiles);
-  UBG_CHECK(aligned16(tiles), "%s: tiles must be 16-byte aligned", fn);
-  UBG_CHECK(!overlap(ctl, UBG_CTL_BYTES, tiles, 16ull * (unsigned long long)ntiles), "%s: ctl overlaps tiles", fn);
-  UBG_CHECK(!overlap(state, 16ull * (unsigned long long)nseg, tiles, 16ull * (unsigned long long)ntiles), "%s: state overlaps tiles", fn);
+  SAT_CHECK(tiles, "%s: null pointer (tiles)", fn);
+  SAT_CHECK(ntiles >= 1 && ntiles <= INT32_MAX, "%s: tile table empty or too long (ntiles=%lld)", fn, (long long)ntiles);
+  SAT_CHECK(aligned16(tiles), "%s: tiles must be 16-byte aligned", fn);
+  SAT_CHECK(!overlap(ctl, UBG_CTL_BYTES, tiles, 16ull * (unsigned long long)ntiles), "%s: ctl overlaps tiles", fn);
+  SAT_CHECK(!overlap(state, 16ull * (unsigned long long)nseg, tiles, 16ull * (unsigned long long)ntiles), "%s: state overlaps tiles", fn);
   return UBG_OK;
 }
 
 int check_table(const char* fn, const float* bc_table, int64_t bc_len, const void* ctl) {
-  UBG_CHECK(bc_table, "%s: null pointer (bc_table)", fn);
-  UBG_CHECK(((uintptr_t)bc_table & 7) == 0, "%s: bc_table must be 8-byte aligned", fn);
-  UBG_CHECK(bc_len >= 1, "%s: bc_len=%lld must be >= 1", fn, (long long)bc_len);
-  UBG_CHECK(!overlap(ctl, UBG_CTL_BYTES, bc_table, 8ull * (unsigned long long)bc_len), "%s: ctl overlaps bc_table", fn);
+  SAT_CHECK(bc_table, "%s: null pointer (bc_table)", fn);
+  SAT_CHECK(((uintptr_t)bc_table & 7) == 0, "%s: bc_table must be 8-byte aligned", fn);
+  SAT_CHECK(bc_len >= 1, "%s: bc_len=%lld must be >= 1", fn, (long long)bc_len);
+  SAT_CHECK(!overlap(ctl, UBG_CTL_BYTES, bc_table, 8ull * (unsigned long long)bc_len), "%s: ctl overlaps bc_table", fn);
   return UBG_OK;
 }
 
 int check_buffers(const char* fn, int64_t n, const void* const* bufs, const char* const* names, int nbufs, const void* tiles,
                   int64_t ntiles, const void* hyper, const void* state, int64_t nseg, const void* ctl) {
-  UBG_CHECK(n > 0 && n % 4 == 0, "%s: n=%lld must be positive and a multiple of 4", fn, (long long)n);
+  SAT_CHECK(n > 0 && n % 4 == 0, "%s: n=%lld must be positive and a multiple of 4", fn, (long long)n);
   const unsigned long long bytes = 4ull * (unsigned long long)n;
   for (int i = 0; i < nbufs; ++i) {
-    UBG_CHECK(aligned16(bufs[i]), "%s: %s must be 16-byte aligned", fn, names[i]);
-    UBG_CHECK(!overlap(ctl, UBG_CTL_BYTES, bufs[i], bytes), "%s: ctl overlaps %s", fn, names[i]);
-    UBG_CHECK(!overlap(state, 16ull * (unsigned long long)nseg, bufs[i], bytes), "%s: state overlaps %s", fn, names[i]);
-    UBG_CHECK(!overlap(hyper, 16ull * (unsigned long long)nseg, bufs[i], bytes), "%s: hyper overlaps %s", fn, names[i]);
-    UBG_CHECK(!overlap(tiles, 16ull * (unsigned long long)ntiles, bufs[i], bytes), "%s: tiles overlap %s", fn, names[i]);
+    SAT_CHECK(aligned16(bufs[i]), "%s: %s must be 16-byte aligned", fn, names[i]);
+    SAT_CHECK(!overlap(ctl, UBG_CTL_BYTES, bufs[i], bytes), "%s: ctl overlaps %s", fn, names[i]);
+    SAT_CHECK(!overlap(state, 16ull * (unsigned long long)nseg, bufs[i], bytes), "%s: state overlaps %s", fn, names[i]);
+    SAT_CHECK(!overlap(hyper, 16ull * (unsigned long long)nseg, bufs[i], bytes), "%s: hyper overlaps %s", fn, names[i]);
+    SAT_CHECK(!overlap(tiles, 16ull * (unsigned long long)ntiles, bufs[i], bytes), "%s: tiles overlap %s", fn, names[i]);
   }
   return UBG_OK;
 }
@@ -330,42 +251,42 @@ extern "C" int64_t ubg_plan_tiles(const int64_t* seg_unit0, const int64_t* seg_u
   const int64_t nt = ubg::plan_tiles(seg_unit0, seg_units, nseg, tiles, cap < 0 ? 0 : cap, &err, &bad);
   switch (err) {
     case ubg::PLAN_OK: return nt;
-    case ubg::PLAN_NULL: ubg_set_error("ubg_plan_tiles: null pointer (seg_unit0, seg_units, tiles)"); break;
-    case ubg::PLAN_NSEG: ubg_set_error("ubg_plan_tiles: nseg=%lld must be in [1, 2^31)", (long long)nseg); break;
-    case ubg::PLAN_UNITS: ubg_set_error("ubg_plan_tiles: segment %lld has %lld units; must be >= 1", (long long)bad, (long long)seg_units[bad]); break;
-    case ubg::PLAN_ORDER: ubg_set_error("ubg_plan_tiles: segment %lld starts at unit %lld, inside or before the segment in front of it", (long long)bad, (long long)seg_unit0[bad]); break;
-    default: ubg_set_error("ubg_plan_tiles: cap=%lld is too small for %lld tiles", (long long)cap, (long long)nt); break;
+    case ubg::PLAN_NULL: set_error("ubg_plan_tiles: null pointer (seg_unit0, seg_units, tiles)"); break;
+    case ubg::PLAN_NSEG: set_error("ubg_plan_tiles: nseg=%lld must be in [1, 2^31)", (long long)nseg); break;
+    case ubg::PLAN_UNITS: set_error("ubg_plan_tiles: segment %lld has %lld units; must be >= 1", (long long)bad, (long long)seg_units[bad]); break;
+    case ubg::PLAN_ORDER: set_error("ubg_plan_tiles: segment %lld starts at unit %lld, inside or before the segment in front of it", (long long)bad, (long long)seg_unit0[bad]); break;
+    default: set_error("ubg_plan_tiles: cap=%lld is too small for %lld tiles", (long long)cap, (long long)nt); break;
   }
   return UBG_EINVAL;
 }
 
 extern "C" int ubg_state_set(void* state, int64_t nseg, int64_t seg0, int64_t count, const int64_t* applied, const float* bc_table,
                              int64_t bc_len, void* stream) {
-  UBG_CHECK(state && applied, "ubg_state_set: null pointer (state, applied)");
-  UBG_CHECK(nseg >= 1 && nseg <= INT32_MAX, "ubg_state_set: nseg=%lld must be in [1, 2^31)", (long long)nseg);
-  UBG_CHECK(seg0 >= 0 && count >= 1 && seg0 <= nseg - count, "ubg_state_set: seg out of range: segments %lld .. %lld of %lld",
+  SAT_CHECK(state && applied, "ubg_state_set: null pointer (state, applied)");
+  SAT_CHECK(nseg >= 1 && nseg <= INT32_MAX, "ubg_state_set: nseg=%lld must be in [1, 2^31)", (long long)nseg);
+  SAT_CHECK(seg0 >= 0 && count >= 1 && seg0 <= nseg - count, "ubg_state_set: seg out of range: segments %lld .. %lld of %lld",
             (long long)seg0, (long long)(seg0 + count - 1), (long long)nseg);
-  UBG_CHECK(aligned16(state) && ((uintptr_t)applied & 7) == 0, "ubg_state_set: state must be 16-byte and applied 8-byte aligned");
-  UBG_CHECK(bc_table, "ubg_state_set: null pointer (bc_table)");
-  UBG_CHECK(((uintptr_t)bc_table & 7) == 0, "ubg_state_set: bc_table must be 8-byte aligned");
-  UBG_CHECK(bc_len >= 1, "ubg_state_set: bc_len=%lld must be >= 1", (long long)bc_len);
-  UBG_CHECK(!overlap(state, 16ull * (unsigned long long)nseg, applied, 8ull * (unsigned long long)count), "ubg_state_set: state overlaps applied");
-  UBG_CHECK(!overlap(state, 16ull * (unsigned long long)nseg, bc_table, 8ull * (unsigned long long)bc_len), "ubg_state_set: state overlaps bc_table");
+  SAT_CHECK(aligned16(state) && ((uintptr_t)applied & 7) == 0, "ubg_state_set: state must be 16-byte and applied 8-byte aligned");
+  SAT_CHECK(bc_table, "ubg_state_set: null pointer (bc_table)");
+  SAT_CHECK(((uintptr_t)bc_table & 7) == 0, "ubg_state_set: bc_table must be 8-byte aligned");
+  SAT_CHECK(bc_len >= 1, "ubg_state_set: bc_len=%lld must be >= 1", (long long)bc_len);
+  SAT_CHECK(!overlap(state, 16ull * (unsigned long long)nseg, applied, 8ull * (unsigned long long)count), "ubg_state_set: state overlaps applied");
+  SAT_CHECK(!overlap(state, 16ull * (unsigned long long)nseg, bc_table, 8ull * (unsigned long long)bc_len), "ubg_state_set: state overlaps bc_table");
   const int64_t blocks = (count + UBG_BLOCK - 1) / UBG_BLOCK;
   group_state_set_kernel<<<dim3((unsigned)(blocks < 64 ? blocks : 64)), dim3(UBG_BLOCK), 0, (hipStream_t)stream>>>(
       (ubg_state*)state, (long)seg0, (long)count, (const long long*)applied, bc_table, (long)bc_len);
-  UBG_LAUNCH_CHECK("ubg_state_set");
+  SAT_LAUNCH_CHECK("ubg_state_set");
   return UBG_OK;
 }
 
 extern "C" int ubg_state_get(const void* state, int64_t nseg, ubg_state* out, void* stream) {
-  UBG_CHECK(state && out, "ubg_state_get: null pointer (state, out)");
-  UBG_CHECK(nseg >= 1 && nseg <= INT32_MAX, "ubg_state_get: nseg=%lld must be in [1, 2^31)", (long long)nseg);
-  UBG_CHECK(aligned16(state) && ((uintptr_t)out & 7) == 0, "ubg_state_get: state must be 16-byte and out 8-byte aligned");
+  SAT_CHECK(state && out, "ubg_state_get: null pointer (state, out)");
+  SAT_CHECK(nseg >= 1 && nseg <= INT32_MAX, "ubg_state_get: nseg=%lld must be in [1, 2^31)", (long long)nseg);
+  SAT_CHECK(aligned16(state) && ((uintptr_t)out & 7) == 0, "ubg_state_get: state must be 16-byte and out 8-byte aligned");
   hipError_t e = hipMemcpyAsync(out, state, 16ull * (unsigned long long)nseg, hipMemcpyDeviceToHost, (hipStream_t)stream);
   if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
   if (e != hipSuccess) {
-    ubg_set_error("ubg_state_get: copy failed: %s", hipGetErrorString(e));
+    set_error("ubg_state_get: copy failed: %s", hipGetErrorString(e));
     return UBG_ELAUNCH;
   }
   return UBG_OK;
@@ -375,21 +296,21 @@ extern "C" int ubg_grad_norm(const float* grad, int64_t n, const void* tiles, in
                              int64_t nseg, float grad_scale, float max_norm, int skip_nonfinite, const float* bc_table,
                              int64_t bc_len, void* ctl, void* stream) {
   const char* fn = "ubg_grad_norm";
-  UBG_CHECK(grad, "%s: null pointer (grad)", fn);
+  SAT_CHECK(grad, "%s: null pointer (grad)", fn);
   if (check_segments(fn, hyper, state, nseg, ctl) || check_tiles(fn, tiles, ntiles, state, nseg, ctl)) return UBG_EINVAL;
   const void* bufs[1] = {grad};
   const char* names[1] = {"grad"};
   if (check_buffers(fn, n, bufs, names, 1, tiles, ntiles, hyper, state, nseg, ctl)) return UBG_EINVAL;
-  UBG_CHECK(max_norm == max_norm, "%s: max_norm is NaN", fn);
+  SAT_CHECK(max_norm == max_norm, "%s: max_norm is NaN", fn);
   if (check_table(fn, bc_table, bc_len, ctl)) return UBG_EINVAL;
   const int grid = (int)(ntiles < UBG_MAX_GRID ? ntiles : UBG_MAX_GRID);
   group_sumsq_kernel<<<dim3((unsigned)grid), dim3(UBG_BLOCK), 0, (hipStream_t)stream>>>(
       (const float4*)grad, (long)(n / 4), (const ubg_tile*)tiles, (int)ntiles, (const ubg_hyper*)hyper, (int)nseg, (Ctl*)ctl);
-  UBG_LAUNCH_CHECK("ubg_grad_norm");
+  SAT_LAUNCH_CHECK("ubg_grad_norm");
   group_decide_kernel<<<dim3(1), dim3(UBG_BLOCK), 0, (hipStream_t)stream>>>((Ctl*)ctl, grid, grad_scale, max_norm, skip_nonfinite ? 1 : 0,
                                                                              (const ubg_hyper*)hyper, (ubg_state*)state, (int)nseg,
                                                                              bc_table, (long)bc_len);
-  UBG_LAUNCH_CHECK("ubg_grad_norm");
+  SAT_LAUNCH_CHECK("ubg_grad_norm");
   return UBG_OK;
 }
 
@@ -400,7 +321,7 @@ extern "C" int ubg_advance(const void* hyper, void* state, int64_t nseg, float g
   if (check_table(fn, bc_table, bc_len, ctl)) return UBG_EINVAL;
   group_decide_kernel<<<dim3(1), dim3(UBG_BLOCK), 0, (hipStream_t)stream>>>((Ctl*)ctl, 0, grad_scale, -1.0f, 0, (const ubg_hyper*)hyper,
                                                                              (ubg_state*)state, (int)nseg, bc_table, (long)bc_len);
-  UBG_LAUNCH_CHECK("ubg_advance");
+  SAT_LAUNCH_CHECK("ubg_advance");
   return UBG_OK;
 }
 
@@ -408,7 +329,7 @@ extern "C" int ubg_adam_step(float* param, const float* grad, float* exp_avg, fl
                              int64_t ntiles, const void* hyper, const void* state, int64_t nseg, float beta1, float beta2, float eps,
                              const void* ctl, void* stream) {
   const char* fn = "ubg_adam_step";
-  UBG_CHECK(param && grad && exp_avg && exp_avg_sq, "%s: null pointer (param, grad, exp_avg, exp_avg_sq)", fn);
+  SAT_CHECK(param && grad && exp_avg && exp_avg_sq, "%s: null pointer (param, grad, exp_avg, exp_avg_sq)", fn);
   if (check_segments(fn, hyper, state, nseg, ctl) || check_tiles(fn, tiles, ntiles, state, nseg, ctl)) return UBG_EINVAL;
   const void* bufs[4] = {param, grad, exp_avg, exp_avg_sq};
   const char* names[4] = {"param", "grad", "exp_avg", "exp_avg_sq"};
@@ -416,7 +337,7 @@ extern "C" int ubg_adam_step(float* param, const float* grad, float* exp_avg, fl
   group_adam_kernel<<<dim3(step_grid(ntiles)), dim3(UBG_BLOCK), 0, (hipStream_t)stream>>>(
       param, grad, exp_avg, exp_avg_sq, (long)(n / 4), (const ubg_tile*)tiles, (int)ntiles, (const ubg_hyper*)hyper,
       (const ubg_state*)state, (int)nseg, beta1, beta2, eps, (const ubg_ctl*)ctl);
-  UBG_LAUNCH_CHECK("ubg_adam_step");
+  SAT_LAUNCH_CHECK("ubg_adam_step");
   return UBG_OK;
 }
 
@@ -424,8 +345,8 @@ extern "C" int ubg_sgd_step(float* param, const float* grad, float* momentum_buf
                             const void* hyper, const void* state, int64_t nseg, float momentum, float dampening, int nesterov,
                             const void* ctl, void* stream) {
   const char* fn = "ubg_sgd_step";
-  UBG_CHECK(param && grad, "%s: null pointer (param, grad)", fn);
-  UBG_CHECK((momentum == 0.f) == (momentum_buf == nullptr), "%s: momentum buffer iff momentum != 0", fn);
+  SAT_CHECK(param && grad, "%s: null pointer (param, grad)", fn);
+  SAT_CHECK((momentum == 0.f) == (momentum_buf == nullptr), "%s: momentum buffer iff momentum != 0", fn);
   if (check_segments(fn, hyper, state, nseg, ctl) || check_tiles(fn, tiles, ntiles, state, nseg, ctl)) return UBG_EINVAL;
   const void* bufs[3] = {param, grad, momentum_buf};
   const char* names[3] = {"param", "grad", "momentum_buf"};
@@ -433,6 +354,6 @@ extern "C" int ubg_sgd_step(float* param, const float* grad, float* momentum_buf
   group_sgd_kernel<<<dim3(step_grid(ntiles)), dim3(UBG_BLOCK), 0, (hipStream_t)stream>>>(
       param, grad, momentum_buf, (long)(n / 4), (const ubg_tile*)tiles, (int)ntiles, (const ubg_hyper*)hyper,
       (const ubg_state*)state, (int)nseg, momentum, dampening, nesterov, (const ubg_ctl*)ctl);
-  UBG_LAUNCH_CHECK("ubg_sgd_step");
+  SAT_LAUNCH_CHECK("ubg_sgd_step");
   return UBG_OK;
 }

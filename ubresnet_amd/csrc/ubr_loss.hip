@@ -1,11 +1,12 @@
-// libubresnet_loss.so: the pixel-wise focal loss and its normalised means (include/ubresnet_loss.h).  Self-contained: nothing of
-// the other ten libraries is linked or included, the launches are plain <<<>>> on the caller's stream, and there is no atomic
-// operation: the forward's streaming pass leaves one row of partials per workgroup, one workgroup adds the rows in a fixed order.
+// libubresnet_loss.so: the pixel-wise focal loss and its normalised means (include/ubresnet_loss.h).  It links against none of
+// the other libraries and shares ubr_sat.h with them, and ubr_rows.h with ubr_dice.hip; the launches are plain <<<>>> on the
+// caller's stream, and there is no atomic operation: the forward's streaming pass leaves one row of partials per workgroup, one
+// workgroup adds the rows in a fixed order.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "ubr_loss_term.h"
+#include "ubr_rows.h"
+#include "ubr_sat.h"
 
 #define UBL_VERSION 1
 #define UBL_TRIP_UNITS (UBL_BLOCK * UBL_UNROLL)
@@ -13,54 +14,12 @@
 #define UBL_FINISH_SUB 16                                  /* the finish adds UBL_FINISH_SUB interleaved row sequences, then those */
 #define UBL_FINISH_BLOCK (UBL_FINISH_SUB * UBL_ROW_WORDS)  /* 576 lanes: one per (sequence, word) */
 
-static thread_local char g_ubl_err[512] = "";
-
-static void ubl_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_ubl_err, sizeof(g_ubl_err), fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* ubl_last_error(void) { return g_ubl_err; }
-extern "C" int ubl_version(void) { return UBL_VERSION; }
-
-#define UBL_CHECK(cond, ...)     \
-  do {                           \
-    if (!(cond)) {               \
-      ubl_set_error(__VA_ARGS__);\
-      return UBL_EINVAL;         \
-    }                            \
-  } while (0)
-
-#define UBL_LAUNCH_CHECK(name)                                              \
-  do {                                                                      \
-    hipError_t e_ = hipGetLastError();                                      \
-    if (e_ != hipSuccess) {                                                 \
-      ubl_set_error(name ": launch failed: %s", hipGetErrorString(e_));     \
-      return UBL_ELAUNCH;                                                   \
-    }                                                                       \
-  } while (0)
+SAT_RETURN_CODES(UBL);
+SAT_EXPORTS(ubl, UBL_VERSION)
+using namespace sat;
+using namespace rowsum;
 
 namespace {
-
-typedef long long ll2 __attribute__((ext_vector_type(2)));
-typedef unsigned long long u64;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  return v;
-}
-
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  return v;
-}
-
-__device__ __forceinline__ bool contributes(long long t, int C, long long ignore_index) {
-  return t != ignore_index && t >= 0 && t < C;
-}
 
 // what a lane keeps over its trips: the totals in registers, the per-class sums in a column of LDS that is the lane's own (so
 // neither a barrier nor an atomic is needed until the end)
@@ -80,6 +39,10 @@ __device__ __forceinline__ void take(Lane& a, double* cls_sum, unsigned* cls_n, 
   a.n += 1u;
   cls_sum[(int)t * UBL_BLOCK] += (double)v;
   cls_n[(int)t * UBL_BLOCK] += 1u;
+}
+
+__device__ __forceinline__ bool integer_word(int word) {
+  return word == UBL_ROW_VALID || word == UBL_ROW_BAD || word >= UBL_ROW_CLASS_PIXELS;
 }
 
 // The forward's streaming pass.  VEC: a unit is 4 pixels of one image (hw % 4 == 0): the target as two 16-byte loads, the weight
@@ -178,23 +141,8 @@ __global__ __launch_bounds__(UBL_BLOCK) void focal_fwd_kernel(const float* __res
     }
   }
   __syncthreads();
-  if (lane < UBL_ROW_WORDS) {
-    const bool integer = lane == UBL_ROW_VALID || lane == UBL_ROW_BAD || lane >= UBL_ROW_CLASS_PIXELS;
-    u64 out;
-    if (integer) {
-      out = 0ull;
-      for (int w = 0; w < UBL_BLOCK / 64; ++w) out += wave_row[w][lane];
-    } else {
-      double d = 0.0;
-      for (int w = 0; w < UBL_BLOCK / 64; ++w) d += __longlong_as_double((long long)wave_row[w][lane]);
-      out = (u64)__double_as_longlong(d);
-    }
-    rows[(long)blockIdx.x * UBL_ROW_WORDS + lane] = out;
-  }
-}
-
-__device__ __forceinline__ bool integer_word(int word) {
-  return word == UBL_ROW_VALID || word == UBL_ROW_BAD || word >= UBL_ROW_CLASS_PIXELS;
+  if (lane < UBL_ROW_WORDS)
+    rows[(long)blockIdx.x * UBL_ROW_WORDS + lane] = add_wave_rows(wave_row, lane, integer_word(lane));
 }
 
 // One workgroup: lane (q, word) adds word `word` of the rows q, q + 16, q + 32, .. in that order; then lane `word` adds the 16
@@ -205,25 +153,10 @@ __global__ __launch_bounds__(UBL_FINISH_BLOCK) void focal_finish_kernel(const u6
   __shared__ u64 tot[UBL_ROW_WORDS];
   const int word = threadIdx.x % UBL_ROW_WORDS, q = threadIdx.x / UBL_ROW_WORDS;
   const bool integer = integer_word(word);
-  u64 ai = 0ull;
-  double ad = 0.0;
-#pragma unroll 8
-  for (int r = q; r < nrows; r += UBL_FINISH_SUB) {
-    const u64 v = rows[(long)r * UBL_ROW_WORDS + word];
-    ai += integer ? v : 0ull;
-    ad += integer ? 0.0 : __longlong_as_double((long long)v);
-  }
-  sub[q][word] = integer ? ai : (u64)__double_as_longlong(ad);
+  sub[q][word] = sequence_sum<UBL_FINISH_SUB, UBL_ROW_WORDS>(rows, nrows, q, word, integer);
   __syncthreads();
   if (threadIdx.x < UBL_ROW_WORDS) {
-    ai = 0ull;
-    ad = 0.0;
-    for (int k = 0; k < UBL_FINISH_SUB; ++k) {
-      const u64 v = sub[k][word];
-      ai += integer ? v : 0ull;
-      ad += integer ? 0.0 : __longlong_as_double((long long)v);
-    }
-    const u64 out = integer ? ai : (u64)__double_as_longlong(ad);
+    const u64 out = sequences_sum(sub, word, integer);
     tot[word] = out;
     // row words 0..3 are ctl words 0..3; the per-class words move up behind the four words of the mean
     ctl[word < UBL_ROW_CLASS_LOSS ? word : word + (UBL_CTL_CLASS_LOSS - UBL_ROW_CLASS_LOSS)] = out;
@@ -334,13 +267,6 @@ __global__ __launch_bounds__(UBL_BLOCK) void focal_bwd_kernel(const float* __res
   }
 }
 
-inline bool aligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) == 0; }
-
-inline bool overlap(const void* a, unsigned long long abytes, const void* b, unsigned long long bbytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x != 0 && y != 0 && x < y + bbytes && y < x + abytes;
-}
-
 inline unsigned grid_of(long total) {
   long grid = (total + UBL_TRIP_PIXELS - 1) / UBL_TRIP_PIXELS;
   return (unsigned)(grid > UBL_MAX_GRID ? UBL_MAX_GRID : grid);
@@ -350,25 +276,25 @@ inline unsigned grid_of(long total) {
 
 // the checks the two calls share; `name` starts the message
 #define UBL_CHECK_OPERANDS(name, predict, target, pixelweights, classw, N, C, H, W, gamma)                                       \
-  UBL_CHECK((predict) && (target) && (pixelweights), name ": null pointer (predict, target, pixelweights)");                     \
-  UBL_CHECK((N) > 0 && (H) > 0 && (W) > 0, name ": bad extents N=%d H=%d W=%d", (N), (H), (W));                                   \
-  UBL_CHECK((C) >= 1 && (C) <= UBL_MAX_CLASSES, name ": C=%d must be in [1, %d]", (C), UBL_MAX_CLASSES);                          \
-  UBL_CHECK((gamma) == (gamma), name ": gamma is NaN");                                                                           \
-  UBL_CHECK((gamma) >= 0.f && (gamma) < INFINITY, name ": gamma=%g must be finite and >= 0", (double)(gamma));                    \
-  UBL_CHECK(aligned((predict), 4) && aligned((pixelweights), 4) && aligned((classw), 4) && aligned((target), 8),                 \
+  SAT_CHECK((predict) && (target) && (pixelweights), name ": null pointer (predict, target, pixelweights)");                     \
+  SAT_CHECK((N) > 0 && (H) > 0 && (W) > 0, name ": bad extents N=%d H=%d W=%d", (N), (H), (W));                                   \
+  SAT_CHECK((C) >= 1 && (C) <= UBL_MAX_CLASSES, name ": C=%d must be in [1, %d]", (C), UBL_MAX_CLASSES);                          \
+  SAT_CHECK((gamma) == (gamma), name ": gamma is NaN");                                                                           \
+  SAT_CHECK((gamma) >= 0.f && (gamma) < INFINITY, name ": gamma=%g must be finite and >= 0", (double)(gamma));                    \
+  SAT_CHECK(aligned((predict), 4) && aligned((pixelweights), 4) && aligned((classw), 4) && aligned((target), 8),                 \
             name ": predict, pixelweights and classw must be 4-byte aligned, target 8-byte aligned")
 
 extern "C" int ubl_focal_fwd(const float* predict, const int64_t* target, const float* pixelweights, const float* classw,
                              int N, int C, int H, int W, int64_t ignore_index, float gamma, int mode,
                              void* workspace, void* ctl, float* loss, void* stream) {
   UBL_CHECK_OPERANDS("ubl_focal_fwd", predict, target, pixelweights, classw, N, C, H, W, gamma);
-  UBL_CHECK(workspace && ctl && loss, "ubl_focal_fwd: null pointer (workspace, ctl, loss)");
-  UBL_CHECK(mode == UBL_MEAN_PIXELS || mode == UBL_MEAN_VALID || mode == UBL_MEAN_WEIGHTS, "ubl_focal_fwd: unknown mode %d", mode);
-  UBL_CHECK(aligned(workspace, 16), "ubl_focal_fwd: workspace must be 16-byte aligned");
-  UBL_CHECK(aligned(ctl, 8) && aligned(loss, 4), "ubl_focal_fwd: ctl must be 8-byte aligned, loss 4-byte aligned");
-  UBL_CHECK(!overlap(workspace, UBL_WORKSPACE_BYTES, ctl, UBL_CTL_BYTES), "ubl_focal_fwd: ctl overlaps workspace");
-  UBL_CHECK(!overlap(workspace, UBL_WORKSPACE_BYTES, loss, 4), "ubl_focal_fwd: loss inside workspace");
-  UBL_CHECK(!overlap(ctl, UBL_CTL_BYTES, loss, 4), "ubl_focal_fwd: loss inside ctl");
+  SAT_CHECK(workspace && ctl && loss, "ubl_focal_fwd: null pointer (workspace, ctl, loss)");
+  SAT_CHECK(mode == UBL_MEAN_PIXELS || mode == UBL_MEAN_VALID || mode == UBL_MEAN_WEIGHTS, "ubl_focal_fwd: unknown mode %d", mode);
+  SAT_CHECK(aligned(workspace, 16), "ubl_focal_fwd: workspace must be 16-byte aligned");
+  SAT_CHECK(aligned(ctl, 8) && aligned(loss, 4), "ubl_focal_fwd: ctl must be 8-byte aligned, loss 4-byte aligned");
+  SAT_CHECK(!overlap(workspace, UBL_WORKSPACE_BYTES, ctl, UBL_CTL_BYTES), "ubl_focal_fwd: ctl overlaps workspace");
+  SAT_CHECK(!overlap(workspace, UBL_WORKSPACE_BYTES, loss, 4), "ubl_focal_fwd: loss inside workspace");
+  SAT_CHECK(!overlap(ctl, UBL_CTL_BYTES, loss, 4), "ubl_focal_fwd: loss inside ctl");
   const long hw = (long)H * W, total = (long)N * hw;
   const unsigned grid = grid_of(total);
   const bool vec = hw % 4 == 0 && aligned(predict, 16) && aligned(target, 16) && aligned(pixelweights, 16);
@@ -378,10 +304,10 @@ extern "C" int ubl_focal_fwd(const float* predict, const int64_t* target, const 
   else
     focal_fwd_kernel<false><<<dim3(grid), dim3(UBL_BLOCK), 0, (hipStream_t)stream>>>(predict, (const long long*)target, pixelweights, classw,
                                                                                     C, hw, total, (long long)ignore_index, gamma, (u64*)workspace);
-  UBL_LAUNCH_CHECK("ubl_focal_fwd");
+  SAT_LAUNCH_CHECK("ubl_focal_fwd");
   focal_finish_kernel<<<dim3(1), dim3(UBL_FINISH_BLOCK), 0, (hipStream_t)stream>>>((const u64*)workspace, (int)grid, mode, (u64)total,
                                                                                   (u64*)ctl, loss);
-  UBL_LAUNCH_CHECK("ubl_focal_fwd (finish)");
+  SAT_LAUNCH_CHECK("ubl_focal_fwd (finish)");
   return UBL_OK;
 }
 
@@ -389,16 +315,16 @@ extern "C" int ubl_focal_bwd(const float* g_loss, const void* ctl, const float* 
                              const float* classw, int N, int C, int H, int W, int64_t ignore_index, float gamma,
                              float* g_predict, void* stream) {
   UBL_CHECK_OPERANDS("ubl_focal_bwd", predict, target, pixelweights, classw, N, C, H, W, gamma);
-  UBL_CHECK(g_loss && ctl && g_predict, "ubl_focal_bwd: null pointer (g_loss, ctl, g_predict)");
-  UBL_CHECK(aligned(ctl, 8) && aligned(g_loss, 4) && aligned(g_predict, 4),
+  SAT_CHECK(g_loss && ctl && g_predict, "ubl_focal_bwd: null pointer (g_loss, ctl, g_predict)");
+  SAT_CHECK(aligned(ctl, 8) && aligned(g_loss, 4) && aligned(g_predict, 4),
             "ubl_focal_bwd: ctl must be 8-byte aligned, g_loss and g_predict 4-byte aligned");
   const long hw = (long)H * W, total = (long)N * hw;
   const unsigned long long gbytes = 4ull * (unsigned long long)total * (unsigned long long)C;
-  UBL_CHECK(!overlap(g_predict, gbytes, predict, gbytes), "ubl_focal_bwd: g_predict overlaps predict");
-  UBL_CHECK(!overlap(g_predict, gbytes, target, 8ull * (unsigned long long)total), "ubl_focal_bwd: g_predict overlaps target");
-  UBL_CHECK(!overlap(g_predict, gbytes, pixelweights, 4ull * (unsigned long long)total), "ubl_focal_bwd: g_predict overlaps pixelweights");
-  UBL_CHECK(!overlap(g_predict, gbytes, ctl, UBL_CTL_BYTES), "ubl_focal_bwd: g_predict overlaps ctl");
-  UBL_CHECK(!overlap(g_predict, gbytes, g_loss, 4), "ubl_focal_bwd: g_predict overlaps g_loss");
+  SAT_CHECK(!overlap(g_predict, gbytes, predict, gbytes), "ubl_focal_bwd: g_predict overlaps predict");
+  SAT_CHECK(!overlap(g_predict, gbytes, target, 8ull * (unsigned long long)total), "ubl_focal_bwd: g_predict overlaps target");
+  SAT_CHECK(!overlap(g_predict, gbytes, pixelweights, 4ull * (unsigned long long)total), "ubl_focal_bwd: g_predict overlaps pixelweights");
+  SAT_CHECK(!overlap(g_predict, gbytes, ctl, UBL_CTL_BYTES), "ubl_focal_bwd: g_predict overlaps ctl");
+  SAT_CHECK(!overlap(g_predict, gbytes, g_loss, 4), "ubl_focal_bwd: g_predict overlaps g_loss");
   const unsigned grid = grid_of(total);
   const bool vec = hw % 4 == 0 && aligned(predict, 16) && aligned(target, 16) && aligned(pixelweights, 16) && aligned(g_predict, 16);
   if (vec)
@@ -409,6 +335,6 @@ extern "C" int ubl_focal_bwd(const float* g_loss, const void* ctl, const float* 
     focal_bwd_kernel<false><<<dim3(grid), dim3(UBL_BLOCK), 0, (hipStream_t)stream>>>(g_loss, (const u64*)ctl, predict, (const long long*)target,
                                                                                     pixelweights, classw, C, hw, total, (long long)ignore_index,
                                                                                     gamma, g_predict);
-  UBL_LAUNCH_CHECK("ubl_focal_bwd");
+  SAT_LAUNCH_CHECK("ubl_focal_bwd");
   return UBL_OK;
 }

@@ -1,31 +1,15 @@
-// libubresnet_post.so: event products of whole-view inference (include/ubresnet_post.h).  Self-contained: nothing of
-// libubresnet_hip.so is linked or included, launches are plain <<<>>> on the caller's stream.
+// libubresnet_post.so: event products of whole-view inference (include/ubresnet_post.h).  It links against none of
+// the other libraries and shares ubr_sat.h with them; launches are plain <<<>>> on the caller's stream.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "../../include/ubresnet_post.h"
+#include "ubr_sat.h"
 
 #define UBP_VERSION 1
 
-static thread_local char g_ubp_err[512] = "";
-
-static void ubp_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_ubp_err, sizeof(g_ubp_err), fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* ubp_last_error(void) { return g_ubp_err; }
-extern "C" int ubp_version(void) { return UBP_VERSION; }
-
-#define UBP_CHECK(cond, ...)     \
-  do {                           \
-    if (!(cond)) {               \
-      ubp_set_error(__VA_ARGS__);\
-      return UBP_EINVAL;         \
-    }                            \
-  } while (0)
+SAT_RETURN_CODES(UBP);
+SAT_EXPORTS(ubp, UBP_VERSION)
+using namespace sat;
 
 namespace {
 
@@ -105,20 +89,20 @@ extern "C" int ubp_stitch_products(const float* logp, int C, int th, int tw, con
                                    const float* adc, int vplanes, float adc_threshold,
                                    uint8_t* label, uint16_t* confidence, unsigned long long* counts,
                                    int fill_label, int P, int rows, int cols, void* stream) {
-  UBP_CHECK(logp && label && confidence, "ubp_stitch_products: null pointer");
-  UBP_CHECK(tile_desc_host && ntiles >= 1 && ntiles <= UBP_MAX_TILES && th > 0 && tw > 0 && rows > 0 && cols > 0 && P >= 1 &&
+  SAT_CHECK(logp && label && confidence, "ubp_stitch_products: null pointer");
+  SAT_CHECK(tile_desc_host && ntiles >= 1 && ntiles <= UBP_MAX_TILES && th > 0 && tw > 0 && rows > 0 && cols > 0 && P >= 1 &&
             (long)th * tw < (1l << 30),
             "ubp_stitch_products: bad arguments (ntiles=%d must be 1..%d; th, tw, rows, cols, P positive, th * tw < 2^30)", ntiles, UBP_MAX_TILES);
-  UBP_CHECK(C >= 1 && C <= UBP_MAX_CLASSES, "ubp_stitch_products: C=%d must be 1..%d", C, UBP_MAX_CLASSES);
-  UBP_CHECK(vplanes >= 1, "ubp_stitch_products: vplanes=%d must be >= 1", vplanes);
-  UBP_CHECK(fill_label >= 0 && fill_label <= 255, "ubp_stitch_products: fill_label=%d must be 0..255", fill_label);
+  SAT_CHECK(C >= 1 && C <= UBP_MAX_CLASSES, "ubp_stitch_products: C=%d must be 1..%d", C, UBP_MAX_CLASSES);
+  SAT_CHECK(vplanes >= 1, "ubp_stitch_products: vplanes=%d must be >= 1", vplanes);
+  SAT_CHECK(fill_label >= 0 && fill_label <= 255, "ubp_stitch_products: fill_label=%d must be 0..255", fill_label);
   PostK k{};
   k.th = th; k.tw = tw; k.rows = rows; k.cols = cols; k.C = C; k.vplanes = vplanes; k.fill = fill_label; k.thr = adc_threshold;
   for (int t = 0; t < ntiles; ++t) {
     const int32_t* d = tile_desc_host + 7 * t;
-    UBP_CHECK(d[0] >= 0 && d[0] < P && d[1] >= 0 && d[2] >= 0 && d[1] < rows && d[2] < cols,
+    SAT_CHECK(d[0] >= 0 && d[0] < P && d[1] >= 0 && d[2] >= 0 && d[1] < rows && d[2] < cols,
               "ubp_stitch_products: tile %d origin out of range", t);
-    UBP_CHECK(d[3] >= 0 && d[3] <= d[4] && d[4] <= th && d[5] >= 0 && d[5] <= d[6] && d[6] <= tw,
+    SAT_CHECK(d[3] >= 0 && d[3] <= d[4] && d[4] <= th && d[5] >= 0 && d[5] <= d[6] && d[6] <= tw,
               "ubp_stitch_products: tile %d keep window out of range", t);
     k.plane[t] = d[0]; k.r0[t] = d[1]; k.c0[t] = d[2];
     k.kr0[t] = d[3]; k.kr1[t] = d[4] < rows - d[1] ? d[4] : rows - d[1];
@@ -126,10 +110,6 @@ extern "C" int ubp_stitch_products(const float* logp, int C, int th, int tw, con
   }
   const unsigned gx = (unsigned)(((long)th * tw + 256 * 8 - 1) / (256 * 8));
   stitch_products_kernel<<<dim3(gx, (unsigned)ntiles), dim3(256), 0, (hipStream_t)stream>>>(logp, adc, label, confidence, counts, k);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    ubp_set_error("ubp_stitch_products: launch failed: %s", hipGetErrorString(e));
-    return UBP_ELAUNCH;
-  }
+  SAT_LAUNCH_CHECK("ubp_stitch_products");
   return UBP_OK;
 }

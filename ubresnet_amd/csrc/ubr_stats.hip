@@ -1,11 +1,10 @@
-// libubresnet_stats.so: the guard of the BatchNorm running statistics (include/ubresnet_stats.h).  Self-contained: nothing of
-// the other nine libraries is linked or included, the launches are plain <<<>>> on the caller's stream.
+// libubresnet_stats.so: the guard of the BatchNorm running statistics (include/ubresnet_stats.h).  It links against
+// none of the other libraries and shares ubr_sat.h with them; the launches are plain <<<>>> on the caller's stream.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stddef.h>
-#include <stdio.h>
 #include "../../include/ubresnet_stats.h"
 #include "ubr_stats_decide.h"
+#include "ubr_sat.h"
 
 #define UBS_VERSION 1
 
@@ -17,33 +16,9 @@ static_assert(sizeof(ubs_seg) == 32 && offsetof(ubs_seg, live) == 8 && offsetof(
               "ubs_seg layout");
 static_assert((UBS_BLOCK & (UBS_BLOCK - 1)) == 0, "the local-memory reduction halves UBS_BLOCK");
 
-static thread_local char g_ubs_err[512] = "";
-
-static void ubs_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_ubs_err, sizeof(g_ubs_err), fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* ubs_last_error(void) { return g_ubs_err; }
-extern "C" int ubs_version(void) { return UBS_VERSION; }
-
-#define UBS_CHECK(cond, ...)     \
-  do {                           \
-    if (!(cond)) {               \
-      ubs_set_error(__VA_ARGS__);\
-      return UBS_EINVAL;         \
-    }                            \
-  } while (0)
-
-#define UBS_LAUNCH_CHECK(name)                                              \
-  do {                                                                      \
-    hipError_t e_ = hipGetLastError();                                      \
-    if (e_ != hipSuccess) {                                                 \
-      ubs_set_error(name ": launch failed: %s", hipGetErrorString(e_));     \
-      return UBS_ELAUNCH;                                                   \
-    }                                                                       \
-  } while (0)
+SAT_RETURN_CODES(UBS);
+SAT_EXPORTS(ubs, UBS_VERSION)
+using namespace sat;
 
 namespace {
 
@@ -122,64 +97,57 @@ __global__ __launch_bounds__(UBS_BLOCK) void resolve_kernel(const ubs_seg* __res
   }
 }
 
-inline bool aligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) == 0; }
-
-inline bool overlap(const void* a, unsigned long long abytes, const void* b, unsigned long long bbytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x != 0 && y != 0 && x < y + bbytes && y < x + abytes;
-}
-
 inline unsigned seg_grid(int64_t nseg) { return (unsigned)(nseg > UBS_SEG_GRID ? UBS_SEG_GRID : nseg); }
 
 }  // namespace
 
 extern "C" int ubs_ctl_init(void* ctl, void* stream) {
-  UBS_CHECK(ctl, "ubs_ctl_init: null ctl");
-  UBS_CHECK(aligned(ctl, 16), "ubs_ctl_init: ctl must be 16-byte aligned");
+  SAT_CHECK(ctl, "ubs_ctl_init: null ctl");
+  SAT_CHECK(aligned(ctl, 16), "ubs_ctl_init: ctl must be 16-byte aligned");
   ctl_init_kernel<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>((ubs_ctl*)ctl);
-  UBS_LAUNCH_CHECK("ubs_ctl_init");
+  SAT_LAUNCH_CHECK("ubs_ctl_init");
   return UBS_OK;
 }
 
 extern "C" int ubs_scan(const void* table, int64_t nseg, int32_t* bad, void* stream) {
-  UBS_CHECK(table && bad, "ubs_scan: null pointer (table, bad)");
-  UBS_CHECK(nseg >= 1 && nseg <= (INT64_MAX >> 6), "ubs_scan: nseg=%lld must be >= 1", (long long)nseg);
-  UBS_CHECK(aligned(table, 8) && aligned(bad, 4), "ubs_scan: table must be 8-byte and bad 4-byte aligned");
-  UBS_CHECK(!overlap(bad, 4ull * (unsigned long long)nseg, table, 32ull * (unsigned long long)nseg), "ubs_scan: bad overlaps table");
+  SAT_CHECK(table && bad, "ubs_scan: null pointer (table, bad)");
+  SAT_CHECK(nseg >= 1 && nseg <= (INT64_MAX >> 6), "ubs_scan: nseg=%lld must be >= 1", (long long)nseg);
+  SAT_CHECK(aligned(table, 8) && aligned(bad, 4), "ubs_scan: table must be 8-byte and bad 4-byte aligned");
+  SAT_CHECK(!overlap(bad, 4ull * (unsigned long long)nseg, table, 32ull * (unsigned long long)nseg), "ubs_scan: bad overlaps table");
   scan_kernel<<<dim3(seg_grid(nseg)), dim3(UBS_BLOCK), 0, (hipStream_t)stream>>>((const ubs_seg*)table, (long)nseg, bad);
-  UBS_LAUNCH_CHECK("ubs_scan");
+  SAT_LAUNCH_CHECK("ubs_scan");
   return UBS_OK;
 }
 
 extern "C" int ubs_note(int32_t* seen, const int32_t* bad, int64_t nseg, void* stream) {
-  UBS_CHECK(seen && bad, "ubs_note: null pointer (seen, bad)");
-  UBS_CHECK(nseg >= 1 && nseg <= (INT64_MAX >> 6), "ubs_note: nseg=%lld must be >= 1", (long long)nseg);
-  UBS_CHECK(aligned(seen, 4) && aligned(bad, 4), "ubs_note: seen and bad must be 4-byte aligned");
-  UBS_CHECK(!overlap(seen, 4ull * (unsigned long long)nseg, bad, 4ull * (unsigned long long)nseg), "ubs_note: seen overlaps bad");
+  SAT_CHECK(seen && bad, "ubs_note: null pointer (seen, bad)");
+  SAT_CHECK(nseg >= 1 && nseg <= (INT64_MAX >> 6), "ubs_note: nseg=%lld must be >= 1", (long long)nseg);
+  SAT_CHECK(aligned(seen, 4) && aligned(bad, 4), "ubs_note: seen and bad must be 4-byte aligned");
+  SAT_CHECK(!overlap(seen, 4ull * (unsigned long long)nseg, bad, 4ull * (unsigned long long)nseg), "ubs_note: seen overlaps bad");
   note_kernel<<<dim3(1), dim3(UBS_BLOCK), 0, (hipStream_t)stream>>>(seen, bad, (long)nseg);
-  UBS_LAUNCH_CHECK("ubs_note");
+  SAT_LAUNCH_CHECK("ubs_note");
   return UBS_OK;
 }
 
 extern "C" int ubs_decide(void* ctl, const int32_t* bad, int64_t nseg, const int32_t* apply_flag, int32_t check, void* stream) {
-  UBS_CHECK(ctl && bad, "ubs_decide: null pointer (ctl, bad)");
-  UBS_CHECK(nseg >= 1 && nseg <= (INT64_MAX >> 6), "ubs_decide: nseg=%lld must be >= 1", (long long)nseg);
-  UBS_CHECK(aligned(ctl, 16), "ubs_decide: ctl must be 16-byte aligned");
-  UBS_CHECK(aligned(bad, 4) && aligned(apply_flag, 4), "ubs_decide: bad and apply_flag must be 4-byte aligned");
-  UBS_CHECK(!overlap(ctl, UBS_CTL_BYTES, apply_flag, 4), "ubs_decide: apply_flag lies inside ctl");
-  UBS_CHECK(!overlap(ctl, UBS_CTL_BYTES, bad, 4ull * (unsigned long long)nseg), "ubs_decide: ctl overlaps bad");
-  UBS_CHECK(!overlap(apply_flag, 4, bad, 4ull * (unsigned long long)nseg), "ubs_decide: apply_flag lies inside bad");
+  SAT_CHECK(ctl && bad, "ubs_decide: null pointer (ctl, bad)");
+  SAT_CHECK(nseg >= 1 && nseg <= (INT64_MAX >> 6), "ubs_decide: nseg=%lld must be >= 1", (long long)nseg);
+  SAT_CHECK(aligned(ctl, 16), "ubs_decide: ctl must be 16-byte aligned");
+  SAT_CHECK(aligned(bad, 4) && aligned(apply_flag, 4), "ubs_decide: bad and apply_flag must be 4-byte aligned");
+  SAT_CHECK(!overlap(ctl, UBS_CTL_BYTES, apply_flag, 4), "ubs_decide: apply_flag lies inside ctl");
+  SAT_CHECK(!overlap(ctl, UBS_CTL_BYTES, bad, 4ull * (unsigned long long)nseg), "ubs_decide: ctl overlaps bad");
+  SAT_CHECK(!overlap(apply_flag, 4, bad, 4ull * (unsigned long long)nseg), "ubs_decide: apply_flag lies inside bad");
   decide_kernel<<<dim3(1), dim3(UBS_BLOCK), 0, (hipStream_t)stream>>>((ubs_ctl*)ctl, bad, (long)nseg, apply_flag, check);
-  UBS_LAUNCH_CHECK("ubs_decide");
+  SAT_LAUNCH_CHECK("ubs_decide");
   return UBS_OK;
 }
 
 extern "C" int ubs_resolve(const void* table, int64_t nseg, const void* ctl, void* stream) {
-  UBS_CHECK(table && ctl, "ubs_resolve: null pointer (table, ctl)");
-  UBS_CHECK(nseg >= 1 && nseg <= (INT64_MAX >> 6), "ubs_resolve: nseg=%lld must be >= 1", (long long)nseg);
-  UBS_CHECK(aligned(table, 8) && aligned(ctl, 16), "ubs_resolve: table must be 8-byte and ctl 16-byte aligned");
-  UBS_CHECK(!overlap(ctl, UBS_CTL_BYTES, table, 32ull * (unsigned long long)nseg), "ubs_resolve: ctl overlaps table");
+  SAT_CHECK(table && ctl, "ubs_resolve: null pointer (table, ctl)");
+  SAT_CHECK(nseg >= 1 && nseg <= (INT64_MAX >> 6), "ubs_resolve: nseg=%lld must be >= 1", (long long)nseg);
+  SAT_CHECK(aligned(table, 8) && aligned(ctl, 16), "ubs_resolve: table must be 8-byte and ctl 16-byte aligned");
+  SAT_CHECK(!overlap(ctl, UBS_CTL_BYTES, table, 32ull * (unsigned long long)nseg), "ubs_resolve: ctl overlaps table");
   resolve_kernel<<<dim3(seg_grid(nseg)), dim3(UBS_BLOCK), 0, (hipStream_t)stream>>>((const ubs_seg*)table, (long)nseg, (const ubs_ctl*)ctl);
-  UBS_LAUNCH_CHECK("ubs_resolve");
+  SAT_LAUNCH_CHECK("ubs_resolve");
   return UBS_OK;
 }

@@ -1,41 +1,16 @@
-// libubresnet_tta.so: flip test-time augmentation of inference (include/ubresnet_tta.h).  Self-contained: nothing of the other
-// twelve libraries is linked or included, the launches are plain <<<>>> on the caller's stream.
+// libubresnet_tta.so: flip test-time augmentation of inference (include/ubresnet_tta.h).  It links against none of the
+// other libraries and shares ubr_sat.h with them; the launches are plain <<<>>> on the caller's stream.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "../../include/ubresnet_tta.h"
+#include "ubr_sat.h"
 
 #define UBT_VERSION 1
 #define UBT_TRIP (UBT_BLOCK * UBT_UNROLL)
 
-static thread_local char g_ubt_err[512] = "";
-
-static void ubt_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_ubt_err, sizeof(g_ubt_err), fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* ubt_last_error(void) { return g_ubt_err; }
-extern "C" int ubt_version(void) { return UBT_VERSION; }
-
-#define UBT_CHECK(cond, ...)     \
-  do {                           \
-    if (!(cond)) {               \
-      ubt_set_error(__VA_ARGS__);\
-      return UBT_EINVAL;         \
-    }                            \
-  } while (0)
-
-#define UBT_LAUNCH_CHECK(name)                                              \
-  do {                                                                      \
-    hipError_t e_ = hipGetLastError();                                      \
-    if (e_ != hipSuccess) {                                                 \
-      ubt_set_error(name ": launch failed: %s", hipGetErrorString(e_));     \
-      return UBT_ELAUNCH;                                                   \
-    }                                                                       \
-  } while (0)
+SAT_RETURN_CODES(UBT);
+SAT_EXPORTS(ubt, UBT_VERSION)
+using namespace sat;
 
 namespace {
 
@@ -109,13 +84,6 @@ __global__ __launch_bounds__(UBT_BLOCK) void tta_kernel(const typename unit_of<V
   }
 }
 
-inline bool aligned(const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) == 0; }
-
-inline bool overlap(const void* a, unsigned long long abytes, const void* b, unsigned long long bbytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x != 0 && y != 0 && x < y + bbytes && y < x + abytes;
-}
-
 template <int FLIP, bool MERGE>
 void launch(const float* src, float* dst, long rows, int H, int W, int last, float log_k, hipStream_t stream) {
   const bool vec = W % 4 == 0 && aligned(src, 16) && aligned(dst, 16);
@@ -143,35 +111,35 @@ void launch_flip(const float* src, float* dst, long rows, int H, int W, int flip
 
 // the checks the two calls share; `name` starts the message, a / b are the argument names of the two buffers
 #define UBT_CHECK_PLANES(name, a, b, src, dst, nplanes, H, W, flip)                                                          \
-  UBT_CHECK((src) && (dst), name ": null pointer (" a ", " b ")");                                                          \
-  UBT_CHECK((nplanes) > 0 && (H) > 0 && (W) > 0, name ": nplanes=%lld, H=%d, W=%d must be positive", (long long)(nplanes), \
+  SAT_CHECK((src) && (dst), name ": null pointer (" a ", " b ")");                                                          \
+  SAT_CHECK((nplanes) > 0 && (H) > 0 && (W) > 0, name ": nplanes=%lld, H=%d, W=%d must be positive", (long long)(nplanes), \
             (int)(H), (int)(W));                                                                                            \
-  UBT_CHECK((nplanes) <= (int64_t)(1ll << 40) / (H) / (W), name ": nplanes=%lld x H=%d x W=%d exceeds 2^40 elements",       \
+  SAT_CHECK((nplanes) <= (int64_t)(1ll << 40) / (H) / (W), name ": nplanes=%lld x H=%d x W=%d exceeds 2^40 elements",       \
             (long long)(nplanes), (int)(H), (int)(W));                                                                      \
-  UBT_CHECK((flip) >= 0 && (flip) <= 3, name ": flip=%d must be a mask of UBT_FLIP_ROWS | UBT_FLIP_COLS (0..3)", (int)(flip)); \
-  UBT_CHECK(aligned((src), 4) && aligned((dst), 4), name ": " a " and " b " must be 4-byte aligned");                       \
-  UBT_CHECK(!overlap((src), 4ull * (unsigned long long)((nplanes) * (H) * (W)), (dst),                                      \
+  SAT_CHECK((flip) >= 0 && (flip) <= 3, name ": flip=%d must be a mask of UBT_FLIP_ROWS | UBT_FLIP_COLS (0..3)", (int)(flip)); \
+  SAT_CHECK(aligned((src), 4) && aligned((dst), 4), name ": " a " and " b " must be 4-byte aligned");                       \
+  SAT_CHECK(!overlap((src), 4ull * (unsigned long long)((nplanes) * (H) * (W)), (dst),                                      \
                      4ull * (unsigned long long)((nplanes) * (H) * (W))), name ": " a " overlaps " b)
 
 extern "C" int ubt_flip_planes(const float* src, float* dst, int64_t nplanes, int H, int W, int flip, void* stream) {
   UBT_CHECK_PLANES("ubt_flip_planes", "src", "dst", src, dst, nplanes, H, W, flip);
   launch_flip<false>(src, dst, (long)nplanes * H, H, W, flip, 0, 0.f, (hipStream_t)stream);
-  UBT_LAUNCH_CHECK("ubt_flip_planes");
+  SAT_LAUNCH_CHECK("ubt_flip_planes");
   return UBT_OK;
 }
 
 extern "C" int ubt_merge_view(const float* logp, float* acc, int64_t nplanes, int H, int W, int flip, int k, int K, float log_k,
                               void* stream) {
   UBT_CHECK_PLANES("ubt_merge_view", "logp", "acc", logp, acc, nplanes, H, W, flip);
-  UBT_CHECK(K >= 1 && K <= UBT_MAX_VIEWS, "ubt_merge_view: K=%d must be in 1..%d (UBT_MAX_VIEWS)", K, UBT_MAX_VIEWS);
-  UBT_CHECK(k >= 0 && k < K, "ubt_merge_view: k=%d must be in 0..K-1 (K=%d)", k, K);
+  SAT_CHECK(K >= 1 && K <= UBT_MAX_VIEWS, "ubt_merge_view: K=%d must be in 1..%d (UBT_MAX_VIEWS)", K, UBT_MAX_VIEWS);
+  SAT_CHECK(k >= 0 && k < K, "ubt_merge_view: k=%d must be in 0..K-1 (K=%d)", k, K);
   const int last = K > 1 && k == K - 1;
-  UBT_CHECK(!last || (log_k == log_k && log_k > 0.f && log_k < INFINITY),
+  SAT_CHECK(!last || (log_k == log_k && log_k > 0.f && log_k < INFINITY),
             "ubt_merge_view: log_k=%g must be finite and > 0 for the last of K=%d views", (double)log_k, K);
   if (k == 0)
     launch_flip<false>(logp, acc, (long)nplanes * H, H, W, flip, 0, 0.f, (hipStream_t)stream);
   else
     launch_flip<true>(logp, acc, (long)nplanes * H, H, W, flip, last, log_k, (hipStream_t)stream);
-  UBT_LAUNCH_CHECK("ubt_merge_view");
+  SAT_LAUNCH_CHECK("ubt_merge_view");
   return UBT_OK;
 }

@@ -1,31 +1,15 @@
-// libubresnet_weight.so: device-side pixel weights for PixelWiseNLLLoss (include/ubresnet_weight.h).  Self-contained: nothing
-// of the other libraries is linked or included, launches are plain <<<>>> on the caller's stream.
+// libubresnet_weight.so: device-side pixel weights for PixelWiseNLLLoss (include/ubresnet_weight.h).  It links against
+// none of the other libraries and shares ubr_sat.h with them; launches are plain <<<>>> on the caller's stream.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include "ubr_weight_tile.h"
+#include "ubr_sat.h"
 
 #define UBW_VERSION 1
 
-static thread_local char g_ubw_err[512] = "";
-
-static void ubw_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_ubw_err, sizeof(g_ubw_err), fmt, ap);
-  va_end(ap);
-}
-extern "C" const char* ubw_last_error(void) { return g_ubw_err; }
-extern "C" int ubw_version(void) { return UBW_VERSION; }
-
-#define UBW_CHECK(cond, ...)     \
-  do {                           \
-    if (!(cond)) {               \
-      ubw_set_error(__VA_ARGS__);\
-      return UBW_EINVAL;         \
-    }                            \
-  } while (0)
+SAT_RETURN_CODES(UBW);
+SAT_EXPORTS(ubw, UBW_VERSION)
+using namespace sat;
 
 namespace {
 
@@ -119,29 +103,27 @@ __global__ __launch_bounds__(UBW_BLOCK) void apply_kernel(const ApplyK k) {
   finish<R>(k, k.wgt + (long)b * n, x0, y0, t, own, rm, wc);
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int ubw_pixel_weights(const int64_t* label, float* weight, int64_t* counts,
                                  int B, int H, int W, int C,
                                  float max_weight, int radius, float gain, int lo, void* stream) {
-  UBW_CHECK(label && weight && counts, "ubw_pixel_weights: null pointer (label %p, weight %p, counts %p)", (const void*)label,
+  SAT_CHECK(label && weight && counts, "ubw_pixel_weights: null pointer (label %p, weight %p, counts %p)", (const void*)label,
             (void*)weight, (void*)counts);
-  UBW_CHECK(B >= 1 && H >= 1 && W >= 1, "ubw_pixel_weights: B=%d, H=%d, W=%d must be >= 1", B, H, W);
+  SAT_CHECK(B >= 1 && H >= 1 && W >= 1, "ubw_pixel_weights: B=%d, H=%d, W=%d must be >= 1", B, H, W);
   const long long hw = (long long)H * W;
-  UBW_CHECK(hw < (1ll << 31) && (long long)B * hw < (1ll << 31), "ubw_pixel_weights: B*H*W = %d*%d*%d must be below 2^31", B, H, W);
-  UBW_CHECK(C >= 1 && C <= UBW_MAX_CLASSES, "ubw_pixel_weights: C=%d must be 1..%d", C, UBW_MAX_CLASSES);
-  UBW_CHECK(radius >= 0 && radius <= UBW_MAX_RADIUS, "ubw_pixel_weights: radius=%d must be 0..%d", radius, UBW_MAX_RADIUS);
-  UBW_CHECK(lo >= 0 && lo <= C, "ubw_pixel_weights: lo=%d must be 0..C=%d", lo, C);
-  UBW_CHECK(max_weight > 0.0f, "ubw_pixel_weights: max_weight=%g must be > 0 (+inf: no cap)", (double)max_weight);
-  UBW_CHECK(gain >= 0.0f && gain < INFINITY, "ubw_pixel_weights: gain=%g must be finite and >= 0", (double)gain);
-  UBW_CHECK(aligned(label, 8) && aligned(counts, 8) && aligned(weight, 4),
+  SAT_CHECK(hw < (1ll << 31) && (long long)B * hw < (1ll << 31), "ubw_pixel_weights: B*H*W = %d*%d*%d must be below 2^31", B, H, W);
+  SAT_CHECK(C >= 1 && C <= UBW_MAX_CLASSES, "ubw_pixel_weights: C=%d must be 1..%d", C, UBW_MAX_CLASSES);
+  SAT_CHECK(radius >= 0 && radius <= UBW_MAX_RADIUS, "ubw_pixel_weights: radius=%d must be 0..%d", radius, UBW_MAX_RADIUS);
+  SAT_CHECK(lo >= 0 && lo <= C, "ubw_pixel_weights: lo=%d must be 0..C=%d", lo, C);
+  SAT_CHECK(max_weight > 0.0f, "ubw_pixel_weights: max_weight=%g must be > 0 (+inf: no cap)", (double)max_weight);
+  SAT_CHECK(gain >= 0.0f && gain < INFINITY, "ubw_pixel_weights: gain=%g must be finite and >= 0", (double)gain);
+  SAT_CHECK(aligned(label, 8) && aligned(counts, 8) && aligned(weight, 4),
             "ubw_pixel_weights: a pointer lacks its natural alignment (4 bytes for float, 8 for int64_t)");
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(counts, 0, sizeof(int64_t) * UBW_MAX_CLASSES * (size_t)B, s);
   if (e != hipSuccess) {
-    ubw_set_error("ubw_pixel_weights: memset of counts failed: %s", hipGetErrorString(e));
+    set_error("ubw_pixel_weights: memset of counts failed: %s", hipGetErrorString(e));
     return UBW_ELAUNCH;
   }
   CountK ck{};
@@ -154,7 +136,7 @@ extern "C" int ubw_pixel_weights(const int64_t* label, float* weight, int64_t* c
   count_kernel<<<dim3((unsigned)(gx * B)), dim3(UBW_BLOCK), 0, s>>>(ck);
   e = hipGetLastError();
   if (e != hipSuccess) {
-    ubw_set_error("ubw_pixel_weights: launch of the count pass failed: %s", hipGetErrorString(e));
+    set_error("ubw_pixel_weights: launch of the count pass failed: %s", hipGetErrorString(e));
     return UBW_ELAUNCH;
   }
   ApplyK k{};
@@ -175,7 +157,7 @@ extern "C" int ubw_pixel_weights(const int64_t* label, float* weight, int64_t* c
   }
   e = hipGetLastError();
   if (e != hipSuccess) {
-    ubw_set_error("ubw_pixel_weights: launch of the apply pass failed: %s", hipGetErrorString(e));
+    set_error("ubw_pixel_weights: launch of the apply pass failed: %s", hipGetErrorString(e));
     return UBW_ELAUNCH;
   }
   return UBW_OK;
