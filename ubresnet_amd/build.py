@@ -1,6 +1,6 @@
 """Build the package's shared libraries with hipcc for gfx950, in-tree.
 
-    python -m ubresnet_amd.build [--force] [--extras]
+    python -m ubresnet_amd.build [--force] [--addons] [--extras]
 
 LIBS is the table of them, in build order: name -> (out, sources, headers, binding).  `hip` is libubresnet_hip.so, all HIP kernels
 of the network and its C ABI; every other entry is a library of one .hip file that links against none of the
@@ -10,8 +10,9 @@ being every file the sources reach through quoted #includes; `binding` names the
 The shared libraries have NO PyTorch dependency: they are plain HIP behind the public headers in include/.  Objects are compiled
 in parallel, one per translation unit, with the same flags.  source_hash() covers the network's library only.
 
-EXTRAS is a second table of the same tuples, for libraries whose sources live under csrc/extra/: build_extras() builds it with the
-same compiler, flags and commands, `--extras` builds it after LIBS.  (Why there are two tables: DESIGN.md, "Two build tables".)
+EXTRAS and ADDONS are two more tables of the same tuples, for libraries whose sources live under csrc/extra/: build_extras() and
+build_addons() build them with the same compiler, flags and commands; on the command line `--addons` and `--extras` build them
+after LIBS, ADDONS first.  (Why there are three tables: DESIGN.md, "Three build tables".)
 """
 from collections import namedtuple
 import os
@@ -53,6 +54,12 @@ LIBS = {
 EXTRAS = {
     "score": Lib(os.path.join(HERE, "libubresnet_score.so"), [os.path.join("extra", "ubr_score.hip")],
                  ["ubr_sat.h", "ubr_rows.h", os.path.join("..", "..", "include", "ubresnet_score.h")], "_score"),
+}
+
+# the libraries after EXTRAS join this table: its tests pin what it contains, not its length
+ADDONS = {
+    "blend": Lib(os.path.join(HERE, "libubresnet_blend.so"), [os.path.join("extra", "ubr_blend.hip")],
+                 ["ubr_sat.h", os.path.join("..", "..", "include", "ubresnet_blend.h")], "_blend"),
 }
 
 
@@ -139,8 +146,15 @@ def build_extras(force=False, verbose=True, only=None):
     return _build(EXTRAS, "build_extras", force, verbose, only, lambda: sys.stderr)
 
 
+def build_addons(force=False, verbose=True, only=None):
+    """the same for ADDONS; echoed to stderr as well"""
+    return _build(ADDONS, "build_addons", force, verbose, only, lambda: sys.stderr)
+
+
 if __name__ == "__main__":
     paths = build(force="--force" in sys.argv)
+    if "--addons" in sys.argv:
+        paths += build_addons(force="--force" in sys.argv)
     if "--extras" in sys.argv:
         paths += build_extras(force="--force" in sys.argv)
     print("\n".join(paths))

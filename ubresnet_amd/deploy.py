@@ -19,6 +19,9 @@ Mirrors the inference side of the reference:
   * flip test-time augmentation (``tta=("rows", "cols", "both")``): training flips every axis with probability 1/2 (``Augment``),
     so the network is evaluated on the flipped views of every batch as well and the class probabilities are averaged
     (include/ubresnet_tta.h) before the unchanged stitch or event products.
+  * overlap-tile inference (``margin=``, ``blend="linear"`` / ``"hann"``): a denser tiling that keeps every kept pixel at least
+    `margin` pixels away from a tile edge the network padded with zeros, and, with `blend`, overlapping tiles that vote: the
+    stitch becomes the log of a weighted mean of the covering tiles' probabilities (include/ubresnet_blend.h).
 """
 from __future__ import annotations
 
@@ -29,6 +32,7 @@ import torch
 
 from . import _lib as L
 from . import _post as PL
+from . import _blend as VL
 from . import _tta as TL
 
 
@@ -203,12 +207,30 @@ def regular_tiling(rows: int, cols: int, th: int = 512, tw: int = 832) -> Tuple[
     return origins(rows, th), origins(cols, tw)
 
 
-def view_tiles(rows: int, cols: int, planes: int, th: int, tw: int, stacked: bool):
+def margin_tiling(rows: int, cols: int, th: int = 512, tw: int = 832, margin: int = 0) -> Tuple[List[int], List[int]]:
+    """row/col origins of the fewest evenly spread tiles whose neighbours overlap by at least 2 * margin: per axis of length n
+    and tile t, [0] if n <= t, else k = ceil((n - t) / (t - 2 * margin)) + 1 tiles at round(i * (n - t) / (k - 1)).  The integer
+    steps are the floor or the ceiling of a real step <= t - 2 * margin, so every overlap is at least 2 * margin and the
+    mid-overlap keep windows (_keep_windows) leave at least `margin` pixels between a kept pixel and any tile edge that is not
+    the view's own.  margin = 0 is regular_tiling.  0 <= 4 * margin <= min(th, tw), else ValueError."""
+    if isinstance(margin, bool) or not isinstance(margin, int) or margin < 0 or 4 * margin > min(th, tw):
+        raise ValueError("margin must be an int with 0 <= 4 * margin <= min(tile) = %d (got %r)" % (min(th, tw), margin))
+
+    def origins(n, t):
+        if n <= t:
+            return [0]
+        k = -(-(n - t) // (t - 2 * margin)) + 1
+        step = (n - t) / float(k - 1)
+        return sorted(set(int(round(i * step)) for i in range(k)))
+    return origins(rows, th), origins(cols, tw)
+
+
+def view_tiles(rows: int, cols: int, planes: int, th: int, tw: int, stacked: bool, margin: int = 0):
     """tile descriptors {plane, row0, col0, keep_r0, keep_r1, keep_c0, keep_c1} (ubr_crop_tiles / ubr_stitch_tiles) of the
-    regular tiling.  Per plane: one descriptor per (plane, row origin, column origin).  Stacked (a model that takes the planes
-    as channels): one descriptor per (row origin, column origin) with plane 0 -- stacked_crop_desc() expands it for the crop,
-    the stitch takes it as it is with P = 1."""
-    ro, co = regular_tiling(rows, cols, th, tw)
+    regular tiling, or of margin_tiling with `margin` > 0.  Per plane: one descriptor per (plane, row origin, column origin).
+    Stacked (a model that takes the planes as channels): one descriptor per (row origin, column origin) with plane 0 --
+    stacked_crop_desc() expands it for the crop, the stitch takes it as it is with P = 1."""
+    ro, co = margin_tiling(rows, cols, th, tw, margin) if margin else regular_tiling(rows, cols, th, tw)
     rk, ck = _keep_windows(ro, th, rows), _keep_windows(co, tw, cols)
     tiles = []
     for p in range(1 if stacked else planes):
@@ -254,13 +276,26 @@ class WholeViewSegmenter:
     through the same captured graph once per view (the identity first, then the named flips in the order given) and the views'
     log-probabilities are merged, un-flipped, into the log of their mean probability (include/ubresnet_tta.h) before the unchanged
     stitch or event products.  None / (): off, today's path call for call.
+
+    margin=m (0 <= 4 m <= the smaller tile side): the tiling of margin_tiling, whose overlaps are at least 2 m wide, so that no
+    kept pixel lies within m pixels of a tile edge inside the view (the networks zero-pad every conv there).  More tiles per
+    event; the crop, stitch and products kernels are the same.  blend="linear" or "hann": overlapping tiles vote instead of being
+    cut in the middle.  Along each axis a tile's weight is zero within `margin` of such an edge, rises over the next
+    ceil(t / 2) - m pixels (linearly, or as sin^2) to one, and the weights of the tiles covering a pixel are normalised to sum to
+    one; a tile's weight at a pixel is its row weight times its column weight.  The scores are the log of that weighted mean of
+    probabilities (include/ubresnet_blend.h: one ubv_blend_begin per call, one ubv_blend_tiles per chunk in place of the stitch,
+    after the merge of the views with `tta`); the log-weights are two tables built once, here.  output="products" with blend
+    needs the dense [planes,C,rows,cols] float32 buffer that plain products avoid: it is kept between calls, and one
+    ubp_stitch_products launch over the finished buffer, every plane one whole-view tile, makes the products.  With
+    margin=0, blend=None the path is today's, call for call.
     """
 
     def __init__(self, model, rows: int, cols: int, planes: int = 3, tile=(512, 832), batch: int = 10,
                  dtype: torch.dtype = torch.float16, use_graph: bool = True, output: str = "scores",
-                 adc_threshold: Optional[float] = 10.0, fill_label: int = 255, tta=None):
+                 adc_threshold: Optional[float] = 10.0, fill_label: int = 255, tta=None, margin: int = 0, blend=None):
         _check_output(output)
         self._flips = TL.parse_views(tta)                   # () or (0, flip mask of every named view)
+        self.blend = VL.check_kind(blend)
         self.output, self.adc_threshold, self.fill_label = output, adc_threshold, fill_label
         self.model, self.rows, self.cols, self.planes = model, rows, cols, planes
         self.th, self.tw = tile
@@ -273,7 +308,9 @@ class WholeViewSegmenter:
                              "are supported" % (cin, planes))
         self.stacked = cin > 1
         self.cin = cin
-        self.tiles = view_tiles(rows, cols, planes, self.th, self.tw, self.stacked)     # (plane, r0, c0, kr0, kr1, kc0, kc1)
+        self.margin = margin
+        self._origins = margin_tiling(rows, cols, self.th, self.tw, margin)             # refuses a bad margin; 0: regular_tiling
+        self.tiles = view_tiles(rows, cols, planes, self.th, self.tw, self.stacked, margin)     # (plane, r0, c0, kr0, kr1, kc0, kc1)
         if batch * cin > L.MAX_TILES:
             raise ValueError("batch * planes must be <= %d tile descriptors (UBR_MAX_TILES)" % L.MAX_TILES)
         self.nclass = model.conv11.out_channels
@@ -285,6 +322,18 @@ class WholeViewSegmenter:
         self._captured_sig = None
         self._tta_side = None                               # the cropped chunk, unflipped; lives and dies with _static_in
         self._tta_merged = None                             # the running merge of the views' log-probabilities
+        self._blend_lw = None                               # (lw_rows [ntiles][th], lw_cols [ntiles][tw]) on the device
+        self._blend_out = None                              # products with blend: the dense scores, kept between calls
+        if self.blend is not None:
+            if batch > VL.MAX_TILES:
+                raise ValueError("batch must be <= %d tile descriptors (UBV_MAX_TILES) with blend" % VL.MAX_TILES)
+            ro, co = self._origins
+            lr = VL.axis_log_weights(ro, self.th, rows, margin, self.blend)
+            lc = VL.axis_log_weights(co, self.tw, cols, margin, self.blend)
+            # in the order of self.tiles: planes x row origins x column origins; float64, rounded once when they go to the device
+            reps = 1 if self.stacked else planes
+            self._blend_host = (torch.tensor([r for _ in range(reps) for r in lr for _ in co], dtype=torch.float64),
+                                torch.tensor([c for _ in range(reps) for _ in ro for c in lc], dtype=torch.float64))
 
     @property
     def tiles_per_event(self):
@@ -338,10 +387,24 @@ class WholeViewSegmenter:
         self._ensure_graph(view.device)
         oplanes = 1 if self.stacked else self.planes
         products = self.output == "products"
+        blended = None
+        if self.blend is not None:
+            if self._blend_lw is None or self._blend_lw[0].device != view.device:
+                self._blend_lw = tuple(t.to(torch.float32).to(view.device) for t in self._blend_host)
+            shape = (oplanes, self.nclass, self.rows, self.cols)
+            if not products:
+                blended = torch.empty(shape, dtype=torch.float32, device=view.device)
+            else:
+                if self._blend_out is None or self._blend_out.device != view.device:
+                    self._blend_out = torch.empty(shape, dtype=torch.float32, device=view.device)
+                blended = self._blend_out
+            VL.blend_begin(blended.data_ptr(), blended.numel(), L.stream_ptr())
         if products:                     # label / confidence uninitialised: the tiling covers the view
             out = Products(torch.empty((oplanes, self.rows, self.cols), dtype=torch.uint8, device=view.device),
                            torch.empty((oplanes, self.rows, self.cols), dtype=torch.float16, device=view.device),
                            torch.zeros((oplanes, self.nclass), dtype=torch.int64, device=view.device))
+        elif blended is not None:
+            out = blended
         else:
             out = torch.empty((oplanes, self.nclass, self.rows, self.cols), dtype=torch.float32, device=view.device)
         lib = L.lib()
@@ -366,12 +429,23 @@ class WholeViewSegmenter:
                                   len(self._flips), L.stream_ptr())
             if self._flips:
                 scores = self._tta_merged
+            if blended is not None:
+                VL.blend_tiles(scores.data_ptr(), self.nclass, self.th, self.tw, VL.desc3(chunk), n,
+                               self._blend_lw[0][i:].data_ptr(), self._blend_lw[1][i:].data_ptr(), blended.data_ptr(), oplanes,
+                               self.rows, self.cols, L.stream_ptr())
+                continue
             if products:
                 _stitch_products(scores, self.nclass, self.th, self.tw, chunk, view, self.planes if self.stacked else 1,
                                  self.adc_threshold, self.fill_label, out, oplanes, self.rows, self.cols)
                 continue
             L.check(lib.ubr_stitch_tiles(scores.data_ptr(), self.nclass, self.th, self.tw, desc, n, out.data_ptr(),
                                          oplanes, self.rows, self.cols, L.stream_ptr()), "stitch_tiles")
+        if products and blended is not None:
+            for j in range(0, oplanes, PL.MAX_TILES):
+                whole = [(p, 0, 0, 0, self.rows, 0, self.cols) for p in range(j, min(j + PL.MAX_TILES, oplanes))]
+                _stitch_products(blended[j:j + len(whole)], self.nclass, self.rows, self.cols, whole, view,
+                                 self.planes if self.stacked else 1, self.adc_threshold, self.fill_label, out, oplanes, self.rows,
+                                 self.cols)
         if products:
             return Products(*(t[0] for t in out)) if self.stacked else out
         return out[0] if self.stacked else out
