@@ -148,6 +148,47 @@ def test_grad_completion_order_covers_all_parameters():
     assert names[0] == "conv11.weight" and names[-1] == "conv1.bias"
 
 
+@pytest.mark.parametrize("kind", ["uresnet", "aspp"])
+def test_grad_completion_order_stage_ends_tile_the_flat_buffer(kind):
+    """the arithmetic of Engine._stage_notifier: a stage reports flat[done:hi] with hi the padded end of the stage's last
+    parameter.  For the stage ends the two backward schedules name (head, dec_layer1..5, enc_layer5..1, the last parameter)
+    those ends must rise strictly and finish at grad_numel -- a parameter listed behind its stage's end would be reported one
+    stage late, one listed before it one stage early (exchanged before it is written)"""
+    from ubresnet_amd.engine import Engine
+    if kind == "uresnet":
+        from ubresnet_amd.models.ub_uresnet import UResNet
+        m = UResNet(num_classes=3, input_channels=1, inplanes=16)
+    else:
+        from ubresnet_amd.models.ASPP_ResNet import ASPP_ResNet
+        m = ASPP_ResNet(num_classes=3, in_channels=3, inplanes=16, showsizes=False)
+    eng = Engine(m, kind)
+    names = [n for n, _ in eng.grad_order]
+    assert sorted(names) == sorted(n for n, _ in m.named_parameters()) and len(set(names)) == len(names)
+    ends = (["bn10.bias"] + ["dec_layer%d.deconv.weight" % i for i in (1, 2, 3, 4, 5)]
+            + ["enc_layer%d.res1.conv1.weight" % i for i in (5, 4, 3, 2, 1)] + [names[-1]])
+    params = dict(eng.grad_order)
+    his = [eng.grad_offsets[n] + (params[n].numel() + 3) // 4 * 4 for n in ends]
+    assert len(his) == 12 and all(b > a for a, b in zip([0] + his, his)), his
+    assert his[-1] == eng.grad_numel
+    # every parameter lies inside the range of the stage whose launches write it
+    stage_of = lambda n: sum(eng.grad_offsets[n] >= h for h in his)
+    for n in names:
+        top = n.split(".")[0]
+        if top in ("conv11", "conv10", "bn10"):
+            want = 0
+        elif top.startswith("dec_layer"):
+            want = int(top[-1])
+        elif top.startswith("enc_layer") or top.startswith("ASPP_"):
+            want = 11 - int(top[-1])           # an ASPP level is back-propagated right before its encoder level
+        else:
+            want = 11                          # stem
+        assert stage_of(n) == want, (n, stage_of(n), want)
+    # offsets are 16-byte aligned and slots do not overlap
+    offs = [eng.grad_offsets[n] for n in names]
+    assert all(o % 4 == 0 for o in offs)
+    assert all(o + params[n].numel() <= o2 for n, o, o2 in zip(names, offs, offs[1:] + [eng.grad_numel]))
+
+
 def test_shard_range():
     from ubresnet_amd.dist import shard_range
     assert [shard_range(128, r, 8) for r in (0, 7)] == [(0, 16), (112, 128)]
