@@ -60,6 +60,8 @@ EXTRAS = {
 ADDONS = {
     "blend": Lib(os.path.join(HERE, "libubresnet_blend.so"), [os.path.join("extra", "ubr_blend.hip")],
                  ["ubr_sat.h", os.path.join("..", "..", "include", "ubresnet_blend.h")], "_blend"),
+    "sparse": Lib(os.path.join(HERE, "libubresnet_sparse.so"), [os.path.join("extra", "ubr_sparse.hip")],
+                  ["ubr_sat.h", "ubr_sparse_plan.h", os.path.join("..", "..", "include", "ubresnet_sparse.h")], "_sparse"),
 }
 
 

@@ -34,6 +34,7 @@ from . import _lib as L
 from . import _post as PL
 from . import _blend as VL
 from . import _tta as TL
+from . import sparse as SP
 
 
 class Products(NamedTuple):
@@ -44,9 +45,10 @@ class Products(NamedTuple):
     counts: torch.Tensor
 
 
-def _check_output(output):
-    if output not in ("scores", "products"):
-        raise ValueError("output must be 'scores' or 'products' (got %r)" % (output,))
+def _check_output(output, pixels=False):
+    """`pixels`: the caller also has the lit-pixel list (WholeViewSegmenter; segment_crops has not)"""
+    if output not in (("scores", "products", "pixels") if pixels else ("scores", "products")):
+        raise ValueError("output must be 'scores'%s or 'products' (got %r)" % (", 'pixels'" if pixels else "", output))
 
 
 def _check_cover(tiles, P, rows, cols):
@@ -288,12 +290,30 @@ class WholeViewSegmenter:
     needs the dense [planes,C,rows,cols] float32 buffer that plain products avoid: it is kept between calls, and one
     ubp_stitch_products launch over the finished buffer, every plane one whole-view tile, makes the products.  With
     margin=0, blend=None the path is today's, call for call.
+
+    Sparse I/O (ubresnet_amd/sparse.py, include/ubresnet_sparse.h).  The call also takes a sparse.SparseEvent in place of the
+    dense view, for every `output`: the list is copied to the device if it is on the host and scattered into a view buffer that
+    is kept between calls; `seg.status` is the device word that counts the entries the scatter refused.  output="pixels" runs the
+    unchanged products path into dense buffers kept between calls and compacts them, on the same stream, into a
+    sparse.PixelList of the lit pixels in ascending pixel-index order (`capacity` entries; None: as many as there are pixels);
+    the list's buffers are kept between calls too, so a call overwrites the list of the call before it.  Nothing is read back:
+    PixelList.read() is the host synchronisation.  With a dense view and "scores" / "products" nothing here runs.
     """
 
     def __init__(self, model, rows: int, cols: int, planes: int = 3, tile=(512, 832), batch: int = 10,
                  dtype: torch.dtype = torch.float16, use_graph: bool = True, output: str = "scores",
-                 adc_threshold: Optional[float] = 10.0, fill_label: int = 255, tta=None, margin: int = 0, blend=None):
-        _check_output(output)
+                 adc_threshold: Optional[float] = 10.0, fill_label: int = 255, tta=None, margin: int = 0, blend=None,
+                 capacity: Optional[int] = None):
+        _check_output(output, pixels=True)
+        if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 1):
+            raise ValueError("capacity must be None or an int >= 1 (got %r)" % (capacity,))
+        if capacity is not None and output != "pixels":
+            raise ValueError("capacity is the length of the pixel list: it needs output='pixels'")
+        self.capacity = capacity
+        self.status = None                                  # sparse input: refused entries, counted on the device (int64 [1])
+        self._view_buf = None                               # sparse input: the dense view, kept between calls
+        self._pix_dense = None                              # output="pixels": the dense label / confidence, kept between calls
+        self._compactor = None                              # output="pixels": the list's buffers and scratch, kept between calls
         self._flips = TL.parse_views(tta)                   # () or (0, flip mask of every named view)
         self.blend = VL.check_kind(blend)
         self.output, self.adc_threshold, self.fill_label = output, adc_threshold, fill_label
@@ -314,7 +334,7 @@ class WholeViewSegmenter:
         if batch * cin > L.MAX_TILES:
             raise ValueError("batch * planes must be <= %d tile descriptors (UBR_MAX_TILES)" % L.MAX_TILES)
         self.nclass = model.conv11.out_channels
-        if output == "products":
+        if output in ("products", "pixels"):
             _check_cover(self.tiles, 1 if self.stacked else planes, rows, cols)
         self._graph = None
         self._static_in = None
@@ -378,7 +398,21 @@ class WholeViewSegmenter:
                 self._graph = g
 
     @torch.no_grad()
-    def __call__(self, view: torch.Tensor):
+    def _scatter(self, event):
+        """a SparseEvent -> the dense view in the buffer kept between calls, on the model's device (or the list's own)"""
+        if (event.planes, event.rows, event.cols) != (self.planes, self.rows, self.cols):
+            raise RuntimeError("WholeViewSegmenter: expected a SparseEvent of %d x %d x %d, got %d x %d x %d"
+                               % (self.planes, self.rows, self.cols, event.planes, event.rows, event.cols))
+        device = event.index.device if event.index.is_cuda else next(self.model.parameters()).device
+        if self._view_buf is None or self._view_buf.device != device:
+            self._view_buf = torch.empty((self.planes, 1, self.rows, self.cols), dtype=torch.float32, device=device)
+            self.status = torch.zeros(1, dtype=torch.int64, device=device)
+        return event.to_view(device, out=self._view_buf, status=self.status)
+
+    @torch.no_grad()
+    def __call__(self, view):
+        if isinstance(view, SP.SparseEvent):
+            view = self._scatter(view)
         L.require_cuda(view, "view")
         if view.dtype != torch.float32 or tuple(view.shape) != (self.planes, 1, self.rows, self.cols):
             raise RuntimeError("WholeViewSegmenter: expected float32 [%d,1,%d,%d], got %s %s"
@@ -386,7 +420,8 @@ class WholeViewSegmenter:
         view = view.contiguous()
         self._ensure_graph(view.device)
         oplanes = 1 if self.stacked else self.planes
-        products = self.output == "products"
+        pixels = self.output == "pixels"
+        products = pixels or self.output == "products"
         blended = None
         if self.blend is not None:
             if self._blend_lw is None or self._blend_lw[0].device != view.device:
@@ -399,7 +434,14 @@ class WholeViewSegmenter:
                     self._blend_out = torch.empty(shape, dtype=torch.float32, device=view.device)
                 blended = self._blend_out
             VL.blend_begin(blended.data_ptr(), blended.numel(), L.stream_ptr())
-        if products:                     # label / confidence uninitialised: the tiling covers the view
+        if pixels:                       # the dense products of the list: kept between calls, every pixel written by the tiling
+            if self._pix_dense is None or self._pix_dense[0].device != view.device:
+                self._pix_dense = (torch.empty((oplanes, self.rows, self.cols), dtype=torch.uint8, device=view.device),
+                                   torch.empty((oplanes, self.rows, self.cols), dtype=torch.float16, device=view.device))
+                self._compactor = SP.Compactor(oplanes, self.rows, self.cols, self.capacity, view.device)
+            out = Products(self._pix_dense[0], self._pix_dense[1],
+                           torch.zeros((oplanes, self.nclass), dtype=torch.int64, device=view.device))
+        elif products:                   # label / confidence uninitialised: the tiling covers the view
             out = Products(torch.empty((oplanes, self.rows, self.cols), dtype=torch.uint8, device=view.device),
                            torch.empty((oplanes, self.rows, self.cols), dtype=torch.float16, device=view.device),
                            torch.zeros((oplanes, self.nclass), dtype=torch.int64, device=view.device))
@@ -446,6 +488,9 @@ class WholeViewSegmenter:
                 _stitch_products(blended[j:j + len(whole)], self.nclass, self.rows, self.cols, whole, view,
                                  self.planes if self.stacked else 1, self.adc_threshold, self.fill_label, out, oplanes, self.rows,
                                  self.cols)
+        if pixels:
+            return self._compactor(out.label, out.confidence, out.counts[0] if self.stacked else out.counts, view,
+                                   self.planes if self.stacked else 1, self.adc_threshold, self.fill_label)
         if products:
             return Products(*(t[0] for t in out)) if self.stacked else out
         return out[0] if self.stacked else out
