@@ -35,11 +35,16 @@ sg = StatsGuard(model, optimizer=opt) if "--stats-guard" in sys.argv else None  
 accumulate = int(sys.argv[sys.argv.index("--accumulate") + 1]) if "--accumulate" in sys.argv else 1   # --accumulate K: one optimizer step per K batches (GradAccumulator); 300 steps are then 300 * K batches
 ld = synthetic.SyntheticLArCVDataset(height=512, width=512, tag="train", nentries=64, cache=64); ld.start(16)
 if weights is not None: ld = NoWeight(ld)
+def stager():
+    if "--event-crops" not in sys.argv: return BatchStager(ld, 16, 512, 512, tag="train", augment=augment, weights=weights, detector=detector)
+    from ubresnet_amd import crops                              # --event-crops: 16 crops of 512 x 512 per batch cut on the device from eight pinned synthetic 3 x 1008 x 3456 events (EventCropStager; --augment does not apply, flips come from the cropper)
+    events = [crops.LabelledEvent(*(torch.from_numpy(a).pin_memory() for a in synthetic.make_labelled_event(3, 1008, 3456, 5000 + 10 * i))) for i in range(8)]
+    return crops.EventCropStager(events, crops.EventCropper(crop=(512, 512), per_event=16, min_lit=2000, tries=8, flip_rows=True, flip_cols=True, seed=1), weights=weights, detector=detector)
 t0 = time.perf_counter()
-with BatchStager(ld, 16, 512, 512, tag="train", augment=augment, weights=weights, detector=detector) as st:
+with stager() as st:
     for ep in range(6):
         loss, acc = epoch.train(st, model, crit, opt, 50 * accumulate, iiter=ep, print_freq=25 * accumulate, accumulate=accumulate, stats_guard=sg, ema=ema)
-        print(ep, round(loss, 4), "mem GB %.2f" % (torch.cuda.max_memory_allocated() / 2**30), "acc[1] %.1f" % acc, st.stage_times(), flush=True)
+        print(ep, round(loss, 4), "mem GB %.2f" % (torch.cuda.max_memory_allocated() / 2**30), "acc[1] %.1f" % acc, st.stage_times() if hasattr(st, "stage_times") else "", flush=True)
 torch.cuda.synchronize(); print("%d steps (%d batches) in %.1f s; finite params: %s" % (opt.steps, 300 * accumulate, time.perf_counter() - t0, all(torch.isfinite(p).all().item() for p in model.parameters())))
 if ema is not None: print("ema updates %d held %d; finite average: %s" % (ema.updates, ema.held, bool(torch.isfinite(ema.shadow).all())))
 if hasattr(crit, "gamma"): print("criterion: gamma %g, normalize %s, last batch %s" % (crit.gamma, crit.normalize, crit.read()))

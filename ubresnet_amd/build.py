@@ -62,6 +62,9 @@ ADDONS = {
                  ["ubr_sat.h", os.path.join("..", "..", "include", "ubresnet_blend.h")], "_blend"),
     "sparse": Lib(os.path.join(HERE, "libubresnet_sparse.so"), [os.path.join("extra", "ubr_sparse.hip")],
                   ["ubr_sat.h", "ubr_sparse_plan.h", os.path.join("..", "..", "include", "ubresnet_sparse.h")], "_sparse"),
+    "crop": Lib(os.path.join(HERE, "libubresnet_crop.so"), [os.path.join("extra", "ubr_crop.hip")],
+                ["ubr_sat.h", "ubr_crop_rule.h", "ubr_det_rule.h", os.path.join("..", "..", "include", "ubresnet_crop.h"),
+                 os.path.join("..", "..", "include", "ubresnet_det.h")], "_crop"),
 }
 
 

@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["make_crop", "make_batch", "SyntheticLArCVDataset"]
+__all__ = ["make_crop", "make_batch", "make_labelled_event", "SyntheticLArCVDataset"]
 
 
 def make_crop(height: int, width: int, seed: int, labelled_weight: float = 10.0):
@@ -84,6 +84,18 @@ def make_batch(batchsize: int, height: int, width: int, seed0: int = 1000, plane
             adc[i, p] = a
         lab[i], wgt[i] = l, w
     return adc, lab, wgt
+
+
+def make_labelled_event(planes: int, rows: int, cols: int, seed: int):
+    """One whole labelled view -> (image float32 [planes,rows,cols], label uint8 [planes,rows,cols]): plane p is
+    ``make_crop(rows, cols, seed + p)`` at the view's size, so the tracks and showers are those of the crops and their number of
+    hits grows with the area.  What ``ubresnet_amd.crops.EventCropper`` cuts training crops from."""
+    image = np.zeros((planes, rows, cols), dtype=np.float32)
+    label = np.zeros((planes, rows, cols), dtype=np.uint8)
+    for p in range(planes):
+        a, l, _ = make_crop(rows, cols, seed + p)
+        image[p], label[p] = a, l.astype(np.uint8)
+    return image, label
 
 
 class SyntheticLArCVDataset(object):
