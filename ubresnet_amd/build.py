@@ -65,6 +65,8 @@ ADDONS = {
     "crop": Lib(os.path.join(HERE, "libubresnet_crop.so"), [os.path.join("extra", "ubr_crop.hip")],
                 ["ubr_sat.h", "ubr_crop_rule.h", "ubr_det_rule.h", os.path.join("..", "..", "include", "ubresnet_crop.h"),
                  os.path.join("..", "..", "include", "ubresnet_det.h")], "_crop"),
+    "calib": Lib(os.path.join(HERE, "libubresnet_calib.so"), [os.path.join("extra", "ubr_calib.hip")],
+                 ["ubr_sat.h", "ubr_calib_plan.h", os.path.join("..", "..", "include", "ubresnet_calib.h")], "_calib"),
 }
 
 

@@ -34,6 +34,7 @@ from . import _lib as L
 from . import _post as PL
 from . import _blend as VL
 from . import _tta as TL
+from . import calibration as CB
 from . import sparse as SP
 
 
@@ -121,9 +122,21 @@ def save_checkpoint(state: dict, is_best: bool, p: int, filename: str = "checkpo
     return filename
 
 
-def _merged_views(model, x, flips, xin, merged):
+def _tempered(logp, scale):
+    """`logp` rescaled in place by `scale` (one ubf_apply launch; every image group 0 unless there is a temperature per image);
+    a model output that is a view of other storage is copied first"""
+    if scale is None:
+        return logp
+    if logp.dtype != torch.float32:
+        raise RuntimeError("segment_crops: temperature needs float32 log-probabilities (got %s)" % logp.dtype)
+    logp = logp.contiguous()
+    return scale.apply_(logp, [0] * logp.shape[0])
+
+
+def _merged_views(model, x, flips, xin, merged, scale=None):
     """the flip views of one batch: `x` [m,C,H,W] is written flipped into `xin` (the identity view is read where it lies), the
-    model runs on it and its float32 log-probabilities are merged, un-flipped, into `merged` [m,classes,H,W]"""
+    model runs on it and its float32 log-probabilities (rescaled by `scale`, if any) are merged, un-flipped, into `merged`
+    [m,classes,H,W]"""
     m, cin, H, W = x.shape
     K = len(flips)
     for k, flip in enumerate(flips):
@@ -133,20 +146,27 @@ def _merged_views(model, x, flips, xin, merged):
         if logp.dtype != torch.float32 or tuple(logp.shape) != tuple(merged.shape):
             raise RuntimeError("segment_crops: the model must return float32 log-probabilities %s (got %s %s)"
                                % (tuple(merged.shape), logp.dtype, tuple(logp.shape)))
+        logp = _tempered(logp, scale)
         TL.merge_view(logp.data_ptr(), merged.data_ptr(), merged.shape[0] * merged.shape[1], H, W, flip, k, K, L.stream_ptr())
 
 
 @torch.no_grad()
 def segment_crops(model, adc: torch.Tensor, batch: int = 4, output: str = "scores", adc_threshold: Optional[float] = 10.0,
-                  fill_label: int = 255, tta=None):
+                  fill_label: int = 255, tta=None, temperature=None):
     """eval forward over pre-cropped images [n,C,H,W] in batches (deploy/run_ubresnet_precropped.py:115-182).
     output="products": Products of [n,H,W] / [n,H,W] / [n,classes] instead of the scores; every image is one whole-image tile
     of ubp_stitch_products and is lit where any of its channels is above `adc_threshold` (None: everywhere).
     tta: None / () or a tuple drawn from "rows", "cols", "both": every batch also runs flipped that way and the scores are the log
     of the mean probability over the views, the identity first (needs a CUDA float32 input; the lit test reads the unflipped
-    `adc`)."""
+    `adc`).
+    temperature: None, or a float, calibration.TemperatureScale or calibration.Calibration: the scores of every forward (every
+    flip view) become log_softmax(scores / T) by one ubf_apply launch before anything else reads them.  The crops carry no
+    plane, so a single temperature is needed (a per-plane scale is a ValueError)."""
     _check_output(output)
     flips = TL.parse_views(tta)
+    scale = CB.as_scale(temperature)
+    if scale is not None and len(scale) != 1:
+        raise ValueError("segment_crops: pre-cropped images carry no plane: temperature must be a single value (got %d)" % len(scale))
     model.eval()
     if flips:
         L.require_cuda(adc, "adc")
@@ -159,7 +179,7 @@ def segment_crops(model, adc: torch.Tensor, batch: int = 4, output: str = "score
         if output == "scores":
             out = torch.empty((n, nclass, H, W), dtype=torch.float32, device=adc.device)
             for i in range(0, n, batch):
-                _merged_views(model, adc[i:i + batch], flips, xin, out[i:i + batch])
+                _merged_views(model, adc[i:i + batch], flips, xin, out[i:i + batch], scale)
             return out
         prod = Products(torch.empty((n, H, W), dtype=torch.uint8, device=adc.device),
                         torch.empty((n, H, W), dtype=torch.float16, device=adc.device),
@@ -167,7 +187,7 @@ def segment_crops(model, adc: torch.Tensor, batch: int = 4, output: str = "score
         merged = torch.empty((min(batch, n), nclass, H, W), dtype=torch.float32, device=adc.device)
         for i in range(0, n, batch):
             nb = min(batch, n - i)
-            _merged_views(model, adc[i:i + nb], flips, xin, merged[:nb])
+            _merged_views(model, adc[i:i + nb], flips, xin, merged[:nb], scale)
             for j in range(0, nb, PL.MAX_TILES):
                 m = min(PL.MAX_TILES, nb - j)
                 tiles = [(i + j + q, 0, 0, 0, H, 0, W) for q in range(m)]
@@ -176,7 +196,7 @@ def segment_crops(model, adc: torch.Tensor, batch: int = 4, output: str = "score
     if output == "scores":
         outs = []
         for i in range(0, adc.shape[0], batch):
-            outs.append(model(adc[i:i + batch]))
+            outs.append(_tempered(model(adc[i:i + batch]), scale))
         return torch.cat(outs, 0)
     L.require_cuda(adc, "adc")
     if adc.dtype != torch.float32 or adc.dim() != 4:
@@ -191,6 +211,7 @@ def segment_crops(model, adc: torch.Tensor, batch: int = 4, output: str = "score
         logp = model(adc[i:i + batch]).contiguous()
         if logp.dtype != torch.float32:
             raise RuntimeError("segment_crops: the model must return float32 log-probabilities (got %s)" % logp.dtype)
+        logp = _tempered(logp, scale)
         for j in range(0, logp.shape[0], PL.MAX_TILES):
             m = min(PL.MAX_TILES, logp.shape[0] - j)
             tiles = [(i + j + q, 0, 0, 0, H, 0, W) for q in range(m)]
@@ -298,13 +319,21 @@ class WholeViewSegmenter:
     sparse.PixelList of the lit pixels in ascending pixel-index order (`capacity` entries; None: as many as there are pixels);
     the list's buffers are kept between calls too, so a call overwrites the list of the call before it.  Nothing is read back:
     PixelList.read() is the host synchronisation.  With a dense view and "scores" / "products" nothing here runs.
+
+    temperature=T: a float, a sequence with one value per plane, a calibration.TemperatureScale or a calibration.Calibration.
+    The scores of EVERY forward -- every chunk, every flip view under `tta` -- become log_softmax(scores / T) by one in-place
+    ubf_apply launch (include/ubresnet_calib.h) right after the replay, before ubt_merge_view, ubv_blend_tiles, the stitch or the
+    event products read them; so the merge and the blend average calibrated probabilities.  The inverse temperature of every
+    tile comes from the tile's plane (stacked tiles: group 0) and is fixed at construction.  T is that of the single-view
+    network: fit it on a segmenter with tta, blend and temperature off.  None: not one launch differs from today.
     """
 
     def __init__(self, model, rows: int, cols: int, planes: int = 3, tile=(512, 832), batch: int = 10,
                  dtype: torch.dtype = torch.float16, use_graph: bool = True, output: str = "scores",
                  adc_threshold: Optional[float] = 10.0, fill_label: int = 255, tta=None, margin: int = 0, blend=None,
-                 capacity: Optional[int] = None):
+                 temperature=None, capacity: Optional[int] = None):
         _check_output(output, pixels=True)
+        self.scale = CB.as_scale(temperature)               # None: not one launch differs
         if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 1):
             raise ValueError("capacity must be None or an int >= 1 (got %r)" % (capacity,))
         if capacity is not None and output != "pixels":
@@ -334,6 +363,13 @@ class WholeViewSegmenter:
         if batch * cin > L.MAX_TILES:
             raise ValueError("batch * planes must be <= %d tile descriptors (UBR_MAX_TILES)" % L.MAX_TILES)
         self.nclass = model.conv11.out_channels
+        self._tile_groups = None                            # temperature: the group of every tile, in the order of self.tiles
+        self._chunk_betas = {}                              # and per chunk start the device array of 1 / T, built on first use
+        if self.scale is not None:
+            if len(self.scale) not in (1, 1 if self.stacked else planes):
+                raise ValueError("WholeViewSegmenter: temperature must be one value or one per plane (%d), got %d; stacked tiles "
+                                 "are group 0" % (1 if self.stacked else planes, len(self.scale)))
+            self._tile_groups = [t[0] if len(self.scale) > 1 else 0 for t in self.tiles]
         if output in ("products", "pixels"):
             _check_cover(self.tiles, 1 if self.stacked else planes, rows, cols)
         self._graph = None
@@ -396,6 +432,16 @@ class WholeViewSegmenter:
                 with torch.cuda.graph(g):
                     self._static_out = self._forward_batch(self._static_in)
                 self._graph = g
+
+    def _temper(self, scores, i, n):
+        """ubf_apply in place on the first n tiles of `scores`, the chunk that starts at tile i"""
+        if scores.dtype != torch.float32 or not scores.is_contiguous():
+            raise RuntimeError("WholeViewSegmenter: temperature needs contiguous float32 scores (got %s)" % scores.dtype)
+        if i not in self._chunk_betas or self._chunk_betas[i].device != scores.device:
+            self._chunk_betas[i] = self.scale.device_betas(self._tile_groups[i:i + n], scores.device)
+        CB._calib.apply(scores.data_ptr(), scores.data_ptr(), self._chunk_betas[i].data_ptr(), n, self.nclass, self.th, self.tw,
+                        L.stream_ptr())
+        return scores
 
     @torch.no_grad()
     def _scatter(self, event):
@@ -466,6 +512,8 @@ class WholeViewSegmenter:
                     scores = self._static_out
                 else:
                     scores = self._forward_batch(self._static_in)
+                if self.scale is not None:                   # in place on the scores of this forward, before anything reads them
+                    scores = self._temper(scores, i, n)
                 if flip is not None:
                     TL.merge_view(scores.data_ptr(), self._tta_merged.data_ptr(), n * self.nclass, self.th, self.tw, flip, k,
                                   len(self._flips), L.stream_ptr())

@@ -228,10 +228,13 @@ def train(stager, model, criterion, optimizer, nbatches, iiter=0, nclasses=3, pr
     return rec.losses.avg, rec.acc_list[1].avg
 
 
-def validate(stager, model, criterion, nbatches, iiter=0, nclasses=3, print_freq=10, log=print, track_shower=False, ema=None):
+def validate(stager, model, criterion, nbatches, iiter=0, nclasses=3, print_freq=10, log=print, track_shower=False,
+             calibration=None, ema=None):
     """`nbatches` batches of `stager.next()` through the model in eval mode, without gradients (the folded inference schedule);
     -> float(acc_list[-1].avg), the average total accuracy in percent (:471), with `track_shower` -> (that, track/shower avg);
-    `ema`: a ParamEMA whose averaged weights the model computes with for the length of the loop"""
+    `ema`: a ParamEMA whose averaged weights the model computes with for the length of the loop;
+    `calibration`: a calibration.TemperatureFit that takes every batch's (pred, label, adc) -- one launch pair per batch on the
+    current stream, nothing read back; the caller reads it after the loop.  The return value and the log lines do not change"""
     batch_time, load_data = AverageMeter(), AverageMeter()
     rec = _EpochRecord(nbatches, nclasses, track_shower)
 
@@ -247,6 +250,8 @@ def validate(stager, model, criterion, nbatches, iiter=0, nclasses=3, print_freq
             # compute output
             pred_t = model.forward(adc_t)
             loss_t = criterion.forward(pred_t, label_t, weight_t)
+            if calibration is not None:
+                calibration.add(pred_t, label_t, adc_t)
 
             rec.put(i, loss_t, pred_t, label_t)
             batch_time.update(time.time() - batchstart)
