@@ -75,6 +75,24 @@ def _stitch_products(logp, nclass, th, tw, tiles, adc, vplanes, adc_threshold, f
                                           fill_label, P, rows, cols, L.stream_ptr()), "stitch_products")
 
 
+def _new_products(P, nclass, rows, cols, device, kept=None):
+    """the Products of a [P,rows,cols] image: label / confidence uninitialised (every pixel lies in one keep window: _check_cover;
+    `kept`: a (label, confidence) pair that is reused instead), counts zero"""
+    label, confidence = kept or (torch.empty((P, rows, cols), dtype=torch.uint8, device=device),
+                                 torch.empty((P, rows, cols), dtype=torch.float16, device=device))
+    return Products(label, confidence, torch.zeros((P, nclass), dtype=torch.int64, device=device))
+
+
+def _image_products(logp, first, adc, vplanes, adc_threshold, fill_label, prod: Products):
+    """images as whole-image tiles: `logp` [m,classes,H,W] are the images `first` .. `first` + m - 1 of `prod`, PL.MAX_TILES of
+    them per ubp_stitch_products launch"""
+    m, nclass, H, W = logp.shape
+    for j in range(0, m, PL.MAX_TILES):
+        tiles = [(first + q, 0, 0, 0, H, 0, W) for q in range(j, min(j + PL.MAX_TILES, m))]
+        _stitch_products(logp[j:j + len(tiles)], nclass, H, W, tiles, adc, vplanes, adc_threshold, fill_label, prod,
+                         prod.label.shape[0], H, W)
+
+
 def load_model(checkpointfile: Optional[str], device, num_classes: int = 4, inplanes: int = 16, input_channels: int = 1,
                map_location=None, state_dict=None, arch: str = "uresnet", ema: bool = False):
     """UResNet (arch="uresnet") or ASPP_ResNet (arch="aspp") for deployment (deploy/ubresnet_funcs.py:41-68).
@@ -150,6 +168,20 @@ def _merged_views(model, x, flips, xin, merged, scale=None):
         TL.merge_view(logp.data_ptr(), merged.data_ptr(), merged.shape[0] * merged.shape[1], H, W, flip, k, K, L.stream_ptr())
 
 
+def _batch_logp(model, x, flips, xin, merged, scale, for_products):
+    """the log-probabilities of one batch `x` [m,C,H,W], rescaled by `scale`, if any: with `flips`, those of the views merged into
+    `merged`; else what the model returns -- contiguous float32 `for_products`, which the products kernel reads"""
+    if flips:
+        _merged_views(model, x, flips, xin, merged, scale)
+        return merged
+    logp = model(x)
+    if for_products:
+        logp = logp.contiguous()
+        if logp.dtype != torch.float32:
+            raise RuntimeError("segment_crops: the model must return float32 log-probabilities (got %s)" % logp.dtype)
+    return _tempered(logp, scale)
+
+
 @torch.no_grad()
 def segment_crops(model, adc: torch.Tensor, batch: int = 4, output: str = "scores", adc_threshold: Optional[float] = 10.0,
                   fill_label: int = 255, tta=None, temperature=None):
@@ -168,66 +200,36 @@ def segment_crops(model, adc: torch.Tensor, batch: int = 4, output: str = "score
     if scale is not None and len(scale) != 1:
         raise ValueError("segment_crops: pre-cropped images carry no plane: temperature must be a single value (got %d)" % len(scale))
     model.eval()
-    if flips:
+    products = output == "products"
+    cin = xin = scores = prod = None
+    if flips or products:                       # the plain scores path takes whatever the model takes
         L.require_cuda(adc, "adc")
         if adc.dtype != torch.float32 or adc.dim() != 4:
             raise RuntimeError("segment_crops: expected float32 [n,C,H,W], got %s %s" % (adc.dtype, tuple(adc.shape)))
         adc = adc.contiguous()
         n, cin, H, W = adc.shape
         nclass = model.conv11.out_channels
-        xin = torch.empty((min(batch, n), cin, H, W), dtype=torch.float32, device=adc.device)
-        if output == "scores":
-            out = torch.empty((n, nclass, H, W), dtype=torch.float32, device=adc.device)
-            for i in range(0, n, batch):
-                _merged_views(model, adc[i:i + batch], flips, xin, out[i:i + batch], scale)
-            return out
-        prod = Products(torch.empty((n, H, W), dtype=torch.uint8, device=adc.device),
-                        torch.empty((n, H, W), dtype=torch.float16, device=adc.device),
-                        torch.zeros((n, nclass), dtype=torch.int64, device=adc.device))
-        merged = torch.empty((min(batch, n), nclass, H, W), dtype=torch.float32, device=adc.device)
-        for i in range(0, n, batch):
-            nb = min(batch, n - i)
-            _merged_views(model, adc[i:i + nb], flips, xin, merged[:nb], scale)
-            for j in range(0, nb, PL.MAX_TILES):
-                m = min(PL.MAX_TILES, nb - j)
-                tiles = [(i + j + q, 0, 0, 0, H, 0, W) for q in range(m)]
-                _stitch_products(merged[j:j + m], nclass, H, W, tiles, adc, cin, adc_threshold, fill_label, prod, n, H, W)
-        return prod
-    if output == "scores":
-        outs = []
-        for i in range(0, adc.shape[0], batch):
-            outs.append(_tempered(model(adc[i:i + batch]), scale))
-        return torch.cat(outs, 0)
-    L.require_cuda(adc, "adc")
-    if adc.dtype != torch.float32 or adc.dim() != 4:
-        raise RuntimeError("segment_crops: expected float32 [n,C,H,W], got %s %s" % (adc.dtype, tuple(adc.shape)))
-    adc = adc.contiguous()
-    n, cin, H, W = adc.shape
-    nclass = model.conv11.out_channels
-    prod = Products(torch.empty((n, H, W), dtype=torch.uint8, device=adc.device),
-                    torch.empty((n, H, W), dtype=torch.float16, device=adc.device),
-                    torch.zeros((n, nclass), dtype=torch.int64, device=adc.device))
+        if flips:                               # the views merge into the scores themselves, or into one batch of them
+            xin = torch.empty((min(batch, n), cin, H, W), dtype=torch.float32, device=adc.device)
+            scores = torch.empty((min(batch, n) if products else n, nclass, H, W), dtype=torch.float32, device=adc.device)
+        if products:
+            prod = _new_products(n, nclass, H, W, adc.device)
+    n, outs = adc.shape[0], []
     for i in range(0, n, batch):
-        logp = model(adc[i:i + batch]).contiguous()
-        if logp.dtype != torch.float32:
-            raise RuntimeError("segment_crops: the model must return float32 log-probabilities (got %s)" % logp.dtype)
-        logp = _tempered(logp, scale)
-        for j in range(0, logp.shape[0], PL.MAX_TILES):
-            m = min(PL.MAX_TILES, logp.shape[0] - j)
-            tiles = [(i + j + q, 0, 0, 0, H, 0, W) for q in range(m)]
-            _stitch_products(logp[j:j + m], nclass, H, W, tiles, adc, cin, adc_threshold, fill_label, prod, n, H, W)
-    return prod
+        x = adc[i:i + batch]
+        merged = None if not flips else scores[:x.shape[0]] if products else scores[i:i + batch]
+        logp = _batch_logp(model, x, flips, xin, merged, scale, products)
+        if products:
+            _image_products(logp, i, adc, cin, adc_threshold, fill_label, prod)
+        else:
+            outs.append(logp)
+    return prod if products else scores if flips else torch.cat(outs, 0)
 
 
 def regular_tiling(rows: int, cols: int, th: int = 512, tw: int = 832) -> Tuple[List[int], List[int]]:
-    """row/col origins of the fewest tiles covering rows x cols with the overlap spread evenly"""
-    def origins(n, t):
-        if n <= t:
-            return [0]
-        k = -(-n // t)                       # number of tiles
-        step = (n - t) / float(k - 1)
-        return sorted(set(int(round(i * step)) for i in range(k)))
-    return origins(rows, th), origins(cols, tw)
+    """row/col origins of the fewest tiles covering rows x cols with the overlap spread evenly: margin_tiling without a margin
+    (for n > t, ceil((n - t) / t) + 1 = ceil(n / t) tiles)"""
+    return margin_tiling(rows, cols, th, tw, margin=0)
 
 
 def margin_tiling(rows: int, cols: int, th: int = 512, tw: int = 832, margin: int = 0) -> Tuple[List[int], List[int]]:
@@ -249,11 +251,11 @@ def margin_tiling(rows: int, cols: int, th: int = 512, tw: int = 832, margin: in
 
 
 def view_tiles(rows: int, cols: int, planes: int, th: int, tw: int, stacked: bool, margin: int = 0):
-    """tile descriptors {plane, row0, col0, keep_r0, keep_r1, keep_c0, keep_c1} (ubr_crop_tiles / ubr_stitch_tiles) of the
-    regular tiling, or of margin_tiling with `margin` > 0.  Per plane: one descriptor per (plane, row origin, column origin).
+    """tile descriptors {plane, row0, col0, keep_r0, keep_r1, keep_c0, keep_c1} (ubr_crop_tiles / ubr_stitch_tiles) of
+    margin_tiling (margin 0: the regular tiling).  Per plane: one descriptor per (plane, row origin, column origin).
     Stacked (a model that takes the planes as channels): one descriptor per (row origin, column origin) with plane 0 --
     stacked_crop_desc() expands it for the crop, the stitch takes it as it is with P = 1."""
-    ro, co = margin_tiling(rows, cols, th, tw, margin) if margin else regular_tiling(rows, cols, th, tw)
+    ro, co = margin_tiling(rows, cols, th, tw, margin)
     rk, ck = _keep_windows(ro, th, rows), _keep_windows(co, tw, cols)
     tiles = []
     for p in range(1 if stacked else planes):
@@ -286,46 +288,48 @@ class WholeViewSegmenter:
                                  dtype=torch.float16)
         scores = seg(view)          # view [planes,1,rows,cols] float32 on the GPU -> [planes,C,rows,cols]
 
-    With output="products" the call returns Products instead -- label and confidence [planes,rows,cols], counts [planes,C] --
-    and no [planes,C,rows,cols] buffer exists: one ubp_stitch_products launch per chunk of tiles takes the place of the stitch,
-    with the input view as the ADC of the lit test (`adc_threshold`, None = every pixel lit; unlit pixels get `fill_label`).
-
     A model whose first conv takes one channel (UResNet, deploy/run_ubresnet_wholeview.py) sees every plane's tiles on their
     own.  A model that takes `planes` channels (ASPP_ResNet, the three planes stacked as channels) sees one stacked tile per
-    position, and the result is one class-score map per event, [C,rows,cols] (products: [rows,cols] and [C]; a pixel is lit if
-    any plane is).
+    position, and the result is one map per event: scores [C,rows,cols], products [rows,cols] and [C], a pixel lit if any plane
+    is.  Everything runs on the current stream and nothing is read back.  A call is five stages, each keyword acting in one:
 
-    tta=("rows", "cols", "both") or any part of it: flip test-time augmentation.  Every chunk of tiles is cropped once, runs
-    through the same captured graph once per view (the identity first, then the named flips in the order given) and the views'
-    log-probabilities are merged, un-flipped, into the log of their mean probability (include/ubresnet_tta.h) before the unchanged
-    stitch or event products.  None / (): off, today's path call for call.
+    1. Input (_input).  A float32 [planes,1,rows,cols] view on the device, or a sparse.SparseEvent (ubresnet_amd/sparse.py): the
+       list is copied to the device if it is on the host and scattered (ubz_scatter_view) into a view buffer kept between calls;
+       `seg.status` is the device word that counts the entries the scatter refused.  The forward of one batch of tiles is
+       captured into a hipGraph on the first call (use_graph=False: run eagerly) and again if the model's storage was replaced.
 
-    margin=m (0 <= 4 m <= the smaller tile side): the tiling of margin_tiling, whose overlaps are at least 2 m wide, so that no
-    kept pixel lies within m pixels of a tile edge inside the view (the networks zero-pad every conv there).  More tiles per
-    event; the crop, stitch and products kernels are the same.  blend="linear" or "hann": overlapping tiles vote instead of being
-    cut in the middle.  Along each axis a tile's weight is zero within `margin` of such an edge, rises over the next
-    ceil(t / 2) - m pixels (linearly, or as sin^2) to one, and the weights of the tiles covering a pixel are normalised to sum to
-    one; a tile's weight at a pixel is its row weight times its column weight.  The scores are the log of that weighted mean of
-    probabilities (include/ubresnet_blend.h: one ubv_blend_begin per call, one ubv_blend_tiles per chunk in place of the stitch,
-    after the merge of the views with `tta`); the log-weights are two tables built once, here.  output="products" with blend
-    needs the dense [planes,C,rows,cols] float32 buffer that plain products avoid: it is kept between calls, and one
-    ubp_stitch_products launch over the finished buffer, every plane one whole-view tile, makes the products.  With
-    margin=0, blend=None the path is today's, call for call.
+    2. Output buffers (_begin).  output="scores": a fresh [planes,C,rows,cols] float32.  output="products": fresh Products --
+       label and confidence [planes,rows,cols], counts [planes,C] -- and no dense score buffer.  output="pixels": the same
+       products path into dense label / confidence buffers kept between calls.  blend: the dense float32 scores the tiles vote
+       into, set to -inf (ubv_blend_begin); fresh for "scores", kept between calls for "products" and "pixels", which then do
+       need the dense buffer that plain products avoid.
 
-    Sparse I/O (ubresnet_amd/sparse.py, include/ubresnet_sparse.h).  The call also takes a sparse.SparseEvent in place of the
-    dense view, for every `output`: the list is copied to the device if it is on the host and scattered into a view buffer that
-    is kept between calls; `seg.status` is the device word that counts the entries the scatter refused.  output="pixels" runs the
-    unchanged products path into dense buffers kept between calls and compacts them, on the same stream, into a
-    sparse.PixelList of the lit pixels in ascending pixel-index order (`capacity` entries; None: as many as there are pixels);
-    the list's buffers are kept between calls too, so a call overwrites the list of the call before it.  Nothing is read back:
-    PixelList.read() is the host synchronisation.  With a dense view and "scores" / "products" nothing here runs.
+    3. Chunks of `batch` tiles (_chunk_scores).  The tiling is fixed at construction.  margin=m (0 <= 4 m <= the smaller tile
+       side) makes it that of margin_tiling, whose overlaps are at least 2 m wide, so that no kept pixel lies within m pixels of a
+       tile edge inside the view (the networks zero-pad every conv there): more tiles per event, the same kernels.  A chunk is
+       cropped once (ubr_crop_tiles) and runs through the forward once per view.  tta=("rows", "cols", "both") or any part of it:
+       the views are the identity, then the named flips in the order given; the chunk is flipped on its way into the forward's
+       input (ubt_flip_planes) and the views' log-probabilities are merged, un-flipped, into the log of their mean probability
+       (ubt_merge_view, include/ubresnet_tta.h).  temperature=T (a float, a sequence with one value per plane, a
+       calibration.TemperatureScale or a calibration.Calibration): the scores of every forward -- every chunk, every view --
+       become log_softmax(scores / T) by one in-place ubf_apply launch (include/ubresnet_calib.h) before anything else reads
+       them, so the merge and the blend average calibrated probabilities.  The inverse temperature of a tile is that of its plane
+       (stacked tiles: group 0).  T is that of the single-view network: fit it with tta, blend and temperature off.
 
-    temperature=T: a float, a sequence with one value per plane, a calibration.TemperatureScale or a calibration.Calibration.
-    The scores of EVERY forward -- every chunk, every flip view under `tta` -- become log_softmax(scores / T) by one in-place
-    ubf_apply launch (include/ubresnet_calib.h) right after the replay, before ubt_merge_view, ubv_blend_tiles, the stitch or the
-    event products read them; so the merge and the blend average calibrated probabilities.  The inverse temperature of every
-    tile comes from the tile's plane (stacked tiles: group 0) and is fixed at construction.  T is that of the single-view
-    network: fit it on a segmenter with tta, blend and temperature off.  None: not one launch differs from today.
+    4. Sink (_emit), one launch per chunk.  blend="linear" or "hann": ubv_blend_tiles (include/ubresnet_blend.h) -- overlapping
+       tiles vote instead of being cut in the middle.  Along each axis a tile's weight is zero within `margin` of a tile edge
+       inside the view, rises over the next ceil(t / 2) - m pixels (linearly, or as sin^2) to one, and the weights of the tiles
+       covering a pixel are normalised to sum to one; a tile's weight at a pixel is its row weight times its column weight, and
+       the scores are the log of that weighted mean of probabilities.  The log-weights are two tables built at construction.
+       Else "products" / "pixels": ubp_stitch_products writes class, confidence and counts of the chunk's keep windows, with the
+       input view as the ADC of the lit test (`adc_threshold`, None = every pixel lit; unlit pixels get `fill_label`).  Else:
+       ubr_stitch_tiles copies the keep windows into the scores.
+
+    5. Finish (_finish).  Products with blend: ubp_stitch_products over the finished dense buffer, every plane one whole-view
+       tile.  "pixels": the dense products are compacted (ubz_compact, include/ubresnet_sparse.h) into a sparse.PixelList of the
+       lit pixels in ascending pixel-index order (`capacity` entries; None: as many as there are pixels); the list's buffers are
+       kept between calls, so a call overwrites the list of the call before it, and PixelList.read() is the host
+       synchronisation.  Stacked results lose their leading axis of one.
     """
 
     def __init__(self, model, rows: int, cols: int, planes: int = 3, tile=(512, 832), batch: int = 10,
@@ -333,19 +337,16 @@ class WholeViewSegmenter:
                  adc_threshold: Optional[float] = 10.0, fill_label: int = 255, tta=None, margin: int = 0, blend=None,
                  temperature=None, capacity: Optional[int] = None):
         _check_output(output, pixels=True)
-        self.scale = CB.as_scale(temperature)               # None: not one launch differs
+        self.scale = CB.as_scale(temperature)
         if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 1):
             raise ValueError("capacity must be None or an int >= 1 (got %r)" % (capacity,))
         if capacity is not None and output != "pixels":
             raise ValueError("capacity is the length of the pixel list: it needs output='pixels'")
         self.capacity = capacity
-        self.status = None                                  # sparse input: refused entries, counted on the device (int64 [1])
-        self._view_buf = None                               # sparse input: the dense view, kept between calls
-        self._pix_dense = None                              # output="pixels": the dense label / confidence, kept between calls
-        self._compactor = None                              # output="pixels": the list's buffers and scratch, kept between calls
         self._flips = TL.parse_views(tta)                   # () or (0, flip mask of every named view)
         self.blend = VL.check_kind(blend)
         self.output, self.adc_threshold, self.fill_label = output, adc_threshold, fill_label
+        self._products = output in ("products", "pixels")
         self.model, self.rows, self.cols, self.planes = model, rows, cols, planes
         self.th, self.tw = tile
         if self.th % 32 or self.tw % 32:
@@ -357,8 +358,10 @@ class WholeViewSegmenter:
                              "are supported" % (cin, planes))
         self.stacked = cin > 1
         self.cin = cin
+        self._oplanes = 1 if self.stacked else planes       # planes of the result
+        self._vplanes = planes if self.stacked else 1       # view planes the lit test reads per plane of the result
         self.margin = margin
-        self._origins = margin_tiling(rows, cols, self.th, self.tw, margin)             # refuses a bad margin; 0: regular_tiling
+        self._origins = margin_tiling(rows, cols, self.th, self.tw, margin)             # refuses a bad margin
         self.tiles = view_tiles(rows, cols, planes, self.th, self.tw, self.stacked, margin)     # (plane, r0, c0, kr0, kr1, kc0, kc1)
         if batch * cin > L.MAX_TILES:
             raise ValueError("batch * planes must be <= %d tile descriptors (UBR_MAX_TILES)" % L.MAX_TILES)
@@ -366,20 +369,12 @@ class WholeViewSegmenter:
         self._tile_groups = None                            # temperature: the group of every tile, in the order of self.tiles
         self._chunk_betas = {}                              # and per chunk start the device array of 1 / T, built on first use
         if self.scale is not None:
-            if len(self.scale) not in (1, 1 if self.stacked else planes):
+            if len(self.scale) not in (1, self._oplanes):
                 raise ValueError("WholeViewSegmenter: temperature must be one value or one per plane (%d), got %d; stacked tiles "
-                                 "are group 0" % (1 if self.stacked else planes, len(self.scale)))
+                                 "are group 0" % (self._oplanes, len(self.scale)))
             self._tile_groups = [t[0] if len(self.scale) > 1 else 0 for t in self.tiles]
-        if output in ("products", "pixels"):
-            _check_cover(self.tiles, 1 if self.stacked else planes, rows, cols)
-        self._graph = None
-        self._static_in = None
-        self._static_out = None
-        self._captured_sig = None
-        self._tta_side = None                               # the cropped chunk, unflipped; lives and dies with _static_in
-        self._tta_merged = None                             # the running merge of the views' log-probabilities
-        self._blend_lw = None                               # (lw_rows [ntiles][th], lw_cols [ntiles][tw]) on the device
-        self._blend_out = None                              # products with blend: the dense scores, kept between calls
+        if self._products:
+            _check_cover(self.tiles, self._oplanes, rows, cols)
         if self.blend is not None:
             if batch > VL.MAX_TILES:
                 raise ValueError("batch must be <= %d tile descriptors (UBV_MAX_TILES) with blend" % VL.MAX_TILES)
@@ -387,16 +382,21 @@ class WholeViewSegmenter:
             lr = VL.axis_log_weights(ro, self.th, rows, margin, self.blend)
             lc = VL.axis_log_weights(co, self.tw, cols, margin, self.blend)
             # in the order of self.tiles: planes x row origins x column origins; float64, rounded once when they go to the device
-            reps = 1 if self.stacked else planes
-            self._blend_host = (torch.tensor([r for _ in range(reps) for r in lr for _ in co], dtype=torch.float64),
-                                torch.tensor([c for _ in range(reps) for _ in ro for c in lc], dtype=torch.float64))
+            self._blend_host = (torch.tensor([r for _ in range(self._oplanes) for r in lr for _ in co], dtype=torch.float64),
+                                torch.tensor([c for _ in range(self._oplanes) for _ in ro for c in lc], dtype=torch.float64))
+        # Device state, built when its feature first runs and None until then.
+        # The forward of one batch of tiles (_ensure_graph); dropped together when the model's storage is replaced:
+        self._graph = self._static_in = self._static_out = self._captured_sig = None
+        self._tta_side = self._tta_merged = None            # tta: the cropped chunk, unflipped; the running merge of the views
+        # Kept between calls:
+        self._blend_lw = None                               # blend: (lw_rows [ntiles][th], lw_cols [ntiles][tw])
+        self._blend_out = None                              # blend with products: the dense scores
+        self._view_buf = self.status = None                 # sparse input: the dense view; the refused entries (int64 [1])
+        self._pix_dense = self._compactor = None            # "pixels": dense (label, confidence); the list's buffers and scratch
 
     @property
     def tiles_per_event(self):
         return len(self.tiles)
-
-    def _desc(self, tiles):
-        return _desc7(tiles)
 
     def _forward_batch(self, x):
         old = getattr(self.model, "compute_dtype", None)
@@ -443,7 +443,6 @@ class WholeViewSegmenter:
                         L.stream_ptr())
         return scores
 
-    @torch.no_grad()
     def _scatter(self, event):
         """a SparseEvent -> the dense view in the buffer kept between calls, on the model's device (or the list's own)"""
         if (event.planes, event.rows, event.cols) != (self.planes, self.rows, self.cols):
@@ -455,8 +454,8 @@ class WholeViewSegmenter:
             self.status = torch.zeros(1, dtype=torch.int64, device=device)
         return event.to_view(device, out=self._view_buf, status=self.status)
 
-    @torch.no_grad()
-    def __call__(self, view):
+    def _input(self, view):
+        """the contiguous float32 view on the device, the forward captured for that device"""
         if isinstance(view, SP.SparseEvent):
             view = self._scatter(view)
         L.require_cuda(view, "view")
@@ -465,80 +464,83 @@ class WholeViewSegmenter:
                                % (self.planes, self.rows, self.cols, view.dtype, tuple(view.shape)))
         view = view.contiguous()
         self._ensure_graph(view.device)
-        oplanes = 1 if self.stacked else self.planes
-        pixels = self.output == "pixels"
-        products = pixels or self.output == "products"
+        return view
+
+    def _begin(self, device):
+        """-> (out, blended): what the call fills, and the dense scores the tiles vote into (None without blend)"""
+        shape = (self._oplanes, self.nclass, self.rows, self.cols)
         blended = None
         if self.blend is not None:
-            if self._blend_lw is None or self._blend_lw[0].device != view.device:
-                self._blend_lw = tuple(t.to(torch.float32).to(view.device) for t in self._blend_host)
-            shape = (oplanes, self.nclass, self.rows, self.cols)
-            if not products:
-                blended = torch.empty(shape, dtype=torch.float32, device=view.device)
+            if self._blend_lw is None or self._blend_lw[0].device != device:
+                self._blend_lw = tuple(t.to(torch.float32).to(device) for t in self._blend_host)
+            if not self._products:
+                blended = torch.empty(shape, dtype=torch.float32, device=device)
             else:
-                if self._blend_out is None or self._blend_out.device != view.device:
-                    self._blend_out = torch.empty(shape, dtype=torch.float32, device=view.device)
+                if self._blend_out is None or self._blend_out.device != device:
+                    self._blend_out = torch.empty(shape, dtype=torch.float32, device=device)
                 blended = self._blend_out
             VL.blend_begin(blended.data_ptr(), blended.numel(), L.stream_ptr())
-        if pixels:                       # the dense products of the list: kept between calls, every pixel written by the tiling
-            if self._pix_dense is None or self._pix_dense[0].device != view.device:
-                self._pix_dense = (torch.empty((oplanes, self.rows, self.cols), dtype=torch.uint8, device=view.device),
-                                   torch.empty((oplanes, self.rows, self.cols), dtype=torch.float16, device=view.device))
-                self._compactor = SP.Compactor(oplanes, self.rows, self.cols, self.capacity, view.device)
-            out = Products(self._pix_dense[0], self._pix_dense[1],
-                           torch.zeros((oplanes, self.nclass), dtype=torch.int64, device=view.device))
-        elif products:                   # label / confidence uninitialised: the tiling covers the view
-            out = Products(torch.empty((oplanes, self.rows, self.cols), dtype=torch.uint8, device=view.device),
-                           torch.empty((oplanes, self.rows, self.cols), dtype=torch.float16, device=view.device),
-                           torch.zeros((oplanes, self.nclass), dtype=torch.int64, device=view.device))
-        elif blended is not None:
-            out = blended
+        if self.output == "pixels" and (self._pix_dense is None or self._pix_dense[0].device != device):
+            self._pix_dense = tuple(_new_products(self._oplanes, self.nclass, self.rows, self.cols, device)[:2])
+            self._compactor = SP.Compactor(self._oplanes, self.rows, self.cols, self.capacity, device)
+        if self._products:
+            return _new_products(self._oplanes, self.nclass, self.rows, self.cols, device, kept=self._pix_dense), blended
+        return (torch.empty(shape, dtype=torch.float32, device=device) if blended is None else blended), blended
+
+    def _chunk_scores(self, view, i, chunk):
+        """the log-probabilities of the tiles `chunk`, which start at tile i: crop, then per view flip -> forward -> temper ->
+        merge.  -> the buffer the sink reads (its first len(chunk) tiles)"""
+        n, st = len(chunk), L.stream_ptr()
+        cropped = self._tta_side if self._flips else self._static_in
+        L.check(L.lib().ubr_crop_tiles(view.data_ptr(), self.planes, self.rows, self.cols,
+                                       _desc7(stacked_crop_desc(chunk, self.planes) if self.stacked else chunk), n * self.cin,
+                                       self.th, self.tw, cropped.data_ptr(), st), "crop_tiles")
+        for k, flip in enumerate(self._flips or (None,)):
+            if flip is not None:                            # the identity view is a copy: flip 0
+                TL.flip_planes(cropped.data_ptr(), self._static_in.data_ptr(), n * self.cin, self.th, self.tw, flip, st)
+            if self._graph is not None:
+                self._graph.replay()
+                scores = self._static_out
+            else:
+                scores = self._forward_batch(self._static_in)
+            if self.scale is not None:                      # in place on the scores of this forward, before anything reads them
+                scores = self._temper(scores, i, n)
+            if flip is not None:
+                TL.merge_view(scores.data_ptr(), self._tta_merged.data_ptr(), n * self.nclass, self.th, self.tw, flip, k,
+                              len(self._flips), st)
+        return self._tta_merged if self._flips else scores
+
+    def _emit(self, scores, i, chunk, view, out, blended):
+        """the one launch that takes the chunk's scores into the result: blend, event products or stitch"""
+        dims = (self._oplanes, self.rows, self.cols)
+        if blended is not None:
+            VL.blend_tiles(scores.data_ptr(), self.nclass, self.th, self.tw, VL.desc3(chunk), len(chunk),
+                           self._blend_lw[0][i:].data_ptr(), self._blend_lw[1][i:].data_ptr(), blended.data_ptr(), *dims,
+                           L.stream_ptr())
+        elif self._products:
+            _stitch_products(scores, self.nclass, self.th, self.tw, chunk, view, self._vplanes, self.adc_threshold, self.fill_label,
+                             out, *dims)
         else:
-            out = torch.empty((oplanes, self.nclass, self.rows, self.cols), dtype=torch.float32, device=view.device)
-        lib = L.lib()
-        for i in range(0, len(self.tiles), self.batch):
-            chunk = self.tiles[i:i + self.batch]
-            n = len(chunk)
-            desc = self._desc(chunk)
-            cdesc = self._desc(stacked_crop_desc(chunk, self.planes)) if self.stacked else desc
-            st = L.stream_ptr()
-            L.check(lib.ubr_crop_tiles(view.data_ptr(), self.planes, self.rows, self.cols, cdesc, n * self.cin, self.th, self.tw,
-                                       (self._tta_side if self._flips else self._static_in).data_ptr(), st), "crop_tiles")
-            for k, flip in enumerate(self._flips or (None,)):
-                if flip is not None:
-                    TL.flip_planes(self._tta_side.data_ptr(), self._static_in.data_ptr(), n * self.cin, self.th, self.tw, flip, st)
-                if self._graph is not None:
-                    self._graph.replay()
-                    scores = self._static_out
-                else:
-                    scores = self._forward_batch(self._static_in)
-                if self.scale is not None:                   # in place on the scores of this forward, before anything reads them
-                    scores = self._temper(scores, i, n)
-                if flip is not None:
-                    TL.merge_view(scores.data_ptr(), self._tta_merged.data_ptr(), n * self.nclass, self.th, self.tw, flip, k,
-                                  len(self._flips), L.stream_ptr())
-            if self._flips:
-                scores = self._tta_merged
-            if blended is not None:
-                VL.blend_tiles(scores.data_ptr(), self.nclass, self.th, self.tw, VL.desc3(chunk), n,
-                               self._blend_lw[0][i:].data_ptr(), self._blend_lw[1][i:].data_ptr(), blended.data_ptr(), oplanes,
-                               self.rows, self.cols, L.stream_ptr())
-                continue
-            if products:
-                _stitch_products(scores, self.nclass, self.th, self.tw, chunk, view, self.planes if self.stacked else 1,
-                                 self.adc_threshold, self.fill_label, out, oplanes, self.rows, self.cols)
-                continue
-            L.check(lib.ubr_stitch_tiles(scores.data_ptr(), self.nclass, self.th, self.tw, desc, n, out.data_ptr(),
-                                         oplanes, self.rows, self.cols, L.stream_ptr()), "stitch_tiles")
-        if products and blended is not None:
-            for j in range(0, oplanes, PL.MAX_TILES):
-                whole = [(p, 0, 0, 0, self.rows, 0, self.cols) for p in range(j, min(j + PL.MAX_TILES, oplanes))]
-                _stitch_products(blended[j:j + len(whole)], self.nclass, self.rows, self.cols, whole, view,
-                                 self.planes if self.stacked else 1, self.adc_threshold, self.fill_label, out, oplanes, self.rows,
-                                 self.cols)
-        if pixels:
-            return self._compactor(out.label, out.confidence, out.counts[0] if self.stacked else out.counts, view,
-                                   self.planes if self.stacked else 1, self.adc_threshold, self.fill_label)
-        if products:
+            L.check(L.lib().ubr_stitch_tiles(scores.data_ptr(), self.nclass, self.th, self.tw, _desc7(chunk), len(chunk),
+                                             out.data_ptr(), *dims, L.stream_ptr()), "stitch_tiles")
+
+    def _finish(self, view, out, blended):
+        """what the call returns: the products of the blended scores, the pixel list of the products, stacked results unwrapped"""
+        if self._products and blended is not None:
+            _image_products(blended, 0, view, self._vplanes, self.adc_threshold, self.fill_label, out)
+        if self.output == "pixels":
+            return self._compactor(out.label, out.confidence, out.counts[0] if self.stacked else out.counts, view, self._vplanes,
+                                   self.adc_threshold, self.fill_label)
+        if self._products:
             return Products(*(t[0] for t in out)) if self.stacked else out
         return out[0] if self.stacked else out
+
+    @torch.no_grad()
+    def __call__(self, view):
+        view = self._input(view)
+        out, blended = self._begin(view.device)
+        for i in range(0, len(self.tiles), self.batch):
+            chunk = self.tiles[i:i + self.batch]
+            self._emit(self._chunk_scores(view, i, chunk), i, chunk, view, out, blended)
+        return self._finish(view, out, blended)
+
