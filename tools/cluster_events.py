@@ -1,0 +1,57 @@
+#!/usr/bin/env python3
+"""Cluster the event products of synthetic labelled events on the device and print the cluster table, largest first.
+
+    python tools/cluster_events.py [--events N] [--rows R] [--cols C] [--top K] [--min-pixels M] [--connectivity 4|8] [--by-class]
+
+Every event goes through WholeViewSegmenter(output="products") and an EventClusterer (ubresnet_amd/clusters.py); nothing leaves
+the device until Clusters.read(), which copies the count and that many table rows.  The model has seeded random weights, so the
+classes mean nothing here; `shower` is the share of class --shower-class among the cluster's pixels."""
+import argparse
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--events", type=int, default=2)
+    ap.add_argument("--rows", type=int, default=512)
+    ap.add_argument("--cols", type=int, default=832)
+    ap.add_argument("--planes", type=int, default=3)
+    ap.add_argument("--classes", type=int, default=3)
+    ap.add_argument("--shower-class", type=int, default=2)
+    ap.add_argument("--top", type=int, default=12)
+    ap.add_argument("--min-pixels", type=int, default=4)
+    ap.add_argument("--connectivity", type=int, default=8, choices=(4, 8))
+    ap.add_argument("--by-class", action="store_true")
+    ap.add_argument("--capacity", type=int, default=65536)
+    a = ap.parse_args()
+    import torch
+    from ubresnet_amd import clusters, deploy, synthetic
+    if not torch.cuda.is_available():
+        raise SystemExit("cluster_events: needs a ROCm device; the HIP path has no CPU fallback")
+    torch.manual_seed(7)
+    model = deploy.load_model(None, "cuda:0", num_classes=a.classes)
+    seg = deploy.WholeViewSegmenter(model, rows=a.rows, cols=a.cols, planes=a.planes, tile=(min(512, a.rows), min(832, a.cols)), batch=3,
+                                    dtype=torch.float16, output="products")
+    cl = clusters.EventClusterer(a.planes, a.rows, a.cols, a.classes, a.connectivity, a.by_class, 255, a.capacity, "cuda:0")
+    for e in range(a.events):
+        image, _ = synthetic.make_labelled_event(a.planes, a.rows, a.cols, 1000 + 10 * e)
+        found = cl(seg(torch.from_numpy(image[:, None].copy()).cuda()))
+        tab = found.read(min_pixels=a.min_pixels)
+        order = torch.argsort(tab.pixels, descending=True)[:a.top]
+        frac, mean = tab.fractions(), tab.mean_confidence()
+        print("event %d: %d clusters, %d of at least %d pixels; foreign labels so far %d"
+              % (e, tab.total, len(tab), a.min_pixels, int(found.status.item())))
+        print("  plane  pixels  rows        cols        shower  mean confidence")
+        for i in order.tolist():
+            r0, r1, c0, c1 = tab.bbox[i].tolist()
+            print("  %5d  %6d  %4d..%-4d  %4d..%-4d  %6.3f  %.4f" % (int(tab.plane[i]), int(tab.pixels[i]), r0, r1, c0, c1,
+                                                                  float(frac[i, a.shower_class]), float(mean[i])))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

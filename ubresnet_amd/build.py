@@ -67,6 +67,8 @@ ADDONS = {
                  os.path.join("..", "..", "include", "ubresnet_det.h")], "_crop"),
     "calib": Lib(os.path.join(HERE, "libubresnet_calib.so"), [os.path.join("extra", "ubr_calib.hip")],
                  ["ubr_sat.h", "ubr_calib_plan.h", os.path.join("..", "..", "include", "ubresnet_calib.h")], "_calib"),
+    "cluster": Lib(os.path.join(HERE, "libubresnet_cluster.so"), [os.path.join("extra", "ubr_cluster.hip")],
+                   ["ubr_sat.h", "ubr_cluster_plan.h", os.path.join("..", "..", "include", "ubresnet_cluster.h")], "_cluster"),
 }
 
 
