@@ -2,10 +2,13 @@
 """Cluster the event products of synthetic labelled events on the device and print the cluster table, largest first.
 
     python tools/cluster_events.py [--events N] [--rows R] [--cols C] [--top K] [--min-pixels M] [--connectivity 4|8] [--by-class]
+                                   [--moments] [--adc-scale S]
 
 Every event goes through WholeViewSegmenter(output="products") and an EventClusterer (ubresnet_amd/clusters.py); nothing leaves
 the device until Clusters.read(), which copies the count and that many table rows.  The model has seeded random weights, so the
-classes mean nothing here; `shower` is the share of class --shower-class among the cluster's pixels."""
+classes mean nothing here; `shower` is the share of class --shower-class among the cluster's pixels.  With --moments a
+ClusterMoments (ubresnet_amd/shapes.py) runs behind the clusterer and the table gains the cluster's charge (summed ADC), the share
+of the shower class in that charge, its length (2 sqrt 3 times the major extent: exact for a uniform line), width and linearity."""
 import argparse
 import os
 import sys
@@ -27,6 +30,8 @@ def main():
     ap.add_argument("--connectivity", type=int, default=8, choices=(4, 8))
     ap.add_argument("--by-class", action="store_true")
     ap.add_argument("--capacity", type=int, default=65536)
+    ap.add_argument("--moments", action="store_true")
+    ap.add_argument("--adc-scale", type=int, default=16)
     a = ap.parse_args()
     import torch
     from ubresnet_amd import clusters, deploy, synthetic
@@ -37,19 +42,32 @@ def main():
     seg = deploy.WholeViewSegmenter(model, rows=a.rows, cols=a.cols, planes=a.planes, tile=(min(512, a.rows), min(832, a.cols)), batch=3,
                                     dtype=torch.float16, output="products")
     cl = clusters.EventClusterer(a.planes, a.rows, a.cols, a.classes, a.connectivity, a.by_class, 255, a.capacity, "cuda:0")
+    cm = None
+    if a.moments:
+        from ubresnet_amd import shapes
+        cm = shapes.ClusterMoments(cl, adc_scale=a.adc_scale)
     for e in range(a.events):
         image, _ = synthetic.make_labelled_event(a.planes, a.rows, a.cols, 1000 + 10 * e)
-        found = cl(seg(torch.from_numpy(image[:, None].copy()).cuda()))
-        tab = found.read(min_pixels=a.min_pixels)
+        view = torch.from_numpy(image[:, None].copy()).cuda()
+        found = cl(seg(view))
+        shape = cm(found, view).read(min_pixels=a.min_pixels) if cm else None
+        tab = shape.clusters if cm else found.read(min_pixels=a.min_pixels)
         order = torch.argsort(tab.pixels, descending=True)[:a.top]
         frac, mean = tab.fractions(), tab.mean_confidence()
         print("event %d: %d clusters, %d of at least %d pixels; foreign labels so far %d"
               % (e, tab.total, len(tab), a.min_pixels, int(found.status.item())))
-        print("  plane  pixels  rows        cols        shower  mean confidence")
+        more = ""
+        if cm:
+            charge, qfrac, length, width, lin = shape.charge(), shape.charge_fractions(), shape.length(), shape.width(), shape.linearity()
+            more = "  %10s  %8s  %7s  %6s  %9s" % ("charge", "shower q", "length", "width", "linearity")
+        print("  plane  pixels  rows        cols        shower  mean confidence" + more)
         for i in order.tolist():
             r0, r1, c0, c1 = tab.bbox[i].tolist()
+            if cm:
+                more = "           %10.1f  %8.3f  %7.1f  %6.1f  %9.4f" % (float(charge[i]), float(qfrac[i, a.shower_class]), float(length[i]),
+                                                                           float(width[i]), float(lin[i]))
             print("  %5d  %6d  %4d..%-4d  %4d..%-4d  %6.3f  %.4f" % (int(tab.plane[i]), int(tab.pixels[i]), r0, r1, c0, c1,
-                                                                  float(frac[i, a.shower_class]), float(mean[i])))
+                                                                  float(frac[i, a.shower_class]), float(mean[i])) + more)
     return 0
 
 

@@ -69,6 +69,8 @@ ADDONS = {
                  ["ubr_sat.h", "ubr_calib_plan.h", os.path.join("..", "..", "include", "ubresnet_calib.h")], "_calib"),
     "cluster": Lib(os.path.join(HERE, "libubresnet_cluster.so"), [os.path.join("extra", "ubr_cluster.hip")],
                    ["ubr_sat.h", "ubr_cluster_plan.h", os.path.join("..", "..", "include", "ubresnet_cluster.h")], "_cluster"),
+    "moment": Lib(os.path.join(HERE, "libubresnet_moment.so"), [os.path.join("extra", "ubr_moment.hip")],
+                  ["ubr_sat.h", "ubr_moment_plan.h", os.path.join("..", "..", "include", "ubresnet_moment.h")], "_moment"),
 }
 
 

@@ -129,6 +129,7 @@ class EventClusterer:
         self.count = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.status = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.scratch = torch.empty(self.scratch_bytes // 4, dtype=torch.int32, device=self.device)
+        self.label = None                                           # the class map of the last call (shapes.ClusterMoments reads it)
 
     def _views(self, label, confidence):
         if confidence is None:
@@ -155,6 +156,7 @@ class EventClusterer:
         """label a deploy.Products, a sparse.PixelList or the uint8 label map (then `confidence` is the float16 map); launches on
         the current stream of the clusterer's device"""
         label, confidence = self._views(label, confidence)
+        self.label = label
         with torch.cuda.device(self.device):
             st = L.stream_ptr()
             IL.label(label.data_ptr(), self.num_classes, self.fill_label, self.connectivity, self.by_class, self.root.data_ptr(),
