@@ -1,9 +1,9 @@
 // The launch plan of libubresnet_cluster.so (ubresnet_amd/csrc/ubr_cluster_plan.h, plain C++ for a host compiler) as a
 // stand-alone program, so that tests/test_cpu_cluster.py can run it under the host sanitizers:
 //   cluster_host P rows cols [P rows cols ...]
-// For every image given, and for every image of 1 x n x 1 pixels with n from 1 to a few pixel blocks, it checks the plan and the
-// scratch layout, then runs the host restatement of count / scan / number over four root maps and holds the numbering against
-// brute force.  Then it runs the model of the kernels' union loop: random unions on random forests, with and without an
+// For every image given, and for every image of 1 x n x 1 pixels with n from 1 to a few pixel blocks, it checks the tiles of
+// the plan (its pixel blocks and scratch layout are tests/scan_host.cpp's), then runs the host restatement of count / scan /
+// number over four root maps and holds the numbering against brute force.  Then it runs the model of the kernels' union loop: random unions on random forests, with and without an
 // adversary that links roots between any two memory operations of the loop, and checks that every loop ends within its bound
 // and that the forest has exactly the components of the union graph, each rooted at its smallest member.  It prints one line per
 // image, `I P rows cols pixels tiles_y tiles_x tiles blocks scan_trips scratch_bytes`, then `G tile_h tile_w lanes border_lanes
@@ -26,16 +26,9 @@ static int check_image(int64_t P, int64_t rows, int64_t cols, bool print) {
   ubi::Plan p;
   if (!ubi::make_plan(P, rows, cols, &p)) return fail("make_plan refused", P, rows, cols, -1);
   const int64_t n = P * rows * cols;
-  if (p.pixels != n || p.blocks < 1 || (p.blocks - 1) * ubi::PIXEL_BLOCK >= n || p.blocks * ubi::PIXEL_BLOCK < n)
-    return fail("blocks do not tile the pixels", P, rows, cols, -1);
   if ((p.tiles_y - 1) * ubi::TILE_H >= rows || p.tiles_y * ubi::TILE_H < rows || (p.tiles_x - 1) * ubi::TILE_W >= cols ||
       p.tiles_x * ubi::TILE_W < cols || p.tiles != P * p.tiles_y * p.tiles_x || p.tiles > n || p.tiles > ubi::MAX_PIXELS)
     return fail("tiles do not tile the planes", P, rows, cols, -1);
-  if (p.scan_trips < 1 || (p.scan_trips - 1) * ubi::SCAN_WIDTH >= p.blocks || p.scan_trips * ubi::SCAN_WIDTH < p.blocks)
-    return fail("scan trips do not tile the blocks", P, rows, cols, -1);
-  if (p.scratch_words < p.blocks || p.scratch_words % ubi::SCAN_LANE_COUNTS || p.scratch_words - p.blocks >= ubi::SCAN_LANE_COUNTS ||
-      p.scratch_bytes != 4 * p.scratch_words)
-    return fail("scratch layout", P, rows, cols, -1);
   if (print)
     std::printf("I %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld\n", (long long)P, (long long)rows, (long long)cols, (long long)p.pixels,
                 (long long)p.tiles_y, (long long)p.tiles_x, (long long)p.tiles, (long long)p.blocks, (long long)p.scan_trips,

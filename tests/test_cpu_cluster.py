@@ -153,8 +153,12 @@ def test_library_stands_alone_and_exports_exactly_its_bindings_symbols():
     code = re.sub(r"//.*", "", src)
     assert "cooperative" not in code.lower() and "while (true)" not in code and "__threadfence" not in code
     assert code.count("is_lit(") == 5, "the lit test: defined once; the local pass, the border pass (twice) and the tally call it"
-    plan = open(os.path.join(B.CSRC, "ubr_cluster_plan.h")).read()
-    assert "hip" not in re.sub(r"//.*", "", plan).lower() and "#include <stdint.h>" in plan and "#include \"" not in plan
+    # the plan compiles without HIP: it reaches the shared scan plan and nothing else, and neither file names HIP outside comments
+    plan, shared = os.path.join(B.CSRC, "ubr_cluster_plan.h"), os.path.join(B.CSRC, "ubr_scan_plan.h")
+    assert _include_closure([plan]) == {os.path.realpath(shared)} and _include_closure([shared]) == set()
+    for f in (plan, shared):
+        assert "hip" not in re.sub(r"//.*", "", open(f).read()).lower(), f
+    assert re.findall(r"#\s*include\s*<([^>]+)>", open(plan).read() + open(shared).read()) == ["stdint.h"]
 
 
 def test_a_missing_library_is_a_runtime_error(monkeypatch):

@@ -2,8 +2,8 @@
 header is C99, header, binding, reference, plan and library agree on entry points and geometry; the compiled kernels are exactly
 those the GPU module's case table runs; the library stands alone and exports its binding's symbols; the ADDONS entry and a forced
 build; every argument refusal returns UBZ_EINVAL with a message before any HIP call; the launch plan and a host restatement of
-count / scan / write as a stand-alone program under the host sanitizers (tests/sparse_host.cpp); the refusals of the Python
-surface that need no device."""
+count / scan / write as a stand-alone program under the host sanitizers (tests/sparse_host.cpp), and the shared scan plan
+beneath it as another (tests/scan_host.cpp); the refusals of the Python surface that need no device."""
 import ctypes as C
 import importlib
 import importlib.util
@@ -166,8 +166,12 @@ def test_library_stands_alone_and_exports_exactly_its_bindings_symbols():
     code = re.sub(r"//.*", "", src)
     assert len(re.findall(r"\batomic\w*\(", code)) == 1 and "atomicAdd(status" in code, "the one atomic is the status word's"
     assert code.count("lit_mask(") == 3, "the predicate: defined once, called by the count pass and by the write pass"
-    plan = open(os.path.join(B.CSRC, "ubr_sparse_plan.h")).read()
-    assert "hip" not in re.sub(r"//.*", "", plan).lower() and "#include <stdint.h>" in plan
+    # the plan compiles without HIP: it reaches the shared scan plan and nothing else, and neither file names HIP outside comments
+    plan, shared = os.path.join(B.CSRC, "ubr_sparse_plan.h"), os.path.join(B.CSRC, "ubr_scan_plan.h")
+    assert _include_closure([plan]) == {os.path.realpath(shared)} and _include_closure([shared]) == set()
+    for f in (plan, shared):
+        assert "hip" not in re.sub(r"//.*", "", open(f).read()).lower(), f
+    assert re.findall(r"#\s*include\s*<([^>]+)>", open(plan).read() + open(shared).read()) == ["stdint.h"]
 
 
 def test_a_missing_library_is_a_runtime_error(monkeypatch):
@@ -398,6 +402,26 @@ def test_plan_as_a_program_under_the_host_sanitizers(tmp_path):
     by_image = {tuple(r[:3]): r for r in rows}
     assert by_image[R.IMG_S][4:6] == [R.S, 1] and by_image[R.IMG_SP1][4:6] == [R.S + 1, 2] and by_image[R.IMG_BP1][4] == 2 and by_image[R.IMG_B][4] == 1
     assert p.stdout.strip().split("\n")[-1].split() == ["G"] + [str(v) for v in (Z.LANES, Z.LANE_PIXELS, Z.PIXEL_BLOCK, Z.SCAN_WIDTH, Z.MAX_GRID)]
+
+
+def test_shared_scan_plan_as_a_program_under_the_host_sanitizers(tmp_path):
+    """tests/scan_host.cpp has its own main and includes ubr_scan_plan.h alone; built with -fsanitize=address,undefined and run as a
+    process of its own: the shared host_count / host_scan / host_rank against brute force at 1, B - 1, B, B + 1 pixels and at S and
+    S + 1 blocks, with a scratch buffer of exactly the planned words, and stride_grid at 0, 1, lanes + 1 and past the cap"""
+    exe = str(tmp_path / "scan_host")
+    r = subprocess.run([H.cc(plus=True), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Werror",
+                        "-I", os.path.join(REPO, "ubresnet_amd", "csrc"), os.path.join(REPO, "tests", "scan_host.cpp"), "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    p = subprocess.run([exe], capture_output=True, text=True)
+    assert p.returncode == 0, "sanitizer or program failure:\n" + p.stderr[-2000:]
+    lines = p.stdout.strip().split("\n")
+    rows = [[int(v) for v in l.split()[1:]] for l in lines if l.startswith("I ")]
+    B_, S_ = R.PIXEL_BLOCK, R.SCAN_WIDTH
+    assert [r[0] for r in rows] == [1, B_ - 1, B_, B_ + 1, S_ * B_, S_ * B_ + 1]
+    assert [r[1:3] for r in rows] == [[1, 1], [1, 1], [1, 1], [2, 1], [S_, 1], [S_ + 1, 2]]
+    assert all(sbytes == 4 * (-(-blocks // 4) * 4) for _, blocks, _, sbytes in rows)
+    assert lines[-1].split() == ["G"] + [str(v) for v in (Z.LANES, Z.LANE_PIXELS, Z.PIXEL_BLOCK, Z.SCAN_WIDTH)]
 
 
 # ------------------------------------------------------------------------------------------------------------------------

@@ -3,8 +3,9 @@ and status.  With T_H x T_W the tile of the local pass, the views are 1x1x1, 1x1
 3x(T_H-1)x(T_W-1); the patterns are those of cluster_ref.PATTERNS (empty, all lit, checkerboard, a diagonal through every tile, a
 serpentine, a "U", a diagonal touch across a four-tile corner, row wrap, plane wrap, striped classes, foreign labels, random fields
 at 1 / 41 / 59 / 90 % lit), each at both connectivities with and without by_class, and one 3 x 200 x 700 cut of
-synthetic.make_labelled_event.  Then: confidence edge values; capacity overflow; of_pixels; two calls and two streams; a captured
-graph replayed over a changed input."""
+synthetic.make_labelled_event.  Then: confidence edge values; capacity overflow; ubi_tabulate alone on hand-made root maps (S + 1
+pixel blocks: the scan's second trip; one wave of two interleaved clusters and of 64 clusters); of_pixels; two calls and two
+streams; a captured graph replayed over a changed input."""
 import numpy as np
 import pytest
 import torch
@@ -138,6 +139,66 @@ def test_capacity_overflow_leaves_the_rows_past_capacity_alone():
                 found.read()
     exact = _clusterer(shape, 8, False, capacity=ref["count"])(*_dev(label, conf)).read(min_pixels=3)
     assert exact.total == ref["count"] and exact.rows.numpy().tolist() == ref["table"][ref["table"][:, 1] >= 3].tolist()
+
+
+def test_numbering_across_two_scan_trips():
+    """ubi_tabulate alone on a hand-made root map of S + 1 pixel blocks, S the scan width: the second trip of the one-workgroup
+    scan and its carry.  Every root is a cluster of one pixel, so the expected values are closed forms: ids is the exclusive
+    cumulative sum of the root flags, count the number of roots, and table row k below the capacity is the k-th root's pixel."""
+    from ubresnet_amd import _lib as L
+    P, rows, cols, C = 1, I.SCAN_WIDTH + 1, I.PIXEL_BLOCK, R.C4
+    n = P * rows * cols
+    assert -(-n // I.PIXEL_BLOCK) == I.SCAN_WIDTH + 1
+    flag = np.random.default_rng(1025).random(n) < 0.003
+    flag[[5, n - 3]] = True                                      # a root in block 0 and one in block S
+    q = np.flatnonzero(flag)
+    capacity = 1000
+    assert capacity < len(q) < 2 * 0.003 * n and q[0] < I.PIXEL_BLOCK and q[-1] >= I.SCAN_WIDTH * I.PIXEL_BLOCK
+    root = np.where(flag, np.arange(n), -1).astype(np.int32)
+    label = np.where(flag, np.arange(n) % C, R.FILL).astype(np.uint8)
+    want_ids = np.where(flag, np.cumsum(flag) - flag, -1).astype(np.int32)
+    want = np.zeros((capacity, R.TABLE_FIXED + C), np.int64)     # root, pixels, row_min, row_max, col_min, col_max, conf_sum, nonfinite
+    k, qk = np.arange(capacity), q[:capacity]
+    want[:, 0], want[:, 1], want[:, 6] = qk, 1, 1 << 24           # fix(1.0) = 2^24
+    want[:, 2], want[:, 3], want[:, 4], want[:, 5] = qk // cols, qk // cols, qk % cols, qk % cols
+    want[k, R.TABLE_FIXED + qk % C] = 1
+    d_root, d_label = torch.from_numpy(root).cuda(), torch.from_numpy(label).cuda()
+    d_conf = torch.full((n,), 1.0, dtype=torch.float16, device="cuda")
+    ids = torch.full((n,), -5, dtype=torch.int32, device="cuda")
+    table = torch.full((len(q), R.TABLE_FIXED + C), -77, dtype=torch.int64, device="cuda")
+    count = torch.full((1,), -1, dtype=torch.int64, device="cuda")
+    scratch = torch.empty(I.scratch_bytes(P, rows, cols) // 4, dtype=torch.int32, device="cuda")
+    I.tabulate(d_label.data_ptr(), d_conf.data_ptr(), d_root.data_ptr(), C, R.FILL, ids.data_ptr(), table.data_ptr(), capacity,
+               count.data_ptr(), scratch.data_ptr(), P, rows, cols, L.stream_ptr())
+    torch.cuda.synchronize()
+    got_ids, got = ids.cpu().numpy(), table.cpu().numpy()
+    assert int(count.item()) == len(q)
+    assert (got_ids == want_ids).all(), "ids: first difference at %s" % (np.flatnonzero(got_ids != want_ids)[:1].tolist(),)
+    assert (got[:capacity] == want).all(), "table: first difference at row, column %s" % (np.argwhere(got[:capacity] != want)[:1].tolist(),)
+    assert (got[capacity:] == -77).all(), "a row at or past the capacity was written"
+
+
+@pytest.mark.parametrize("shape_of_keys", ["interleaved", "distinct"])
+def test_the_tally_on_one_wave_of_hand_made_roots(shape_of_keys):
+    """ubi_tabulate alone on one row of 64 pixels, all lit, the tally's whole wave: two clusters interleaved lane by lane (which
+    no labelling of a single row can make), and 64 clusters of one pixel"""
+    from ubresnet_amd import _lib as L
+    n, C = 64, R.C4
+    q = np.arange(n)
+    root = (q % 2 if shape_of_keys == "interleaved" else q).astype(np.int32).reshape(1, 1, n)
+    label, conf = (q // 3 % C).astype(np.uint8).reshape(1, 1, n), R.confidence_bits((1, 1, n))
+    want_ids, want, want_count = R.tabulate(label, conf, root, C)
+    assert want_count == (2 if shape_of_keys == "interleaved" else n) and want[:, 1].sum() == n
+    ids = torch.full((n,), -5, dtype=torch.int32, device="cuda")
+    table = torch.full((want_count, R.TABLE_FIXED + C), -77, dtype=torch.int64, device="cuda")
+    count = torch.full((1,), -1, dtype=torch.int64, device="cuda")
+    scratch = torch.empty(I.scratch_bytes(1, 1, n) // 4, dtype=torch.int32, device="cuda")
+    (dl, dc), dr = _dev(label, conf), torch.from_numpy(root).cuda()
+    I.tabulate(dl.data_ptr(), dc.data_ptr(), dr.data_ptr(), C, R.FILL, ids.data_ptr(), table.data_ptr(), want_count, count.data_ptr(),
+               scratch.data_ptr(), 1, 1, n, L.stream_ptr())
+    torch.cuda.synchronize()
+    assert int(count.item()) == want_count and (ids.cpu().numpy() == want_ids.reshape(-1)).all()
+    assert (table.cpu().numpy() == want).all(), (table.cpu().numpy().tolist(), want.tolist())
 
 
 def test_of_pixels_is_ids_at_the_listed_pixels():

@@ -5,7 +5,7 @@ cur=None; rows={}
 for l in r.stderr.split("\n"):
     m=re.search(r"Function Name: (\S+)",l)
     if m: cur=m.group(1); rows[cur]={}
-    for key in ("VGPRs","AGPRs","ScratchSize \[bytes/lane\]","Occupancy \[waves/SIMD\]","VGPRs Spill","SGPRs"):
+    for key in ("VGPRs","AGPRs","ScratchSize \[bytes/lane\]","Occupancy \[waves/SIMD\]","VGPRs Spill","TotalSGPRs","SGPRs Spill","LDS Size \[bytes/block\]"):
         m=re.search(r"remark:\s+"+key+r": (\d+)",l)
         if m and cur: rows[cur][key.split(" [")[0].replace("\\","")]=int(m.group(1))
 import subprocess as sp

@@ -4,7 +4,8 @@
 
 LIBS is the table of them, in build order: name -> (out, sources, headers, binding).  `hip` is libubresnet_hip.so, all HIP kernels
 of the network and its C ABI; every other entry is a library of one .hip file that links against none of the
-others (csrc/ubr_sat.h is the support header they all include), and whose purpose the docstring of its binding module states.  `sources` and `headers` are relative to csrc/, `headers`
+others (csrc/ubr_sat.h is the support header they all include; the event-product libraries of csrc/extra/ also share
+csrc/ubr_wave.h, their wave and workgroup primitives, and csrc/ubr_scan_plan.h, the plan of their pixel-block compaction), and whose purpose the docstring of its binding module states.  `sources` and `headers` are relative to csrc/, `headers`
 being every file the sources reach through quoted #includes; `binding` names the ctypes module of ubresnet_amd that loads `out`.
 
 The shared libraries have NO PyTorch dependency: they are plain HIP behind the public headers in include/.  Objects are compiled
@@ -53,7 +54,7 @@ LIBS = {
 
 EXTRAS = {
     "score": Lib(os.path.join(HERE, "libubresnet_score.so"), [os.path.join("extra", "ubr_score.hip")],
-                 ["ubr_sat.h", "ubr_rows.h", os.path.join("..", "..", "include", "ubresnet_score.h")], "_score"),
+                 ["ubr_sat.h", "ubr_wave.h", os.path.join("..", "..", "include", "ubresnet_score.h")], "_score"),
 }
 
 # the libraries after EXTRAS join this table: its tests pin what it contains, not its length
@@ -61,16 +62,16 @@ ADDONS = {
     "blend": Lib(os.path.join(HERE, "libubresnet_blend.so"), [os.path.join("extra", "ubr_blend.hip")],
                  ["ubr_sat.h", os.path.join("..", "..", "include", "ubresnet_blend.h")], "_blend"),
     "sparse": Lib(os.path.join(HERE, "libubresnet_sparse.so"), [os.path.join("extra", "ubr_sparse.hip")],
-                  ["ubr_sat.h", "ubr_sparse_plan.h", os.path.join("..", "..", "include", "ubresnet_sparse.h")], "_sparse"),
+                  ["ubr_sat.h", "ubr_sparse_plan.h", "ubr_scan_plan.h", "ubr_wave.h", os.path.join("..", "..", "include", "ubresnet_sparse.h")], "_sparse"),
     "crop": Lib(os.path.join(HERE, "libubresnet_crop.so"), [os.path.join("extra", "ubr_crop.hip")],
-                ["ubr_sat.h", "ubr_crop_rule.h", "ubr_det_rule.h", os.path.join("..", "..", "include", "ubresnet_crop.h"),
+                ["ubr_sat.h", "ubr_crop_rule.h", "ubr_det_rule.h", "ubr_wave.h", os.path.join("..", "..", "include", "ubresnet_crop.h"),
                  os.path.join("..", "..", "include", "ubresnet_det.h")], "_crop"),
     "calib": Lib(os.path.join(HERE, "libubresnet_calib.so"), [os.path.join("extra", "ubr_calib.hip")],
                  ["ubr_sat.h", "ubr_calib_plan.h", os.path.join("..", "..", "include", "ubresnet_calib.h")], "_calib"),
     "cluster": Lib(os.path.join(HERE, "libubresnet_cluster.so"), [os.path.join("extra", "ubr_cluster.hip")],
-                   ["ubr_sat.h", "ubr_cluster_plan.h", os.path.join("..", "..", "include", "ubresnet_cluster.h")], "_cluster"),
+                   ["ubr_sat.h", "ubr_cluster_plan.h", "ubr_scan_plan.h", "ubr_wave.h", os.path.join("..", "..", "include", "ubresnet_cluster.h")], "_cluster"),
     "moment": Lib(os.path.join(HERE, "libubresnet_moment.so"), [os.path.join("extra", "ubr_moment.hip")],
-                  ["ubr_sat.h", "ubr_moment_plan.h", os.path.join("..", "..", "include", "ubresnet_moment.h")], "_moment"),
+                  ["ubr_sat.h", "ubr_moment_plan.h", "ubr_scan_plan.h", "ubr_wave.h", os.path.join("..", "..", "include", "ubresnet_moment.h")], "_moment"),
 }
 
 

@@ -1,7 +1,8 @@
 // libubresnet_cluster.so: connected components of event products (include/ubresnet_cluster.h).  It links against none of the
 // other libraries and shares ubr_sat.h with them; the launches are plain <<<>>> on the caller's stream.  Tile, pixel block, grids
 // and the scratch layout come from ../ubr_cluster_plan.h, which tests/cluster_host.cpp runs on the host together with a model of
-// the find and union loops below.
+// the find and union loops below; the workgroup count, rank and scan of the numbering, the key walk and the wave sum of the tally
+// come from ../ubr_wave.h.
 //
 // Loops and their bounds ("EventClusters"):
 //   find     x = parent[x] while parent[x] < x: x strictly decreases, at most x trips
@@ -12,6 +13,7 @@
 #include "../../../include/ubresnet_cluster.h"
 #include "../ubr_cluster_plan.h"
 #include "../ubr_sat.h"
+#include "../ubr_wave.h"
 
 #define UBI_VERSION 1
 
@@ -138,13 +140,9 @@ __global__ __launch_bounds__(UBI_LANES) void local_kernel(const LabelK k) {
     }
     k.root[t.plane + (long)gy * k.cols + gx] = out;
   }
-  if (lane == 0) s_foreign[wave] = foreign;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned n = 0;
-    for (int w = 0; w < ubi::WAVES; ++w) n += s_foreign[w];
+  wv::block_total<ubi::WAVES>(foreign, s_foreign, [&k](unsigned n) {
     if (n) atomicAdd(k.status, (u64)n);
-  }
+  });
 }
 
 // launch 2 of ubi_label: one workgroup per tile; lanes 0..TW-1 the pixels of the tile's last row, united with the three pixels
@@ -200,50 +198,13 @@ __global__ __launch_bounds__(UBI_LANES) void count_kernel(const int32_t* __restr
   __shared__ unsigned s_wave[ubi::WAVES];
   int r[4];
   const unsigned m = root_mask(root, blockIdx.x * (unsigned)UBI_PIXEL_BLOCK + threadIdx.x * 4u, pixels, r);
-  unsigned c = 0;
-  for (int j = 0; j < 4; ++j) c += (unsigned)__popcll(__ballot((m >> j) & 1u));
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned t = 0;
-    for (int w = 0; w < ubi::WAVES; ++w) t += s_wave[w];
-    scratch[blockIdx.x] = t;
-  }
+  wv::block_total<ubi::WAVES>(wv::mask_count<4>(m), s_wave, [scratch](unsigned t) { scratch[blockIdx.x] = t; });
 }
 
 // ONE workgroup; an exclusive scan of the block counts in place, UBI_SCAN_WIDTH per trip, four per lane; count[0] = total
 __global__ __launch_bounds__(UBI_LANES) void scan_kernel(unsigned* __restrict__ scratch, long blocks, long trips, u64* __restrict__ count) {
   __shared__ unsigned s_wave[ubi::WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned carry = 0;
-  for (long t = 0; t < trips; ++t) {
-    const long i0 = t * UBI_SCAN_WIDTH + (long)threadIdx.x * 4;
-    uint4 c = make_uint4(0u, 0u, 0u, 0u);
-    if (i0 < blocks) {                                         // i0 + 3 < scratch_words: the plan rounds the words up to four
-      c = *(const uint4*)(scratch + i0);
-      if (i0 + 1 >= blocks) c.y = 0u;                          // the words past the last block were never written
-      if (i0 + 2 >= blocks) c.z = 0u;
-      if (i0 + 3 >= blocks) c.w = 0u;
-    }
-    const unsigned sum = c.x + c.y + c.z + c.w;
-    unsigned inc = sum;
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned up = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += up;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    unsigned before = 0, total = 0;
-    for (int w = 0; w < ubi::WAVES; ++w) {
-      if (w < wave) before += s_wave[w];
-      total += s_wave[w];
-    }
-    const unsigned ex = carry + before + inc - sum;
-    if (i0 < blocks) *(uint4*)(scratch + i0) = make_uint4(ex, ex + c.x, ex + c.x + c.y, ex + c.x + c.y + c.z);
-    carry += total;
-    __syncthreads();                                           // s_wave is written again in the next trip
-  }
-  if (threadIdx.x == 0) count[0] = (u64)carry;
+  wv::scan_block_counts<ubi::WAVES>(scratch, blocks, trips, count, s_wave);
 }
 
 // ids = the cluster number at the roots and -1 at the pixels that are not lit; the root of cluster k < capacity also stores the
@@ -252,22 +213,11 @@ __global__ __launch_bounds__(UBI_LANES) void number_kernel(const int32_t* __rest
                                                            int32_t* __restrict__ ids, long long* __restrict__ table, u64 capacity, int C,
                                                            int rows, int cols) {
   __shared__ unsigned s_wave[ubi::WAVES];
-  const int wave = threadIdx.x >> 6;
   const unsigned q = blockIdx.x * (unsigned)UBI_PIXEL_BLOCK + threadIdx.x * 4u;
   int r[4];
   const unsigned m = root_mask(root, q, pixels, r);
-  unsigned in_wave = 0, lanes_before = 0;
-  for (int j = 0; j < 4; ++j) {
-    const u64 b = __ballot((m >> j) & 1u);
-    in_wave += (unsigned)__popcll(b);
-    lanes_before += __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-  }
-  if ((threadIdx.x & 63) == 0) s_wave[wave] = in_wave;
-  __syncthreads();
-  unsigned waves_before = 0;
-  for (int w = 0; w < ubi::WAVES; ++w)
-    if (w < wave) waves_before += s_wave[w];
-  u64 kq = (u64)scratch[blockIdx.x] + waves_before + lanes_before;
+  const unsigned before = wv::block_rank<ubi::WAVES, 4>(m, s_wave);
+  u64 kq = (u64)scratch[blockIdx.x] + before;
   const int width = UBI_TABLE_FIXED + C;
   for (unsigned j = 0; j < 4u; ++j) {
     if (q + j >= pixels) break;
@@ -289,16 +239,6 @@ __global__ __launch_bounds__(UBI_LANES) void number_kernel(const int32_t* __rest
 // wave that share a cluster number are found by ballot and combined before one lane goes to memory; a lane alone with its
 // number goes by itself, after the loop, together with the other such lanes.
 // ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 wave_sum_all(u64 v) {
-  unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    v += ((u64)(unsigned)__shfl_xor((int)hi, d) << 32) | (unsigned)__shfl_xor((int)lo, d);
-    lo = (unsigned)v; hi = (unsigned)(v >> 32);
-  }
-  return v;
-}
-
 __device__ __forceinline__ void tally_row(u64* row, u64 n, int ymin, int ymax, int xmin, int xmax, u64 sum, u64 bad) {
   atomicAdd(row + 1, n);
   atomicMin(row + 2, (u64)ymin);
@@ -346,39 +286,35 @@ __global__ __launch_bounds__(UBI_LANES) void tally_kernel(const uint8_t* __restr
     }
     bool solo = false;
     while (rem != 0ull) {                                       // wave-uniform: one trip per distinct number among the counted lanes
-      const int leader = __ffsll((long long)rem) - 1;
-      const int kk = __shfl(k, leader);
-      const bool member = counted && k == kk;
-      const u64 m = __ballot(member);
-      rem &= ~m;
-      const unsigned n = (unsigned)__popcll(m);
+      const wv::KeyGroup<int> g = wv::next_key_group(rem, k, counted);
+      const unsigned n = (unsigned)__popcll(g.lanes);
       if (n == 1u) {
-        solo = solo || lane == leader;
+        solo = solo || lane == g.leader;
         continue;
       }
       // a cluster lies in one plane, so its rows ascend with the lane: the first and the last member hold the extremes
-      const int last = 63 - __clzll((long long)m);
-      const int ymin = __shfl(y, leader), ymax = __shfl(y, last);
+      const int last = 63 - __clzll((long long)g.lanes);
+      const int ymin = __shfl(y, g.leader), ymax = __shfl(y, last);
       int xmin, xmax;
       if (ymin == ymax) {                                       // one row: the columns ascend as well
-        xmin = __shfl(x, leader);
+        xmin = __shfl(x, g.leader);
         xmax = __shfl(x, last);
       } else {
-        xmin = member ? x : 0x7FFFFFFF;
-        xmax = member ? x : 0;
+        xmin = g.member ? x : 0x7FFFFFFF;
+        xmax = g.member ? x : 0;
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) {
           xmin = min(xmin, __shfl_xor(xmin, d));
           xmax = max(xmax, __shfl_xor(xmax, d));
         }
       }
-      const u64 sum = wave_sum_all(member ? fx : 0ull);
-      const u64 nbad = (u64)__popcll(__ballot(member && bad));
-      u64* row = table + (u64)kk * (u64)width;
-      if (lane == leader) tally_row(row, (u64)n, ymin, ymax, xmin, xmax, sum, nbad);
+      const u64 sum = wv::sum_all(g.member ? fx : 0ull);
+      const u64 nbad = (u64)__popcll(__ballot(g.member && bad));
+      u64* row = table + (u64)g.key * (u64)width;
+      if (lane == g.leader) tally_row(row, (u64)n, ymin, ymax, xmin, xmax, sum, nbad);
       for (int c = 0; c < C; ++c) {
-        const unsigned nc = (unsigned)__popcll(__ballot(member && lab == (unsigned)c));
-        if (nc != 0u && lane == leader) atomicAdd(row + UBI_TABLE_FIXED + c, (u64)nc);
+        const unsigned nc = (unsigned)__popcll(__ballot(g.member && lab == (unsigned)c));
+        if (nc != 0u && lane == g.leader) atomicAdd(row + UBI_TABLE_FIXED + c, (u64)nc);
       }
     }
     if (solo) {

@@ -1,11 +1,12 @@
 // libubresnet_crop.so: training crops out of a whole labelled view (include/ubresnet_crop.h).  It links against none of the other
 // libraries and shares ubr_sat.h with them; the launches are plain <<<>>> on the caller's stream.  The rule -- geometry, label
 // conversion, the selection of one crop, the check of a table row -- is ../ubr_crop_rule.h, which tests/crop_host.cpp runs on
-// the host; Philox comes with it from ../ubr_det_rule.h.
+// the host; Philox comes with it from ../ubr_det_rule.h.  The workgroup scan of the occupancy rows is that of ../ubr_wave.h.
 #include <hip/hip_runtime.h>
 #include "../../../include/ubresnet_crop.h"
 #include "../ubr_sat.h"
 #include "../ubr_crop_rule.h"
+#include "../ubr_wave.h"
 
 #define UBN_VERSION 1
 
@@ -126,7 +127,7 @@ __global__ __launch_bounds__(UBN_LANES) void count_rows_kernel(const occ_t a) {
     for (int u0 = 0; u0 < quads; u0 += 64) {
       const int u = u0 + lane;
       const unsigned m = u < quads ? count_mask(a, q, i * g + (u >> sh), j * g + 4 * (u & (qpr - 1))) : 0u;
-      for (int b = 0; b < 4; ++b) c += (int32_t)__popcll(__ballot((m >> b) & 1u));
+      c += (int32_t)wv::mask_count<4>(m);
     }
     if (lane == 0) s_cnt[j] = c;
   }
@@ -135,19 +136,9 @@ __global__ __launch_bounds__(UBN_LANES) void count_rows_kernel(const occ_t a) {
   int32_t carry = 0;
   for (int j0 = 0; j0 < a.CC; j0 += UBN_LANES) {
     const int j = j0 + (int)threadIdx.x;
-    int32_t inc = j < a.CC ? s_cnt[j] : 0;
-    for (int d = 1; d < 64; d <<= 1) {
-      const int32_t up = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += up;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    int32_t before = 0, total = 0;
-    for (int w = 0; w < WAVES; ++w) {
-      if (w < wave) before += s_wave[w];
-      total += s_wave[w];
-    }
-    if (j < a.CC) row[j + 1] = carry + before + inc;
+    int32_t total;
+    const int32_t upto = wv::block_scan<WAVES, int32_t>(j < a.CC ? s_cnt[j] : 0, s_wave, &total);
+    if (j < a.CC) row[j + 1] = carry + upto;
     carry += total;
     __syncthreads();                                                        // s_wave is written again in the next trip
   }

@@ -1,6 +1,7 @@
 // libubresnet_moment.so: per-cluster charge and shape (include/ubresnet_moment.h).  It links against none of the other libraries
 // and shares ubr_sat.h with them; the launches are plain <<<>>> on the caller's stream.  Trip, grid, span, limits and the overflow
-// bound come from ../ubr_moment_plan.h, which tests/moment_host.cpp runs on the host.
+// bound come from ../ubr_moment_plan.h, which tests/moment_host.cpp runs on the host; the key walk and the wave sums from
+// ../ubr_wave.h.
 //
 // Loops and their bounds ("ClusterMoments"):
 //   the trip loop of a workgroup runs over the host-computed span; the clear strides over a length read from the device
@@ -11,6 +12,7 @@
 #include "../../../include/ubresnet_moment.h"
 #include "../ubr_moment_plan.h"
 #include "../ubr_sat.h"
+#include "../ubr_wave.h"
 
 #define UBM_VERSION 1
 
@@ -50,22 +52,6 @@ __global__ __launch_bounds__(UBM_LANES) void clear_kernel(u64* __restrict__ tabl
   if (n > capacity) n = capacity;
   n *= width;
   for (u64 i = (u64)blockIdx.x * UBM_LANES + threadIdx.x; i < n; i += (u64)gridDim.x * UBM_LANES) table[i] = 0ull;
-}
-
-__device__ __forceinline__ unsigned wave_sum32(unsigned v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += (unsigned)__shfl_xor((int)v, d);
-  return v;
-}
-
-__device__ __forceinline__ u64 wave_sum64(u64 v) {
-  unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    v += ((u64)(unsigned)__shfl_xor((int)hi, d) << 32) | (unsigned)__shfl_xor((int)lo, d);
-    lo = (unsigned)v; hi = (unsigned)(v >> 32);
-  }
-  return v;
 }
 
 // The weight of an ADC value and its count word (weighted | clipped << COUNT_BITS | odd << 2 COUNT_BITS).  The sign and NaN
@@ -142,35 +128,31 @@ __device__ __forceinline__ void wave_round(const Lds& s, const MomK& a, int key,
   u64 rem = __ballot(active);
   bool solo = false;
   while (rem != 0ull) {                                           // wave-uniform: one trip per distinct cluster among the active lanes
-    const int leader = __ffsll((long long)rem) - 1;
-    const int kl = __shfl(key, leader);
-    const bool member = active && key == kl;
-    const u64 mm = __ballot(member);
-    rem &= ~mm;
-    if (__popcll(mm) == 1) {
-      solo = solo || lane == leader;
+    const wv::KeyGroup<int> g = wv::next_key_group(rem, key, active);
+    if (__popcll(g.lanes) == 1) {
+      solo = solo || lane == g.leader;
       continue;
     }
     Sums t;
-    t.cnt = wave_sum32(member ? m.cnt : 0u);
-    t.q = wave_sum32(member ? m.q : 0u);
-    t.qr = wave_sum64(member ? m.qr : 0ull);
-    t.qc = wave_sum64(member ? m.qc : 0ull);
-    t.qrr = wave_sum64(member ? m.qrr : 0ull);
-    t.qrc = wave_sum64(member ? m.qrc : 0ull);
-    t.qcc = wave_sum64(member ? m.qcc : 0ull);
+    t.cnt = wv::sum_all(g.member ? m.cnt : 0u);
+    t.q = wv::sum_all(g.member ? m.q : 0u);
+    t.qr = wv::sum_all(g.member ? m.qr : 0ull);
+    t.qc = wv::sum_all(g.member ? m.qc : 0ull);
+    t.qrr = wv::sum_all(g.member ? m.qrr : 0ull);
+    t.qrc = wv::sum_all(g.member ? m.qrc : 0ull);
+    t.qcc = wv::sum_all(g.member ? m.qcc : 0ull);
     int slot = -1;
-    if (lane == leader) {
-      slot = find_slot(s, kl);
-      push_sums(s, a, slot, kl, t);
+    if (lane == g.leader) {
+      slot = find_slot(s, g.key);
+      push_sums(s, a, slot, g.key, t);
     }
     if (t.q != 0u) {
       for (int c = 0; c < a.C; ++c) {
         unsigned mine = 0u;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) mine += (member && ((pm >> j) & 1u) && lab[j] == (unsigned)c) ? w[j] : 0u;
-        const unsigned qc = wave_sum32(mine);
-        if (lane == leader) push(s, a, slot, kl, UBM_TABLE_FIXED + c, (u64)qc);
+        for (int j = 0; j < 4; ++j) mine += (g.member && ((pm >> j) & 1u) && lab[j] == (unsigned)c) ? w[j] : 0u;
+        const unsigned qc = wv::sum_all(mine);
+        if (lane == g.leader) push(s, a, slot, g.key, UBM_TABLE_FIXED + c, (u64)qc);
       }
     }
   }

@@ -1,10 +1,10 @@
 // libubresnet_score.so: event products scored against a truth image (include/ubresnet_score.h).  It links against none of the
-// other libraries and shares ubr_sat.h with them and ubr_rows.h with the loss libraries; the launch is a plain <<<>>> on the
-// caller's stream.
+// other libraries and shares ubr_sat.h with them and ubr_wave.h (the key walk, the wave sum) with the other event-product
+// libraries; the launch is a plain <<<>>> on the caller's stream.
 #include <hip/hip_runtime.h>
 #include "../../../include/ubresnet_score.h"
-#include "../ubr_rows.h"
 #include "../ubr_sat.h"
+#include "../ubr_wave.h"
 
 #define UBQ_VERSION 1
 
@@ -195,15 +195,12 @@ __global__ __launch_bounds__(BLOCK) void score_kernel(const ScoreK k) {
           key = (s << 14) | (tr[q] << 10) | (lab[q] << 6) | b;  // tr, lab < 16; b <= 32
         }
         while (rem != 0ull) {                                   // wave-uniform: one trip per distinct key among the scored lanes
-          const int leader = __ffsll((long long)rem) - 1;
-          const unsigned kk = (unsigned)__shfl((int)key, leader);
-          const bool member = scored && key == kk;
-          const unsigned long long m = __ballot(member);
-          const unsigned n = (unsigned)__popcll(m);
-          unsigned long long sum = member ? fx : 0ull;
-          if (n > 1u) sum = rowsum::wave_sum_all(sum);
-          if (lane == leader) {
-            const unsigned s = kk >> 14, tt = (kk >> 10) & 15u, ll = (kk >> 6) & 15u, b = kk & 63u;
+          const wv::KeyGroup<unsigned> g = wv::next_key_group(rem, key, scored);
+          const unsigned n = (unsigned)__popcll(g.lanes);
+          unsigned long long sum = g.member ? fx : 0ull;
+          if (n > 1u) sum = wv::sum_all(sum);
+          if (lane == g.leader) {
+            const unsigned kk = g.key, s = kk >> 14, tt = (kk >> 10) & 15u, ll = (kk >> 6) & 15u, b = kk & 63u;
             atomicAdd(&tab[(s * C + tt) * C + ll], (unsigned long long)n);
             if ((int)b < bins) {
               unsigned long long* r = tab + conf_words + (s * bins + b) * 3;
@@ -214,7 +211,6 @@ __global__ __launch_bounds__(BLOCK) void score_kernel(const ScoreK k) {
               atomicAdd(&tab[tally_at + 3], (unsigned long long)n);
             }
           }
-          rem &= ~m;
         }
       }
     }

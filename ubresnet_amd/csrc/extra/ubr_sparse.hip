@@ -1,10 +1,11 @@
 // libubresnet_sparse.so: sparse event I/O (include/ubresnet_sparse.h).  It links against none of the other libraries and shares
 // ubr_sat.h with them; the launches are plain <<<>>> on the caller's stream.  Block sizes, grids and the scratch layout come
-// from ../ubr_sparse_plan.h, which tests/sparse_host.cpp runs on the host.
+// from ../ubr_sparse_plan.h, which tests/sparse_host.cpp runs on the host; the workgroup count, rank and scan from ../ubr_wave.h.
 #include <hip/hip_runtime.h>
 #include "../../../include/ubresnet_sparse.h"
 #include "../ubr_sat.h"
 #include "../ubr_sparse_plan.h"
+#include "../ubr_wave.h"
 
 #define UBZ_VERSION 1
 
@@ -94,15 +95,11 @@ __global__ __launch_bounds__(UBZ_LANES) void scatter_kernel(const int32_t* __res
       }
       invalid = !valid;
     }
-    bad += (unsigned)__popcll(__ballot(invalid));
+    bad += wv::mask_count<1>(invalid);
   }
-  if ((threadIdx.x & 63) == 0) s_bad[threadIdx.x >> 6] = bad;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned t = 0;
-    for (int w = 0; w < ubz::WAVES; ++w) t += s_bad[w];
+  wv::block_total<ubz::WAVES>(bad, s_bad, [status](unsigned t) {
     if (t) atomicAdd(status, (u64)t);
-  }
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -144,75 +141,27 @@ __global__ __launch_bounds__(UBZ_LANES) void count_kernel(const float* __restric
   __shared__ unsigned s_wave[ubz::WAVES];
   const unsigned q = blockIdx.x * (unsigned)UBZ_PIXEL_BLOCK + threadIdx.x * 4u;
   const unsigned m = lit_mask(adc, vplanes, thr, q, pixels, rc);
-  unsigned c = 0;
-  for (int j = 0; j < 4; ++j) c += (unsigned)__popcll(__ballot((m >> j) & 1u));
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned t = 0;
-    for (int w = 0; w < ubz::WAVES; ++w) t += s_wave[w];
-    scratch[blockIdx.x] = t;
-  }
+  wv::block_total<ubz::WAVES>(wv::mask_count<4>(m), s_wave, [scratch](unsigned t) { scratch[blockIdx.x] = t; });
 }
 
 // launch 2: ONE workgroup; an exclusive scan of the block counts in place, UBZ_SCAN_WIDTH per trip, four per lane; count[0] = total
 __global__ __launch_bounds__(UBZ_LANES) void scan_kernel(unsigned* __restrict__ scratch, long blocks, long trips, u64* __restrict__ count) {
   __shared__ unsigned s_wave[ubz::WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned carry = 0;
-  for (long t = 0; t < trips; ++t) {
-    const long i0 = t * UBZ_SCAN_WIDTH + (long)threadIdx.x * 4;
-    uint4 c = make_uint4(0u, 0u, 0u, 0u);
-    if (i0 < blocks) {                                       // i0 + 3 < scratch_words: the plan rounds the words up to four
-      c = *(const uint4*)(scratch + i0);
-      if (i0 + 1 >= blocks) c.y = 0u;                        // the words past the last block were never written
-      if (i0 + 2 >= blocks) c.z = 0u;
-      if (i0 + 3 >= blocks) c.w = 0u;
-    }
-    const unsigned sum = c.x + c.y + c.z + c.w;
-    unsigned inc = sum;
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned up = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += up;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    unsigned before = 0, total = 0;
-    for (int w = 0; w < ubz::WAVES; ++w) {
-      if (w < wave) before += s_wave[w];
-      total += s_wave[w];
-    }
-    const unsigned ex = carry + before + inc - sum;
-    if (i0 < blocks) *(uint4*)(scratch + i0) = make_uint4(ex, ex + c.x, ex + c.x + c.y, ex + c.x + c.y + c.z);
-    carry += total;
-    __syncthreads();                                         // s_wave is written again in the next trip
-  }
-  if (threadIdx.x == 0) count[0] = (u64)carry;
+  wv::scan_block_counts<ubz::WAVES>(scratch, blocks, trips, count, s_wave);
 }
 
 // launch 3: the same predicate again; a lit pixel's place is its block's offset + the lit pixels of the waves before its own
-// (LDS) + those of the lanes before its own (mbcnt of the four ballots) + those before it in its lane
+// and of the lanes before its own (wv::block_rank) + those before it in its lane
 __global__ __launch_bounds__(UBZ_LANES) void write_kernel(const uint8_t* __restrict__ label, const uint16_t* __restrict__ confidence,
                                                           const float* __restrict__ adc, int vplanes, float thr, unsigned pixels,
                                                           unsigned rc, const unsigned* __restrict__ scratch, u64 capacity,
                                                           int32_t* __restrict__ out_index, uint8_t* __restrict__ out_label,
                                                           uint16_t* __restrict__ out_confidence) {
   __shared__ unsigned s_wave[ubz::WAVES];
-  const int wave = threadIdx.x >> 6;
   const unsigned q = blockIdx.x * (unsigned)UBZ_PIXEL_BLOCK + threadIdx.x * 4u;
   const unsigned m = lit_mask(adc, vplanes, thr, q, pixels, rc);
-  unsigned in_wave = 0, lanes_before = 0;
-  for (int j = 0; j < 4; ++j) {
-    const u64 b = __ballot((m >> j) & 1u);
-    in_wave += (unsigned)__popcll(b);
-    lanes_before += __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-  }
-  if ((threadIdx.x & 63) == 0) s_wave[wave] = in_wave;
-  __syncthreads();
-  unsigned waves_before = 0;
-  for (int w = 0; w < ubz::WAVES; ++w)
-    if (w < wave) waves_before += s_wave[w];
-  u64 k = (u64)scratch[blockIdx.x] + waves_before + lanes_before;
+  const unsigned before = wv::block_rank<ubz::WAVES, 4>(m, s_wave);
+  u64 k = (u64)scratch[blockIdx.x] + before;
   for (unsigned j = 0; j < 4u; ++j) {
     if (!((m >> j) & 1u)) continue;
     if (k < capacity) {

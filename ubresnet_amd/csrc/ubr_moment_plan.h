@@ -12,7 +12,7 @@
 #ifndef UBR_MOMENT_PLAN_H
 #define UBR_MOMENT_PLAN_H
 
-#include <stdint.h>
+#include "ubr_scan_plan.h"                            // MAX_PIXELS, the bound of an int32 pixel index, and nothing else
 
 namespace ubm {
 
@@ -33,7 +33,7 @@ constexpr int64_t MAX_ROWS = 4096, MAX_COLS = 4096;
 constexpr int64_t MAX_PLANE_PIXELS = (int64_t)1 << 22;
 constexpr int64_t MAX_WEIGHT = 65535;
 constexpr int MAX_SCALE = 256;
-constexpr int64_t MAX_PIXELS = ((int64_t)1 << 31) - 1;  // a pixel index is an int32
+using scanplan::MAX_PIXELS;
 static_assert((SLOTS & (SLOTS - 1)) == 0 && SLOTS <= LANES && PROBES <= SLOTS, "k % SLOTS is a mask; one lane resets one slot key");
 static_assert(WAVE * LANE_PIXELS < (1 << COUNT_BITS), "a count field holds the pixels of a wave round");
 static_assert((uint64_t)WAVE * LANE_PIXELS * MAX_WEIGHT < ((uint64_t)1 << 32), "the charge of a wave round fits 32 bits");

@@ -1,8 +1,7 @@
 // The fixed-order sums of libubresnet_loss.so and libubresnet_dice.so (ubr_loss.hip, ubr_dice.hip): a streaming pass leaves one
 // row of 64-bit words per workgroup, fp64 sums and integer counts side by side, and one workgroup adds the rows.  The order of
 // the additions is part of those libraries' contract -- the same rows give the same bits -- so what is here is what the two
-// sources add in the same order; extra/ubr_score.hip takes its wave sum from here.  Device code only.  No other header of the
-// project is included here.
+// sources add in the same order.  Device code only.  No other header of the project is included here.
 #ifndef UBR_ROWS_H
 #define UBR_ROWS_H
 
@@ -23,18 +22,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 __device__ __forceinline__ u64 wave_sum(u64 v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  return v;
-}
-
-// the integer sum of a wave in every lane of it (a butterfly of 32-bit halves)
-__device__ __forceinline__ u64 wave_sum_all(u64 v) {
-  unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const u64 o = ((u64)(unsigned)__shfl_xor((int)hi, d) << 32) | (unsigned)__shfl_xor((int)lo, d);
-    v += o;
-    lo = (unsigned)v; hi = (unsigned)(v >> 32);
-  }
   return v;
 }
 

@@ -1,109 +1,31 @@
 // The launch plan of libubresnet_sparse.so's compaction (ubz_compact of include/ubresnet_sparse.h) as plain C++: no HIP, so
-// tests/sparse_host.cpp compiles it into a stand-alone program with the host sanitizers on.  The pixel block, the number of
-// blocks, the scan's trip count, the three grids and the scratch layout are decided here and nowhere else; host_count /
-// host_scan / host_write restate the three launches over the same plan, for that program to hold against brute force.
+// tests/sparse_host.cpp compiles it into a stand-alone program with the host sanitizers on.  The compaction is the pixel-block
+// count / scan / rank of ubr_scan_plan.h with "lit" as the predicate; what is decided here is the grid cap of the fill and
+// scatter launches, and host_count / host_write say what the count and write launches do with the shared walk.
 #ifndef UBR_SPARSE_PLAN_H
 #define UBR_SPARSE_PLAN_H
 
-#include <stdint.h>
+#include "ubr_scan_plan.h"
 
 namespace ubz {
 
-constexpr int WAVE = 64;
-constexpr int LANES = 256;                            // lanes of every workgroup: four waves
-constexpr int WAVES = LANES / WAVE;
-constexpr int LANE_PIXELS = 4;                        // consecutive pixels of one lane: one 16-byte load of adc
-constexpr int PIXEL_BLOCK = LANES * LANE_PIXELS;      // B: pixels of one workgroup of the count and write passes
-constexpr int SCAN_LANE_COUNTS = 4;                   // block counts of one lane of the scan per trip: one 16-byte load
-constexpr int SCAN_WIDTH = LANES * SCAN_LANE_COUNTS;  // S: block counts of one trip of the one-workgroup scan
+using namespace scanplan;                             // the constants, host_scan: under their names here as well
 constexpr int MAX_GRID = 4096;                        // workgroups of the fill and scatter launches (they stride)
-constexpr int64_t MAX_PIXELS = ((int64_t)1 << 31) - 1;  // a pixel index is an int32
 
-struct Plan {
-  int64_t pixels;         // P * rows * cols
-  int64_t blocks;         // ceil(pixels / PIXEL_BLOCK): the grid of the count and of the write pass
-  int64_t scan_trips;     // ceil(blocks / SCAN_WIDTH): trips of the scan's single workgroup
-  int64_t scratch_words;  // uint32 words of scratch: blocks rounded up to SCAN_LANE_COUNTS; word b is block b's count after
-                          // the count pass and the number of lit pixels before block b after the scan
-  int64_t scratch_bytes;
-};
+typedef scanplan::BlockPlan Plan;
+inline bool make_plan(int64_t P, int64_t rows, int64_t cols, Plan* p) { return scanplan::make_block_plan(P, rows, cols, p); }
+inline int64_t stride_grid(int64_t units) { return scanplan::stride_grid(units, LANES, MAX_GRID); }
 
-// false (and nothing defined in *p) when the image has no pixel or too many for an int32 index
-inline bool make_plan(int64_t P, int64_t rows, int64_t cols, Plan* p) {
-  if (P < 1 || rows < 1 || cols < 1) return false;
-  if (rows > MAX_PIXELS / P || cols > MAX_PIXELS / (P * rows)) return false;
-  p->pixels = P * rows * cols;
-  p->blocks = (p->pixels + PIXEL_BLOCK - 1) / PIXEL_BLOCK;
-  p->scan_trips = (p->blocks + SCAN_WIDTH - 1) / SCAN_WIDTH;
-  p->scratch_words = (p->blocks + SCAN_LANE_COUNTS - 1) / SCAN_LANE_COUNTS * SCAN_LANE_COUNTS;
-  p->scratch_bytes = 4 * p->scratch_words;
-  return true;
-}
-
-// workgroups of a striding launch over `units` units of LANES lanes each; 0 when there is nothing to do
-inline int64_t stride_grid(int64_t units) {
-  const int64_t trips = (units + LANES - 1) / LANES;
-  return trips > MAX_GRID ? MAX_GRID : trips;
-}
-
-// ---- the three launches on the host, block by block and lane by lane as the kernels walk them ----
-
-// launch 1: scratch[b] = lit pixels of block b
+// launch 1: scratch[b] = lit pixels of block b; launch 2 is scanplan::host_scan
 inline void host_count(const Plan& p, const uint8_t* lit, uint32_t* scratch) {
-  for (int64_t b = 0; b < p.blocks; ++b) {
-    uint32_t c = 0;
-    for (int lane = 0; lane < LANES; ++lane)
-      for (int j = 0; j < LANE_PIXELS; ++j) {
-        const int64_t q = b * PIXEL_BLOCK + (int64_t)lane * LANE_PIXELS + j;
-        if (q < p.pixels && lit[q]) ++c;
-      }
-    scratch[b] = c;
-  }
-}
-
-// launch 2: an exclusive scan in place, SCAN_WIDTH counts per trip with the carry of the trips before; -> the total
-inline uint64_t host_scan(const Plan& p, uint32_t* scratch) {
-  uint32_t carry = 0;
-  for (int64_t t = 0; t < p.scan_trips; ++t) {
-    uint32_t lane_sum[LANES];
-    for (int lane = 0; lane < LANES; ++lane) {
-      lane_sum[lane] = 0;
-      for (int k = 0; k < SCAN_LANE_COUNTS; ++k) {
-        const int64_t i = t * SCAN_WIDTH + (int64_t)lane * SCAN_LANE_COUNTS + k;
-        if (i < p.blocks) lane_sum[lane] += scratch[i];
-      }
-    }
-    uint32_t before = carry;
-    for (int lane = 0; lane < LANES; ++lane) {
-      uint32_t run = before;
-      for (int k = 0; k < SCAN_LANE_COUNTS; ++k) {
-        const int64_t i = t * SCAN_WIDTH + (int64_t)lane * SCAN_LANE_COUNTS + k;
-        if (i < p.blocks) {
-          const uint32_t c = scratch[i];
-          scratch[i] = run;
-          run += c;
-        }
-      }
-      before += lane_sum[lane];
-    }
-    carry = before;
-  }
-  return carry;
+  scanplan::host_count(p, [lit](int64_t q) { return lit[q] != 0; }, scratch);
 }
 
 // launch 3: the k-th lit pixel of the image goes to out_index[k], k < capacity; nothing at or past capacity is written
 inline void host_write(const Plan& p, const uint8_t* lit, const uint32_t* scratch, int64_t capacity, int32_t* out_index) {
-  for (int64_t b = 0; b < p.blocks; ++b) {
-    int64_t k = scratch[b];
-    for (int lane = 0; lane < LANES; ++lane)
-      for (int j = 0; j < LANE_PIXELS; ++j) {
-        const int64_t q = b * PIXEL_BLOCK + (int64_t)lane * LANE_PIXELS + j;
-        if (q < p.pixels && lit[q]) {
-          if (k < capacity) out_index[k] = (int32_t)q;
-          ++k;
-        }
-      }
-  }
+  scanplan::host_rank(p, [lit](int64_t q) { return lit[q] != 0; }, scratch, [=](int64_t q, int64_t k) {
+    if (k < capacity) out_index[k] = (int32_t)q;
+  });
 }
 
 }  // namespace ubz
