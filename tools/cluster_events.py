@@ -2,13 +2,17 @@
 """Cluster the event products of synthetic labelled events on the device and print the cluster table, largest first.
 
     python tools/cluster_events.py [--events N] [--rows R] [--cols C] [--top K] [--min-pixels M] [--connectivity 4|8] [--by-class]
-                                   [--moments] [--adc-scale S]
+                                   [--moments] [--adc-scale S] [--truth]
 
 Every event goes through WholeViewSegmenter(output="products") and an EventClusterer (ubresnet_amd/clusters.py); nothing leaves
 the device until Clusters.read(), which copies the count and that many table rows.  The model has seeded random weights, so the
 classes mean nothing here; `shower` is the share of class --shower-class among the cluster's pixels.  With --moments a
 ClusterMoments (ubresnet_amd/shapes.py) runs behind the clusterer and the table gains the cluster's charge (summed ADC), the share
-of the shower class in that charge, its length (2 sqrt 3 times the major extent: exact for a uniform line), width and linearity."""
+of the shower class in that charge, its length (2 sqrt 3 times the major extent: exact for a uniform line), width and linearity.
+With --truth the truth of the event is clustered the same way (overlap.truth_products into a second EventClusterer) and a
+ClusterOverlap (ubresnet_amd/overlap.py) matches the predicted clusters against the true ones: beside the table above, per
+predicted cluster, largest first, its purity, the efficiency of its best match and that match, pixel- and charge-weighted, and the
+event's adjusted Rand index.  (Without --by-class both sides cluster the same lit pixels whatever their class, and agree.)"""
 import argparse
 import os
 import sys
@@ -32,6 +36,7 @@ def main():
     ap.add_argument("--capacity", type=int, default=65536)
     ap.add_argument("--moments", action="store_true")
     ap.add_argument("--adc-scale", type=int, default=16)
+    ap.add_argument("--truth", action="store_true")
     a = ap.parse_args()
     import torch
     from ubresnet_amd import clusters, deploy, synthetic
@@ -46,10 +51,16 @@ def main():
     if a.moments:
         from ubresnet_amd import shapes
         cm = shapes.ClusterMoments(cl, adc_scale=a.adc_scale)
+    if a.truth:
+        from ubresnet_amd import overlap
+        cl_true = clusters.EventClusterer(a.planes, a.rows, a.cols, a.classes, a.connectivity, a.by_class, 255, a.capacity, "cuda:0")
+        co = overlap.ClusterOverlap(a.planes, a.rows, a.cols, 4 * a.capacity, None, a.adc_scale, "cuda:0")
     for e in range(a.events):
-        image, _ = synthetic.make_labelled_event(a.planes, a.rows, a.cols, 1000 + 10 * e)
+        image, truth = synthetic.make_labelled_event(a.planes, a.rows, a.cols, 1000 + 10 * e)
         view = torch.from_numpy(image[:, None].copy()).cuda()
         found = cl(seg(view))
+        if a.truth:                                               # launched before anything is read back
+            ov = co(found, cl_true(*overlap.truth_products(torch.from_numpy(truth).cuda(), view)), view)
         shape = cm(found, view).read(min_pixels=a.min_pixels) if cm else None
         tab = shape.clusters if cm else found.read(min_pixels=a.min_pixels)
         order = torch.argsort(tab.pixels, descending=True)[:a.top]
@@ -68,6 +79,22 @@ def main():
                                                                            float(width[i]), float(lin[i]))
             print("  %5d  %6d  %4d..%-4d  %4d..%-4d  %6.3f  %.4f" % (int(tab.plane[i]), int(tab.pixels[i]), r0, r1, c0, c1,
                                                                   float(frac[i, a.shower_class]), float(mean[i])) + more)
+        if a.truth:
+            match = ov.read()
+            sizes, eff_of = match.sizes_a(), {}
+            for weighted in (False, True):
+                eff = match.efficiency(weighted)
+                eff_of[weighted] = dict(zip(eff.cluster.tolist(), eff.value.tolist()))
+            pur = {w: match.purity(w) for w in (False, True)}
+            print("  %d pairs of %d predicted and %d true clusters; adjusted Rand index %.4f" % (len(match), len(sizes), len(match.sizes_b()), match.ari()))
+            print("  cluster  pixels  purity  efficiency  best true  |  by charge: purity  efficiency  best true")
+            for k in sorted(sizes, key=lambda c: -sizes[c])[:a.top]:
+                cells = []
+                for weighted in (False, True):
+                    i = pur[weighted].cluster.tolist().index(k)
+                    best = int(pur[weighted].best[i])
+                    cells += [float(pur[weighted].value[i]), eff_of[weighted].get(best, float("nan")), best]
+                print("  %7d  %6d  %6.3f  %10.3f  %9d  |  %17.3f  %10.3f  %9d" % ((k, sizes[k]) + tuple(cells)))
     return 0
 
 

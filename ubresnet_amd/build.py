@@ -72,6 +72,8 @@ ADDONS = {
                    ["ubr_sat.h", "ubr_cluster_plan.h", "ubr_scan_plan.h", "ubr_wave.h", os.path.join("..", "..", "include", "ubresnet_cluster.h")], "_cluster"),
     "moment": Lib(os.path.join(HERE, "libubresnet_moment.so"), [os.path.join("extra", "ubr_moment.hip")],
                   ["ubr_sat.h", "ubr_moment_plan.h", "ubr_scan_plan.h", "ubr_wave.h", os.path.join("..", "..", "include", "ubresnet_moment.h")], "_moment"),
+    "overlap": Lib(os.path.join(HERE, "libubresnet_overlap.so"), [os.path.join("extra", "ubr_overlap.hip")],
+                   ["ubr_sat.h", "ubr_overlap_plan.h", "ubr_scan_plan.h", "ubr_wave.h", os.path.join("..", "..", "include", "ubresnet_overlap.h")], "_overlap"),
 }
 
 

@@ -1,5 +1,5 @@
 // The wave and workgroup primitives of the event-product libraries (extra/ubr_sparse.hip, ubr_cluster.hip, ubr_moment.hip,
-// ubr_crop.hip, ubr_score.hip): integer sums across a wave, the walk over the distinct keys of a wave, and the count, rank and
+// ubr_crop.hip, ubr_score.hip, ubr_overlap.hip): integer sums across a wave, the walk over the distinct keys of a wave, and the count, rank and
 // scan of a workgroup of 64-lane waves through a few words of LDS -- the device side of the three launches ubr_scan_plan.h plans.
 // Everything is integer arithmetic, so no order of additions is anybody's contract (the fixed-order sums of the loss libraries
 // are ubr_rows.h).  A function that says it holds a barrier is called by every lane of the workgroup, wave-uniformly.  Device
@@ -48,6 +48,17 @@ __device__ __forceinline__ KeyGroup<K> next_key_group(u64& rem, K key, bool acti
   KeyGroup<K> g;
   g.leader = __ffsll((long long)rem) - 1;
   g.key = (K)__shfl((int)key, g.leader);
+  g.member = active && key == g.key;
+  g.lanes = __ballot(g.member);
+  rem &= ~g.lanes;
+  return g;
+}
+
+// the same for a 64-bit key, which travels as two 32-bit halves
+__device__ __forceinline__ KeyGroup<u64> next_key_group(u64& rem, u64 key, bool active) {
+  KeyGroup<u64> g;
+  g.leader = __ffsll((long long)rem) - 1;
+  g.key = ((u64)(unsigned)__shfl((int)(key >> 32), g.leader) << 32) | (unsigned)__shfl((int)key, g.leader);
   g.member = active && key == g.key;
   g.lanes = __ballot(g.member);
   rem &= ~g.lanes;
