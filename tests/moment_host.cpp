@@ -1,16 +1,15 @@
 // The launch plan and the limits of libubresnet_moment.so (ubresnet_amd/csrc/ubr_moment_plan.h, plain C++ for a host compiler) as
 // a stand-alone program, so that tests/test_cpu_moment.py can run it under the host sanitizers:
 //   moment_host P rows cols capacity C [P rows cols capacity C ...]
-// For every image given, and for every image of 1 x 1 x n pixels with n from 1 to a few trips, it checks that the spans of the
-// workgroups tile the trips, that the trips tile the pixels (marking every pixel of every lane slot of every trip in a buffer of
-// exactly `pixels` bytes), and the clear grid.  Then it checks what the plan refuses, the scales it accepts, and the overflow
-// bound over every accepted plane shape with power-of-two sides and at the largest planes.  It prints one line per image,
+// For every image given, and for every image of 1 x 1 x n pixels with n from 1 to a few trips, it checks that the plan's walk is
+// ubr_walk_plan.h's (that the walk tiles the pixels, and the scales it accepts, are tests/walk_host.cpp's to check) and the clear
+// grid.  Then it checks what the plan refuses and the overflow bound over every accepted plane shape with power-of-two sides and
+// at the largest planes.  It prints one line per image,
 // `I P rows cols pixels trips span grid clear_grid`, then `B <worst column over all accepted shapes>`, then `G lanes trip_pixels
 // max_grid slots probes flush_above`, and exits 1 at the first disagreement.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <vector>
 #include "ubr_moment_plan.h"
 
 static int fail(const char* what, int64_t P, int64_t rows, int64_t cols) {
@@ -22,32 +21,14 @@ static int check_image(int64_t P, int64_t rows, int64_t cols, int64_t capacity, 
   ubm::Plan p;
   if (!ubm::make_plan(P, rows, cols, capacity, C, &p)) return fail("make_plan refused", P, rows, cols);
   const int64_t n = P * rows * cols;
-  if (p.pixels != n || p.trips < 1 || (p.trips - 1) * ubm::TRIP_PIXELS >= n || p.trips * ubm::TRIP_PIXELS < n)
-    return fail("trips do not tile the pixels", P, rows, cols);
-  if (p.grid < 1 || p.grid > ubm::MAX_GRID || p.span < 1 || (p.grid - 1) * p.span >= p.trips || p.grid * p.span < p.trips)
-    return fail("spans do not tile the trips", P, rows, cols);
+  const walk::Walk w = walk::make_walk(n);
+  if (p.pixels != n || p.trips != w.trips || p.span != w.span || p.grid != w.grid) return fail("the walk is not the walk plan's", P, rows, cols);
   const int64_t words = (capacity < n ? capacity : n) * (ubm::TABLE_FIXED + C);
   if (p.clear_grid < 1 || p.clear_grid > ubm::MAX_GRID || (p.clear_grid < ubm::MAX_GRID && p.clear_grid * ubm::LANES < words))
     return fail("clear grid", P, rows, cols);
   if (print)
     std::printf("I %lld %lld %lld %lld %lld %lld %lld %lld\n", (long long)P, (long long)rows, (long long)cols, (long long)p.pixels,
                 (long long)p.trips, (long long)p.span, (long long)p.grid, (long long)p.clear_grid);
-  // the kernel's walk: workgroup g, trip t of its span, load u, lane l, pixel j; a pixel at or past `pixels` is not touched
-  std::vector<uint8_t> seen((size_t)n, 0);                         // exactly the pixels: a step outside is the sanitizer's
-  for (int64_t g = 0; g < p.grid; ++g) {
-    const int64_t t0 = g * p.span, t1 = (t0 + p.span < p.trips) ? t0 + p.span : p.trips;
-    if (t0 >= t1) return fail("a workgroup without a trip", P, rows, cols);
-    for (int64_t t = t0; t < t1; ++t)
-      for (int u = 0; u < ubm::TRIP_LOADS; ++u)
-        for (int l = 0; l < ubm::LANES; ++l) {
-          const int64_t q = t * ubm::TRIP_PIXELS + (int64_t)u * ubm::LANES * ubm::LANE_PIXELS + (int64_t)l * ubm::LANE_PIXELS;
-          if (q % ubm::LANE_PIXELS) return fail("a lane's first pixel is not a multiple of four", P, rows, cols);
-          for (int j = 0; j < ubm::LANE_PIXELS; ++j)
-            if (q + j < n && seen[(size_t)(q + j)]++) return fail("a pixel is visited twice", P, rows, cols);
-        }
-  }
-  for (int64_t q = 0; q < n; ++q)
-    if (seen[(size_t)q] != 1) return fail("a pixel is not visited", P, rows, cols);
   return 0;
 }
 
@@ -76,11 +57,6 @@ int main(int argc, char** argv) {
   if (p.trips != 5103 || p.span != 5 || p.grid != 1021 || p.clear_grid != ubm::MAX_GRID) return fail("the plan of the full event", 3, 1008, 3456);
   if (ubm::valid_image(1 << 20, 1 << 20, 1 << 20, &why) || !ubm::valid_image(3, 1008, 3456, &why) || *why != 0)
     return fail("valid_image", 0, 0, 0);
-  for (int s = -2; s <= 600; ++s) {
-    const bool want = s == 1 || s == 2 || s == 4 || s == 8 || s == 16 || s == 32 || s == 64 || s == 128 || s == 256;
-    if (ubm::valid_scale((float)s) != want || ubm::valid_scale((float)s + 0.5f)) return fail("valid_scale", s, 0, 0);
-  }
-  if (ubm::valid_scale(0.5f) || ubm::valid_scale(1.0f / 0.0f) || ubm::valid_scale(0.0f / 0.0f)) return fail("valid_scale", 0, 0, 0);
   // the overflow bound: over every accepted plane of power-of-two sides and the planes next to them
   uint64_t worst = 0;
   for (int64_t rows = 1; rows <= ubm::MAX_ROWS; rows *= 2)

@@ -70,6 +70,50 @@ def adc(shape, seed=5, lit=None):
     return v
 
 
+WALK_PIXELS = 2 * TRIP_PIXELS * 2 + 5     # several trips, an odd count, a ragged last load whose last lane holds one real pixel
+
+
+def walk_case():
+    """(ids int32 [n], label uint8 [n], view float32 [n], n_ids) for n = WALK_PIXELS flat pixels: one case that crosses every branch
+    of the pixel walk the moment and overlap libraries share (csrc/ubr_walk.h).  A wave holds 64 lanes of four consecutive pixels,
+    256 pixels; the waves cycle through four id patterns, each with ids of its own:
+      0  all 64 lanes share one id (one group of 64, one combined round)
+      1  64 distinct ids, one per lane (every lane solo)
+      2  two ids interleaved lane by lane (two groups of 32)
+      3  lanes 0..15 one id; lane 16 two ids, two pixels each (the "mixed" round: four per-pixel rounds for the wave); lanes 17..31
+         no pixel that takes part; lanes 32..47 an id each (solo); lanes 48..63 two ids interleaved, the pixels 1 and 2 of each
+         lane dark (a group whose lanes hold fewer than four pixels)
+    The last load is ragged: lane 0 holds four pixels and lane 1 one, of the same id.  The ADC values cycle through EDGE_ADC (23
+    values, coprime with the 4 pixels of a lane and the 256 of a wave); the labels cycle through 0..3 with a foreign 4 every 11th."""
+    n = WALK_PIXELS
+    lane, wave = (np.arange(n) // 4) % 64, np.arange(n) // 256
+    slot = np.arange(n) % 4
+    base = wave * 100                                             # the ids of a wave are its own: < 100 per wave
+    ids = np.full(n, -1, np.int64)
+    for kind in range(4):
+        w = wave % 4 == kind
+        if kind == 0:
+            ids[w] = base[w]
+        elif kind == 1:
+            ids[w] = base[w] + lane[w]
+        elif kind == 2:
+            ids[w] = base[w] + lane[w] % 2
+        else:
+            ids[w & (lane < 16)] = base[w & (lane < 16)]
+            mixed = w & (lane == 16)
+            ids[mixed] = base[mixed] + 1 + slot[mixed] // 2
+            solo = w & (lane >= 32) & (lane < 48)
+            ids[solo] = base[solo] + lane[solo]
+            pair = w & (lane >= 48) & ((slot == 0) | (slot == 3))
+            ids[pair] = base[pair] + 90 + lane[pair] % 2
+    ids[n - 5:] = base[-1] + 99                                   # the ragged tail: lane 0 whole, lane 1 one pixel
+    label = (np.arange(n) % 4).astype(np.uint8)
+    label[::11] = 4
+    view = EDGE_ADC[np.arange(n) % len(EDGE_ADC)]
+    assert n % 4 == 1 and n > 4 * TRIP_PIXELS and (wave[-1] % 4, lane[-1], slot[-1]) == (0, 1, 0)
+    return ids.astype(np.int32), label, view.astype(np.float32), int(ids.max()) + 1
+
+
 def central(row):
     """the exact central second moments of a table row as Python-int numerators over Q^2: (Q, Q Qrr - Qr^2, Q Qrc - Qr Qc, Q Qcc - Qc^2)"""
     Q, Qr, Qc, Qrr, Qrc, Qcc = (int(v) for v in row[3:9])

@@ -2,9 +2,9 @@
 // ubr_scan_plan.h, plain C++ for a host compiler) as a stand-alone program, so that tests/test_cpu_overlap.py can run it under
 // the host sanitizers:
 //   overlap_host P rows cols slots [P rows cols slots ...]
-// For every image given, and for a ladder of 1 x 1 x n images, it checks that the spans of the workgroups tile the trips, that
-// the trips tile the pixels (marking every pixel of every lane slot in a buffer of exactly `pixels` bytes), the clear grid and
-// the scratch layout.  Then what the plan refuses, the key of a pair, the default slots, and a sequential model of
+// For every image given, and for a ladder of 1 x 1 x n images, it checks that the plan's walk is ubr_walk_plan.h's (that the walk
+// tiles the pixels, and the scales it accepts, are tests/walk_host.cpp's to check), that the pixel blocks of launches 3 to 5 tile
+// the pixels (in a buffer of exactly `pixels` bytes), the clear grid and the scratch layout.  Then what the plan refuses, the key of a pair, the default slots, and a sequential model of
 // insert-then-look-up over shuffled insertion orders: the (key -> sums) content and the set of occupied slots are the same for
 // every order, and with a table too small every key is found by every later look-up or by none.  It prints one line per image,
 // `I P rows cols pixels trips span grid clear_grid blocks scratch_bytes`, then `G lanes trip_pixels max_grid lds_slots lds_probes
@@ -27,10 +27,8 @@ static int check_image(int64_t P, int64_t rows, int64_t cols, int64_t slots, boo
   ubh::Plan p;
   if (!ubh::make_plan(P, rows, cols, slots, &p)) return fail("make_plan refused", P, rows, cols);
   const int64_t n = P * rows * cols;
-  if (p.pixels != n || p.trips < 1 || (p.trips - 1) * ubh::TRIP_PIXELS >= n || p.trips * ubh::TRIP_PIXELS < n)
-    return fail("trips do not tile the pixels", P, rows, cols);
-  if (p.grid < 1 || p.grid > ubh::MAX_GRID || p.span < 1 || (p.grid - 1) * p.span >= p.trips || p.grid * p.span < p.trips)
-    return fail("spans do not tile the trips", P, rows, cols);
+  const walk::Walk w = walk::make_walk(n);
+  if (p.pixels != n || p.trips != w.trips || p.span != w.span || p.grid != w.grid) return fail("the walk is not the walk plan's", P, rows, cols);
   if (p.clear_grid < 1 || p.clear_grid > ubh::MAX_GRID || (p.clear_grid < ubh::MAX_GRID && p.clear_grid * ubh::LANES < slots))
     return fail("clear grid", P, rows, cols);
   scanplan::BlockPlan b;
@@ -44,30 +42,16 @@ static int check_image(int64_t P, int64_t rows, int64_t cols, int64_t slots, boo
     std::printf("I %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld\n", (long long)P, (long long)rows, (long long)cols, (long long)p.pixels,
                 (long long)p.trips, (long long)p.span, (long long)p.grid, (long long)p.clear_grid, (long long)b.blocks,
                 (long long)p.scratch_bytes);
-  // the insert's walk: workgroup g, trip t of its span, load u, lane l, pixel j; a pixel at or past `pixels` is not touched
+  // the count and number passes: block b, lane l, pixel j; a pixel at or past `pixels` is not touched
   std::vector<uint8_t> seen((size_t)n, 0);                         // exactly the pixels: a step outside is the sanitizer's
-  for (int64_t g = 0; g < p.grid; ++g) {
-    const int64_t t0 = g * p.span, t1 = (t0 + p.span < p.trips) ? t0 + p.span : p.trips;
-    if (t0 >= t1) return fail("a workgroup without a trip", P, rows, cols);
-    for (int64_t t = t0; t < t1; ++t)
-      for (int u = 0; u < ubh::TRIP_LOADS; ++u)
-        for (int l = 0; l < ubh::LANES; ++l) {
-          const int64_t q = t * ubh::TRIP_PIXELS + (int64_t)u * ubh::LANES * ubh::LANE_PIXELS + (int64_t)l * ubh::LANE_PIXELS;
-          for (int j = 0; j < ubh::LANE_PIXELS; ++j)
-            if (q + j < n && seen[(size_t)(q + j)]++) return fail("a pixel is visited twice", P, rows, cols);
-        }
-  }
-  for (int64_t q = 0; q < n; ++q)
-    if (seen[(size_t)q] != 1) return fail("a pixel is not visited", P, rows, cols);
-  // the count and number passes: block b, lane l, pixel j
   for (int64_t blk = 0; blk < b.blocks; ++blk)
     for (int l = 0; l < scanplan::LANES; ++l)
       for (int j = 0; j < scanplan::LANE_PIXELS; ++j) {
         const int64_t q = scanplan::lane_pixel(blk, l, j);
-        if (q < n && seen[(size_t)q]++ != 1) return fail("the blocks do not tile the pixels", P, rows, cols);
+        if (q < n && seen[(size_t)q]++) return fail("the blocks do not tile the pixels", P, rows, cols);
       }
   for (int64_t q = 0; q < n; ++q)
-    if (seen[(size_t)q] != 2) return fail("a pixel is in no block", P, rows, cols);
+    if (seen[(size_t)q] != 1) return fail("a pixel is in no block", P, rows, cols);
   return 0;
 }
 
@@ -178,10 +162,6 @@ int main(int argc, char** argv) {
   if (p.trips != 5103 || p.span != 5 || p.grid != 1021 || p.clear_grid != ubh::MAX_GRID || p.log2_slots != 18 || p.probes != 128)
     return fail("the plan of the full event", 3, 1008, 3456);
   if (ubh::valid_image(1 << 20, 1 << 20, 1 << 20, &why) || !ubh::valid_image(3, 1008, 3456, &why) || *why != 0) return fail("valid_image", 0, 0, 0);
-  for (int s = -2; s <= 600; ++s) {
-    const bool want = s == 1 || s == 2 || s == 4 || s == 8 || s == 16 || s == 32 || s == 64 || s == 128 || s == 256;
-    if (ubh::valid_scale((float)s) != want || ubh::valid_scale((float)s + 0.5f)) return fail("valid_scale", s, 0, 0);
-  }
   // the key: never 0 for a pair that takes part, 0 for two nones, every negative id is none, the largest ids fit
   if (ubh::pair_key(-1, -1) != 0 || ubh::pair_key(-7, INT32_MIN) != 0 || ubh::pair_key(0, -1) != ((uint64_t)1 << 32) || ubh::pair_key(-1, 0) != 1 ||
       ubh::pair_key(-5, 3) != ubh::pair_key(-1, 3) || ubh::pair_key(INT32_MAX, INT32_MAX) != (((uint64_t)1 << 31) << 32 | ((uint64_t)1 << 31)) ||

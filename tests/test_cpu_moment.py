@@ -3,7 +3,8 @@ double loop; the weight rule on its edge values; libubresnet_moment.so's header 
 library agree on entry points and constants; the library stands alone and exports its binding's symbols; the ADDONS entry, its
 include closure and a forced build; a missing library is a RuntimeError; every argument refusal returns UBM_EINVAL with a message
 before any HIP call; the overflow bound and the launch plan as a stand-alone program under the host sanitizers
-(tests/moment_host.cpp); ShapeTable and the refusals of the Python surface that need no device."""
+(tests/moment_host.cpp), and the pixel walk and the weight rule it shares with ClusterOverlap as another (tests/walk_host.cpp);
+ShapeTable and the refusals of the Python surface that need no device."""
 import importlib
 import importlib.util
 import math
@@ -177,12 +178,18 @@ def test_library_stands_alone_and_exports_exactly_its_bindings_symbols():
     code = re.sub(r"//.*", "", src)
     assert "asm" not in code and "Malloc" not in src and "hipFree" not in src and "Synchronize" not in src, "no allocation, free or sync"
     assert "cooperative" not in code.lower() and "while (true)" not in code and "__threadfence" not in code
-    # the plan compiles without HIP: it reaches the shared scan plan and nothing else, and neither file names HIP outside comments
-    plan, shared = os.path.join(B.CSRC, "ubr_moment_plan.h"), os.path.join(B.CSRC, "ubr_scan_plan.h")
-    assert _include_closure([plan]) == {os.path.realpath(shared)} and _include_closure([shared]) == set()
-    for f in (plan, shared):
+    # the plan compiles without HIP: it reaches the shared scan plan and walk plan and nothing else, and none of the files names HIP
+    # outside comments
+    plan, shared, walk = (os.path.join(B.CSRC, f) for f in ("ubr_moment_plan.h", "ubr_scan_plan.h", "ubr_walk_plan.h"))
+    assert _include_closure([plan]) == {os.path.realpath(shared), os.path.realpath(walk)}
+    assert _include_closure([shared]) == set() and _include_closure([walk]) == set()
+    for f in (plan, shared, walk):
         assert "hip" not in re.sub(r"//.*", "", open(f).read()).lower(), f
-    assert re.findall(r"#\s*include\s*<([^>]+)>", open(plan).read() + open(shared).read()) == ["stdint.h"]
+    assert re.findall(r"#\s*include\s*<([^>]+)>", open(plan).read() + open(shared).read() + open(walk).read()) == ["stdint.h"] * 2
+    # the weight rule is host and device code: it reaches the walk plan alone, and HIP only behind its __HIPCC__ guard
+    rule = os.path.join(B.CSRC, "ubr_adc_rule.h")
+    assert _include_closure([rule]) == {os.path.realpath(walk)} and re.findall(r"#\s*include\s*<([^>]+)>", open(rule).read()) == ["stdint.h", "string.h"]
+    assert '#include "../ubr_walk.h"' in src and '#include "../ubr_adc_rule.h"' in src and "weight_of(float" not in src
 
 
 def test_a_missing_library_is_a_runtime_error(monkeypatch):
@@ -311,8 +318,8 @@ def test_moments_refusals_precede_any_hip_call(name):
 # ------------------------------------------------------------------------------------------------------------------------
 def test_plan_and_overflow_bound_as_a_program_under_the_host_sanitizers(tmp_path):
     """tests/moment_host.cpp has its own main and includes ubr_moment_plan.h; built with -fsanitize=address,undefined and run as a
-    process of its own over every view of the GPU tests: the spans tile the trips and the lane slots tile the pixels in a buffer
-    of exactly the pixels, what the plan refuses, the scales it accepts, and the overflow bound at the largest accepted shape"""
+    process of its own over every view of the GPU tests: the plan's walk is the shared walk plan's (which the next test holds), the
+    clear grid, what the plan refuses, and the overflow bound at the largest accepted shape"""
     exe = str(tmp_path / "moment_host")
     r = subprocess.run([H.cc(plus=True), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Werror",
                         "-I", os.path.join(REPO, "ubresnet_amd", "csrc"), os.path.join(REPO, "tests", "moment_host.cpp"), "-o", exe],
@@ -335,6 +342,46 @@ def test_plan_and_overflow_bound_as_a_program_under_the_host_sanitizers(tmp_path
     # the closed form of the GPU test's largest plane stays inside it
     assert 65535 * 1024 * (4095 * 4096 * 8191 // 6) <= bound
     assert lines[-1].split() == ["G", str(M.LANES), str(M.TRIP_PIXELS), str(M.MAX_GRID), str(M.SLOTS), "4", str(M.SLOTS // 2)]
+
+
+def test_shared_walk_and_weight_rule_as_a_program_under_the_host_sanitizers(tmp_path):
+    """tests/walk_host.cpp has its own main and includes ubr_walk_plan.h and ubr_adc_rule.h, the walk and the weight rule that the
+    moment and overlap libraries share; built with -fsanitize=address,undefined and -ffp-contract=off and run as a process of its
+    own.  (a) the spans tile the trips and the lane slots tile the pixels in a buffer of exactly the pixels, from 1 pixel to a few
+    trips past MAX_GRID * TRIP_PIXELS and at the full event; (b) the weight and its class of every edge ADC value and of every
+    65521st float bit pattern, at every valid scale, bit for bit against moment_ref.weight"""
+    exe = str(tmp_path / "walk_host")
+    r = subprocess.run([H.cc(plus=True), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                        "-Wall", "-Werror", "-I", os.path.join(REPO, "ubresnet_amd", "csrc"), os.path.join(REPO, "tests", "walk_host.cpp"), "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    stride, edge = 65521, R.EDGE_ADC.view(np.uint32)
+    p = subprocess.run([exe, str(stride)] + ["%08x" % b for b in edge.tolist()], capture_output=True, text=True)
+    assert p.returncode == 0, "sanitizer or program failure:\n" + p.stderr[-2000:]
+    lines = p.stdout.strip().split("\n")
+    # (a)
+    walks = {int(l.split()[1]): [int(v) for v in l.split()[2:]] for l in lines if l.startswith("W ")}
+    full = M.MAX_GRID * M.TRIP_PIXELS
+    assert set(walks) >= {1, 3 * M.TRIP_PIXELS + 1, full - 1, full, full + 1, full + 3 * M.TRIP_PIXELS + 5, 3 * 1008 * 3456}
+    for n, (trips, span, grid) in walks.items():
+        assert trips == -(-n // M.TRIP_PIXELS) and span == -(-trips // min(trips, M.MAX_GRID)) and grid == -(-trips // span) <= M.MAX_GRID
+    assert walks[full] == [1024, 1, 1024] and walks[full + 1] == [1025, 2, 513] and walks[3 * 1008 * 3456] == [5103, 5, 1021]
+    # (b)
+    def classes(values, scale):
+        w, clipped, odd = R.weight(values, scale)
+        return w, np.where(odd, 2, np.where(clipped, 1, 0))
+    scales = [1, 2, 4, 8, 16, 32, 64, 128, 256]
+    sweep = np.arange(0, 2 ** 32, stride, dtype=np.uint64).astype(np.uint32)
+    assert [int(l.split()[1]) for l in lines if l.startswith("S ")] == scales and len(sweep) > 65000
+    for scale in scales:
+        got = [[int(t, 16) if i == 0 else int(t) for i, t in enumerate(l.split()[2:])] for l in lines if l.startswith("E %d " % scale)]
+        w, cls = classes(R.EDGE_ADC, scale)
+        assert got == [[int(b), int(x), int(c)] for b, x, c in zip(edge, w, cls)], scale
+        at = lines.index("S %d %d" % (scale, stride))
+        packed = np.array([int(t, 16) for t in lines[at + 1].split()], np.int64)
+        w, cls = classes(sweep.view(f32), scale)
+        assert len(packed) == len(sweep) and np.array_equal(packed >> 2, w) and np.array_equal(packed & 3, cls), scale
+        assert set(cls.tolist()) == {0, 1, 2} and (w[cls == 0] > 0).any()
 
 
 # ------------------------------------------------------------------------------------------------------------------------

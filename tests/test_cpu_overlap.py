@@ -110,10 +110,11 @@ def test_library_stands_alone_and_exports_exactly_its_bindings_symbols():
     assert "asm" not in code and "Malloc" not in src and "hipFree" not in src and "Synchronize" not in src, "no allocation, free or sync"
     assert "cooperative" not in code.lower() and "while (true)" not in code and "__threadfence" not in code
     assert len(re.findall(r"<<<", code)) == 5, "five launches"
-    # the plan compiles without HIP: it reaches the shared scan plan and nothing else, and neither file names HIP outside comments
-    shared = os.path.join(B.CSRC, "ubr_scan_plan.h")
-    assert _include_closure([PLAN]) == {os.path.realpath(shared)}
+    # the plan compiles without HIP: it reaches the shared scan plan and walk plan and nothing else, and names no HIP outside comments
+    shared, walk = os.path.join(B.CSRC, "ubr_scan_plan.h"), os.path.join(B.CSRC, "ubr_walk_plan.h")
+    assert _include_closure([PLAN]) == {os.path.realpath(shared), os.path.realpath(walk)}
     assert "hip" not in re.sub(r"//.*", "", open(PLAN).read()).lower()
+    assert '#include "../ubr_walk.h"' in src and '#include "../ubr_adc_rule.h"' in src and "weight_of(float" not in src
     assert re.findall(r"#\s*include\s*<([^>]+)>", open(PLAN).read()) == []
     host = os.path.join(REPO, "tests", "overlap_host.cpp")
     assert re.findall(r'#\s*include\s*"([^"]+)"', open(host).read()) == ["ubr_overlap_plan.h", "ubr_scan_plan.h"]

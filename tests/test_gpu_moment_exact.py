@@ -4,7 +4,7 @@ tests/cluster_ref.py (connectivity 8), with `checker` and `random-41` also 4-con
 of its own, so that a workgroup meets far more clusters than its LDS table holds (the direct path and the flush of a full table).
 Then: the contended case (all lit over many workgroups); a view of several trips per workgroup; dark and foreign pixels; capacity
 below the count; stored, not added; the largest accepted plane in closed form; two calls and two streams; a captured graph;
-sparse input."""
+sparse input; one hand-made case across every branch of the pixel walk shared with ClusterOverlap; views below four pixels."""
 import numpy as np
 import pytest
 import torch
@@ -267,3 +267,36 @@ def test_a_sparse_event_equals_the_dense_view():
         got, _, _, _, _, _ = _run(label, event, cm=cm, cl=cl)
         assert got.tobytes() == dense.tobytes()
     assert cm._dense is not None and cm._dense.shape == (shape[0], 1, shape[1], shape[2])
+
+
+def _raw(ids, label, view, shape, capacity, count):
+    """the whole table buffer after ubm_moments on maps no clusterer made, through the binding alone"""
+    dev = [torch.from_numpy(np.ascontiguousarray(x).reshape(shape)).cuda() for x in (ids, label, view)]
+    table = torch.full((capacity, R.TABLE_FIXED + CR.C4), SENTINEL, dtype=torch.int64, device="cuda")
+    n = torch.tensor([count], dtype=torch.int64, device="cuda")
+    M.moments(dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), CR.C4, SCALE, table.data_ptr(), capacity, n.data_ptr(), *shape)
+    torch.cuda.synchronize()
+    return table.cpu().numpy()
+
+
+def test_one_case_across_every_branch_of_the_shared_walk():
+    """moment_ref.walk_case(): 2 * TRIP_PIXELS * 2 + 5 = 8197 pixels whose waves hold one id in all 64 lanes, 64 solo ids, two ids
+    interleaved, a lane of two ids (the mixed round), lanes without a pixel, and a ragged last load, with the ADC edge values on
+    them; tests/test_gpu_overlap_exact.py runs the same pixels through the other library.  ubm_moments takes at most 4096 columns,
+    so the 8197 pixels are a 1 x 7 x 1171 view here: the walk is over the flat pixel index and is the 1 x 1 x 8197 view's"""
+    ids, label, view, n_ids = R.walk_case()
+    shape = (1, 7, 1171)
+    assert ids.size == R.WALK_PIXELS == 7 * 1171 == 2 * R.TRIP_PIXELS * 2 + 5
+    got = _raw(ids, label, view, shape, n_ids + 3, n_ids)
+    ref = _same(got, ids, n_ids, label.reshape(shape), view.reshape(shape), n_ids + 3)
+    assert (ref[:, :3].sum(0) > 0).all() and (got[n_ids:] == SENTINEL).all(), "weighted, clipped and odd pixels; the canary rows"
+
+
+@pytest.mark.parametrize("n", [2, 3])
+def test_a_view_below_four_pixels_takes_the_tail_of_the_id_load_alone(n):
+    """n % 4 == 2 and 3 at n < 4 (n = 1 is the `1x1x1` view of test_patterns_on_every_view_bit_for_bit): no aligned 16-byte load"""
+    ids, label = np.arange(n, dtype=np.int32) % 2, np.arange(n, dtype=np.uint8) % CR.C4
+    view = np.array([4095.9375, 1e30, 2.5], np.float32)[:n]
+    got = _raw(ids, label, view, (1, 1, n), 5, 2)
+    ref = _same(got, ids, 2, label.reshape(1, 1, n), view.reshape(1, 1, n), 5)
+    assert ref[:, 0].tolist() == [n - 1, 1] and ref[:, 1].tolist() == [0, 1]

@@ -5,7 +5,8 @@ against itself; `checker` and `random-41` 4-connected, where nearly every lit pi
 far more pairs than its LDS table holds (the direct path and the flush of a full table); the contended case (all lit over many
 workgroups); a ragged view of several trips per workgroup.  Then: one and both maps without a cluster; raw maps no clusterer made;
 capacity below the count; a table of 64 slots against thousands of pairs (the bounded refusal); two calls and two streams; a
-captured graph.  tests/test_cpu_overlap.py shows that no insertion order can drop a pair in any case but the 64-slot one, so a
+captured graph; one hand-made case across every branch of the pixel walk shared with ClusterMoments; views below four pixels.
+tests/test_cpu_overlap.py shows that no insertion order can drop a pair in any case but the 64-slot one, so a
 nonzero status[0] here is a bug."""
 import numpy as np
 import pytest
@@ -275,3 +276,41 @@ def test_a_captured_graph_replayed_twice_on_changed_inputs():
     assert seen[0] == seen[2] != seen[1]
     eager, _, _, _, _ = _run(a2, b2, adc2, capacity)
     assert eager.tobytes() == seen[2]
+
+
+def _no_drop(a, b, slots):
+    """the condition of tests/test_cpu_overlap.py for a case built here: no insertion order can drop a pair"""
+    keys = np.unique(R.keys_of(a, b))
+    held, dropped = R.occupied(keys[keys != 0].tolist(), slots)
+    assert not dropped and R.longest_run(held, slots) < R.probes(slots)
+
+
+def test_one_case_across_every_branch_of_the_shared_walk():
+    """moment_ref.walk_case() as a 1 x 1 x 8197 view, the pixels tests/test_gpu_moment_exact.py runs through the other library: map
+    a is its id map, map b halves the ids (so a pair of b holds two of a where the wave has both) and is none on every fourth lane
+    of the interleaved waves; with and without the view"""
+    ids, _, view, _ = MR.walk_case()
+    n = ids.size
+    shape = (1, 1, n)
+    assert n == MR.WALK_PIXELS == 2 * R.TRIP_PIXELS * 2 + 5
+    lane, wave = (np.arange(n) // 4) % 64, np.arange(n) // 256
+    other = np.where(ids >= 0, ids // 2, -1).astype(np.int32)
+    other[(wave % 4 == 2) & (lane % 4 == 3)] = -1
+    _no_drop(ids, other, R.default_slots(n))
+    a, b = torch.from_numpy(ids.reshape(shape)).cuda(), torch.from_numpy(other.reshape(shape)).cuda()
+    for adc in (view.reshape(shape), None):
+        got, count, status, _, _ = _run(a, b, adc, n)
+        ref = _same(got, count, status, a, b, adc, n)
+        assert (ref[:, 1] == -1).any() and ref[-1, 2:4].tolist() == [n - 5, 5], "pairs with a none side; the ragged tail is a pair"
+
+
+@pytest.mark.parametrize("n", [2, 3])
+def test_a_view_below_four_pixels_takes_the_tail_of_the_id_load_alone(n):
+    """n % 4 == 2 and 3 at n < 4 (n = 1 is the `1x1x1` view of test_patterns_on_every_view_bit_for_bit): no aligned 16-byte load"""
+    na, nb = np.array([[[7, 7, -1]]], np.int32)[:, :, :n], np.array([[[-1, 3, 3]]], np.int32)[:, :, :n]
+    adc = np.array([[[4095.9375, 1e30, 2.5]]], np.float32)[:, :, :n]
+    _no_drop(na, nb, 64)
+    a, b = torch.from_numpy(np.ascontiguousarray(na)).cuda(), torch.from_numpy(np.ascontiguousarray(nb)).cuda()
+    got, count, status, _, _ = _run(a, b, np.ascontiguousarray(adc), 4, slots=64)
+    ref = _same(got, count, status, a, b, adc, 4)
+    assert ref[:, :4].tolist() == [[7, -1, 0, 1], [7, 3, 1, 1], [-1, 3, 2, 1]][:n]

@@ -1,18 +1,22 @@
 // libubresnet_moment.so: per-cluster charge and shape (include/ubresnet_moment.h).  It links against none of the other libraries
-// and shares ubr_sat.h with them; the launches are plain <<<>>> on the caller's stream.  Trip, grid, span, limits and the overflow
-// bound come from ../ubr_moment_plan.h, which tests/moment_host.cpp runs on the host; the key walk and the wave sums from
-// ../ubr_wave.h.
+// and shares ubr_sat.h with them; the launches are plain <<<>>> on the caller's stream.  Limits, the clear grid and the overflow
+// bound come from ../ubr_moment_plan.h, which tests/moment_host.cpp runs on the host; trip, grid and span from ../ubr_walk_plan.h
+// (tests/walk_host.cpp); the loads, the wave round and the trip loop from ../ubr_walk.h, the weight of a pixel from
+// ../ubr_adc_rule.h, the wave sums from ../ubr_wave.h.  libubresnet_overlap.so walks the pixels with the same three headers.
 //
 // Loops and their bounds ("ClusterMoments"):
-//   the trip loop of a workgroup runs over the host-computed span; the clear strides over a length read from the device
-//   a wave round ends after one trip per distinct cluster among its lanes: each trip clears at least one bit of `rem`
+//   the trip loop of a workgroup (walk::trip_loop, ubr_walk.h) runs over the host-computed span; the clear strides over a length
+//     read from the device
+//   a wave round (walk::wave_round, ubr_walk.h) ends after one trip per distinct cluster among its lanes: each trip clears at
+//     least one bit of `rem`
 //   find_slot makes at most PROBES probes
 // No loop reads a word to wait for another workgroup's store.
 #include <hip/hip_runtime.h>
 #include "../../../include/ubresnet_moment.h"
 #include "../ubr_moment_plan.h"
+#include "../ubr_adc_rule.h"
 #include "../ubr_sat.h"
-#include "../ubr_wave.h"
+#include "../ubr_walk.h"
 
 #define UBM_VERSION 1
 
@@ -31,7 +35,6 @@ namespace {
 
 typedef unsigned long long u64;
 constexpr int SLOT_WORDS = ubm::SLOT_WORDS;
-constexpr int LOAD_PIXELS = ubm::LANES * ubm::LANE_PIXELS;     // pixels of one load of the workgroup
 
 struct MomK {
   const int32_t* ids;
@@ -54,22 +57,10 @@ __global__ __launch_bounds__(UBM_LANES) void clear_kernel(u64* __restrict__ tabl
   for (u64 i = (u64)blockIdx.x * UBM_LANES + threadIdx.x; i < n; i += (u64)gridDim.x * UBM_LANES) table[i] = 0ull;
 }
 
-// The weight of an ADC value and its count word (weighted | clipped << COUNT_BITS | odd << 2 COUNT_BITS).  The sign and NaN
-// tests read the bits, so that they do not depend on how the float unit treats a subnormal; scale > 0, so t < 0 iff v < 0.
-__device__ __forceinline__ unsigned weight_of(float v, float scale, unsigned* cnt) {
-  const unsigned bits = __float_as_uint(v), mag = bits & 0x7FFFFFFFu;
-  if (mag > 0x7F800000u || ((bits >> 31) != 0u && mag != 0u)) {   // NaN, or below zero
-    *cnt = 1u << (2 * ubm::COUNT_BITS);
-    return 0u;
-  }
-  const float t = v * scale;                                      // exact: scale is a power of two
-  if (t > (float)UBM_MAX_WEIGHT) {
-    *cnt = 1u | (1u << ubm::COUNT_BITS);
-    return (unsigned)UBM_MAX_WEIGHT;
-  }
-  const unsigned w = (unsigned)__builtin_rintf(t);                // ties to even
-  *cnt = w != 0u ? 1u : 0u;
-  return w;
+// the count word of a weighed pixel: weighted | clipped << COUNT_BITS | odd << 2 COUNT_BITS
+__device__ __forceinline__ unsigned count_word(const adc::Weight& r) {
+  if (r.cls == adc::PLAIN) return r.w != 0u ? 1u : 0u;
+  return r.cls == adc::ODD ? 1u << (2 * ubm::COUNT_BITS) : 1u | (1u << ubm::COUNT_BITS);
 }
 
 // The LDS table of a workgroup: SLOTS slots of SLOT_WORDS sums, keyed by the cluster number (-1: free).  A free slot holds zeros.
@@ -118,21 +109,12 @@ __device__ __forceinline__ void push_sums(const Lds& s, const MomK& a, int slot,
 }
 
 // One wave round: every lane brings the sums `m` of those of its four pixels that `pm` names, all of cluster `key` (-1: none).
-// The lanes that share a cluster are found by ballot and summed across the wave, and the first of them sends the sums on; a lane
-// alone with its cluster sends its own after the loop, together with the other such lanes.  w[j] is 0 for a pixel that adds no
-// charge, and lab[j] < C wherever w[j] != 0.
+// The lanes that share a cluster are summed across the wave, and the first of them sends the sums on; a lane alone with its
+// cluster sends its own (walk::wave_round).  w[j] is 0 for a pixel that adds no charge, and lab[j] < C wherever w[j] != 0.
 __device__ __forceinline__ void wave_round(const Lds& s, const MomK& a, int key, unsigned pm, const Sums& m, const unsigned (&w)[4],
                                            const unsigned (&lab)[4]) {
-  const int lane = threadIdx.x & 63;
   const bool active = key >= 0 && (m.cnt | m.q) != 0u;            // a pixel of weight 0 that is neither clipped nor odd adds nothing
-  u64 rem = __ballot(active);
-  bool solo = false;
-  while (rem != 0ull) {                                           // wave-uniform: one trip per distinct cluster among the active lanes
-    const wv::KeyGroup<int> g = wv::next_key_group(rem, key, active);
-    if (__popcll(g.lanes) == 1) {
-      solo = solo || lane == g.leader;
-      continue;
-    }
+  walk::wave_round(key, active, [&](const wv::KeyGroup<int>& g, int lane) {
     Sums t;
     t.cnt = wv::sum_all(g.member ? m.cnt : 0u);
     t.q = wv::sum_all(g.member ? m.q : 0u);
@@ -155,14 +137,13 @@ __device__ __forceinline__ void wave_round(const Lds& s, const MomK& a, int key,
         if (lane == g.leader) push(s, a, slot, g.key, UBM_TABLE_FIXED + c, (u64)qc);
       }
     }
-  }
-  if (solo) {
+  }, [&] {
     const int slot = find_slot(s, key);
     push_sums(s, a, slot, key, m);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (((pm >> j) & 1u) && w[j] != 0u) push(s, a, slot, key, UBM_TABLE_FIXED + (int)lab[j], (u64)w[j]);
-  }
+  });
 }
 
 // the four pixels q .. q + 3 of a lane, whose cluster numbers are k4
@@ -204,7 +185,9 @@ __device__ __forceinline__ void lane_pixels(const Lds& s, const MomK& a, unsigne
       if (lab[j] >= (unsigned)a.C) {                              // no class of the table: odd, and nothing else
         cnt[j] = 1u << (2 * ubm::COUNT_BITS);
       } else {
-        w[j] = weight_of(v[j], a.scale, &cnt[j]);
+        const adc::Weight r = adc::weight_of(v[j], a.scale);
+        w[j] = r.w;
+        cnt[j] = count_word(r);
       }
       if (first < 0) first = k[j];
       else mixed = mixed || k[j] != first;
@@ -259,32 +242,8 @@ __global__ __launch_bounds__(UBM_LANES) void moment_kernel(const MomK a) {
   __syncthreads();
   u64 nrows = *a.count;
   if (nrows > a.capacity) nrows = a.capacity;
-  const unsigned t0 = blockIdx.x * a.span;
-  unsigned t1 = t0 + a.span;
-  if (t1 > a.trips) t1 = a.trips;
-  for (unsigned t = t0; t < t1; ++t) {                            // workgroup-uniform
-    const unsigned q0 = t * (unsigned)UBM_TRIP_PIXELS + threadIdx.x * 4u;   // < 2^31 + TRIP_PIXELS
-    int4 k4[ubm::TRIP_LOADS];
-#pragma unroll
-    for (int u = 0; u < ubm::TRIP_LOADS; ++u) {
-      const unsigned q = q0 + (unsigned)u * LOAD_PIXELS;
-      if (q + 3u < a.pixels) {
-        k4[u] = *(const int4*)(a.ids + q);                        // ids is 16-byte aligned and q a multiple of four
-      } else {
-        k4[u].x = q < a.pixels ? a.ids[q] : -1;
-        k4[u].y = q + 1u < a.pixels ? a.ids[q + 1u] : -1;
-        k4[u].z = q + 2u < a.pixels ? a.ids[q + 2u] : -1;
-        k4[u].w = -1;                                             // q + 3 >= pixels
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < ubm::TRIP_LOADS; ++u) lane_pixels(s, a, q0 + (unsigned)u * LOAD_PIXELS, k4[u], nrows);
-    __syncthreads();
-    const unsigned used = s_used;
-    __syncthreads();                                              // nobody claims a slot of the next trip before everybody has read
-    if (used > (unsigned)ubm::FLUSH_ABOVE) flush(s, a);           // workgroup-uniform
-  }
-  flush(s, a);
+  walk::trip_loop(a.trips, a.span, &s_used, (unsigned)ubm::FLUSH_ABOVE, [&](unsigned q) { return walk::load_ids(a.ids, q, a.pixels); },
+                  [&](unsigned q, const int4& k4) { lane_pixels(s, a, q, k4, nrows); }, [&] { flush(s, a); });
 }
 
 }  // namespace

@@ -1,19 +1,24 @@
 // libubresnet_overlap.so: the pair table of two id maps (include/ubresnet_overlap.h).  It links against none of the other
-// libraries and shares ubr_sat.h with them; the launches are plain <<<>>> on the caller's stream.  Trip, grids, span, scratch
+// libraries and shares ubr_sat.h with them; the launches are plain <<<>>> on the caller's stream.  The clear grid, the scratch
 // layout, the pair key, its home slot and the probe limit come from ../ubr_overlap_plan.h, which tests/overlap_host.cpp runs on
-// the host; the key walk, the wave sums and the count / scan / rank of the numbering from ../ubr_wave.h.
+// the host; trip, grid and span from ../ubr_walk_plan.h (tests/walk_host.cpp); the loads, the wave round and the trip loop of
+// the insert from ../ubr_walk.h, the weight of a pixel from ../ubr_adc_rule.h -- libubresnet_moment.so walks the pixels with the
+// same three headers -- and the wave sums and the count / scan / rank of the numbering from ../ubr_wave.h.
 //
 // Loops and their bounds ("ClusterOverlap"):
-//   the trip loop of a workgroup runs over the host-computed span; the clear strides over the host-given slots
-//   a wave round ends after one trip per distinct pair among its lanes: each trip clears at least one bit of `rem`
+//   the trip loop of a workgroup (walk::trip_loop, ubr_walk.h) runs over the host-computed span; the clear strides over the
+//     host-given slots
+//   a wave round (walk::wave_round, ubr_walk.h) ends after one trip per distinct pair among its lanes: each trip clears at
+//     least one bit of `rem`
 //   lds_slot makes at most LDS_PROBES probes; claim_slot and find_slot at most `probes` = min(slots, 128)
 //   the scan makes the host-computed trips of ubr_scan_plan.h
 // No loop reads a word to wait for another workgroup's store.
 #include <hip/hip_runtime.h>
 #include "../../../include/ubresnet_overlap.h"
 #include "../ubr_overlap_plan.h"
+#include "../ubr_adc_rule.h"
 #include "../ubr_sat.h"
-#include "../ubr_wave.h"
+#include "../ubr_walk.h"
 
 #define UBH_VERSION 1
 
@@ -33,7 +38,6 @@ namespace {
 
 typedef unsigned long long u64;
 constexpr int WAVES = ubh::LANES / ubh::WAVE;
-constexpr int LOAD_PIXELS = ubh::LANES * ubh::LANE_PIXELS;     // pixels of one load of the workgroup
 constexpr unsigned COUNT_MASK = (1u << ubh::COUNT_BITS) - 1u;
 
 // a slot in scratch: {key, first, pixels, weighted, Q}
@@ -114,16 +118,6 @@ __device__ __forceinline__ const u64* find_slot(const u64* __restrict__ slot, u6
 // ---------------------------------------------------------------------------------------------------------------------------
 // launch 2: insert
 // ---------------------------------------------------------------------------------------------------------------------------
-// the weight of an ADC value: the rule of ubresnet_moment.h.  The sign and NaN tests read the bits, so that they do not depend on
-// how the float unit treats a subnormal; scale > 0, so t < 0 iff v < 0.
-__device__ __forceinline__ unsigned weight_of(float v, float scale) {
-  const unsigned bits = __float_as_uint(v), mag = bits & 0x7FFFFFFFu;
-  if (mag > 0x7F800000u || ((bits >> 31) != 0u && mag != 0u)) return 0u;   // NaN, or below zero
-  const float t = v * scale;                                      // exact: scale is a power of two
-  if (t > (float)UBH_MAX_WEIGHT) return (unsigned)UBH_MAX_WEIGHT;
-  return (unsigned)__builtin_rintf(t);                            // ties to even
-}
-
 // the key of the pair of one pixel: (a + 1) << 32 | (b + 1), a negative id counting as -1; 0 where the pixel does not take part
 __device__ __forceinline__ u64 key_of(int a, int b) {
   const u64 ka = a < 0 ? 0ull : (u64)(unsigned)a + 1ull, kb = b < 0 ? 0ull : (u64)(unsigned)b + 1ull;
@@ -169,25 +163,15 @@ __device__ __forceinline__ void push(const Lds& s, const OvK& k, u64 key, unsign
 }
 
 // One wave round: every lane brings the sums of those of its four pixels that belong to the pair `key` (0: none): cnt = pixels |
-// weighted << COUNT_BITS, the charge q and the smallest pixel index `first`.  The lanes that share a pair are found by ballot and
-// summed across the wave, and the first of them sends the sums on; a lane alone with its pair sends its own after the loop,
-// together with the other such lanes.  The pixels of a wave ascend with the lane, so the group's smallest index is its leader's.
+// weighted << COUNT_BITS, the charge q and the smallest pixel index `first`.  The lanes that share a pair are summed across the
+// wave, and the first of them sends the sums on; a lane alone with its pair sends its own (walk::wave_round).  The pixels of a
+// wave ascend with the lane, so the group's smallest index is its leader's.
 __device__ __forceinline__ void wave_round(const Lds& s, const OvK& k, u64 key, unsigned first, unsigned cnt, unsigned q) {
-  const int lane = threadIdx.x & 63;
-  const bool active = key != ubh::EMPTY_KEY;
-  u64 rem = __ballot(active);
-  bool solo = false;
-  while (rem != 0ull) {                                           // wave-uniform: one trip per distinct pair among the active lanes
-    const wv::KeyGroup<u64> g = wv::next_key_group(rem, key, active);
-    if (__popcll(g.lanes) == 1) {
-      solo = solo || lane == g.leader;
-      continue;
-    }
+  walk::wave_round(key, key != ubh::EMPTY_KEY, [&](const wv::KeyGroup<u64>& g, int lane) {
     const unsigned tc = wv::sum_all(g.member ? cnt : 0u);
     const unsigned tq = wv::sum_all(g.member ? q : 0u);
     if (lane == g.leader) push(s, k, g.key, first, tc, tq);
-  }
-  if (solo) push(s, k, key, first, cnt, q);
+  }, [&] { push(s, k, key, first, cnt, q); });
 }
 
 // the four pixels p .. p + 3 of a lane, whose ids are a4 and b4 (-1 past the end of the image)
@@ -212,7 +196,7 @@ __device__ __forceinline__ void lane_pixels(const Lds& s, const OvK& k, unsigned
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        if ((part >> j) & 1u) w[j] = weight_of(v[j], k.scale);
+        if ((part >> j) & 1u) w[j] = adc::weight_of(v[j], k.scale).w;
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -253,17 +237,6 @@ __device__ __forceinline__ void flush(const Lds& s, const OvK& k) {
   __syncthreads();
 }
 
-// four ids of one map from pixel p on (p a multiple of four, the map 16-byte aligned); -1 past the end of the image
-__device__ __forceinline__ int4 load_ids(const int32_t* __restrict__ ids, unsigned p, unsigned pixels) {
-  if (p + 3u < pixels) return *(const int4*)(ids + p);
-  int4 r;
-  r.x = p < pixels ? ids[p] : -1;
-  r.y = p + 1u < pixels ? ids[p + 1u] : -1;
-  r.z = p + 2u < pixels ? ids[p + 2u] : -1;
-  r.w = -1;                                                       // p + 3 >= pixels
-  return r;
-}
-
 __global__ __launch_bounds__(UBH_LANES) void insert_kernel(const OvK k) {
   __shared__ u64 s_key[ubh::LDS_SLOTS];
   __shared__ u64 s_first[ubh::LDS_SLOTS];
@@ -277,25 +250,10 @@ __global__ __launch_bounds__(UBH_LANES) void insert_kernel(const OvK k) {
   }
   if (threadIdx.x == 0) s_used = 0u;
   __syncthreads();
-  const unsigned t0 = blockIdx.x * k.span;
-  unsigned t1 = t0 + k.span;
-  if (t1 > k.trips) t1 = k.trips;
-  for (unsigned t = t0; t < t1; ++t) {                            // workgroup-uniform
-    const unsigned p0 = t * (unsigned)UBH_TRIP_PIXELS + threadIdx.x * 4u;   // < 2^31 + TRIP_PIXELS
-    int4 a4[ubh::TRIP_LOADS], b4[ubh::TRIP_LOADS];
-#pragma unroll
-    for (int u = 0; u < ubh::TRIP_LOADS; ++u) {
-      a4[u] = load_ids(k.a, p0 + (unsigned)u * LOAD_PIXELS, k.pixels);
-      b4[u] = load_ids(k.b, p0 + (unsigned)u * LOAD_PIXELS, k.pixels);
-    }
-#pragma unroll
-    for (int u = 0; u < ubh::TRIP_LOADS; ++u) lane_pixels(s, k, p0 + (unsigned)u * LOAD_PIXELS, a4[u], b4[u]);
-    __syncthreads();
-    const unsigned used = s_used;
-    __syncthreads();                                              // nobody claims a slot of the next trip before everybody has read
-    if (used > (unsigned)ubh::FLUSH_ABOVE) flush(s, k);           // workgroup-uniform
-  }
-  flush(s, k);
+  struct Ids { int4 a, b; };
+  walk::trip_loop(k.trips, k.span, &s_used, (unsigned)ubh::FLUSH_ABOVE,
+                  [&](unsigned p) { return Ids{walk::load_ids(k.a, p, k.pixels), walk::load_ids(k.b, p, k.pixels)}; },
+                  [&](unsigned p, const Ids& i) { lane_pixels(s, k, p, i.a, i.b); }, [&] { flush(s, k); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -313,7 +271,7 @@ struct NumK {
 };
 
 __device__ __forceinline__ unsigned root_mask(const NumK& k, unsigned p, const u64* (&root)[4]) {
-  const int4 a4 = load_ids(k.a, p, k.pixels), b4 = load_ids(k.b, p, k.pixels);
+  const int4 a4 = walk::load_ids(k.a, p, k.pixels), b4 = walk::load_ids(k.b, p, k.pixels);
   const u64 key[4] = {key_of(a4.x, b4.x), key_of(a4.y, b4.y), key_of(a4.z, b4.z), key_of(a4.w, b4.w)};
   unsigned m = 0u;
 #pragma unroll

@@ -1,6 +1,7 @@
 // The launch plan and the limits of libubresnet_moment.so (include/ubresnet_moment.h) as plain C++: no HIP, so
-// tests/moment_host.cpp compiles it into a stand-alone program with the host sanitizers on.  The trip, the grid, the span of
-// trips of a workgroup, what is refused and the overflow bound are decided here and nowhere else.
+// tests/moment_host.cpp compiles it into a stand-alone program with the host sanitizers on.  What is refused, the LDS table, the
+// clear grid and the overflow bound are decided here and nowhere else; the trip, the grid and the span of trips of a workgroup are
+// the pixel walk of ubr_walk_plan.h, which libubresnet_overlap.so shares.
 //
 // The overflow bound.  A weight is at most MAX_WEIGHT = 2^16 - 1.  A row or column index is at most MAX_ROWS - 1 = 2^12 - 1, so
 // r^2, r c and c^2 are below 2^24.  A cluster lies in one plane and a plane has at most MAX_PLANE_PIXELS = 2^22 pixels.  So the
@@ -13,37 +14,24 @@
 #define UBR_MOMENT_PLAN_H
 
 #include "ubr_scan_plan.h"                            // MAX_PIXELS, the bound of an int32 pixel index, and nothing else
+#include "ubr_walk_plan.h"
 
 namespace ubm {
 
-constexpr int WAVE = 64;
-constexpr int LANES = 256;                            // lanes of a workgroup: four waves
-constexpr int LANE_PIXELS = 4;                        // pixels of one lane per load: one 16-byte load of ids
-constexpr int TRIP_LOADS = 2;                         // loads of one lane per trip, both issued before either is used
-constexpr int TRIP_PIXELS = LANES * LANE_PIXELS * TRIP_LOADS;
-constexpr int MAX_GRID = 1024;                        // workgroups of the accumulation and of the clear
+using walk::WAVE; using walk::LANES; using walk::LANE_PIXELS; using walk::TRIP_LOADS; using walk::TRIP_PIXELS;
+using walk::MAX_GRID;                                 // workgroups of the accumulation and of the clear
+using walk::COUNT_BITS;                               // weighted | clipped << 10 | odd << 20 within one wave round
+using walk::MAX_WEIGHT; using walk::MAX_SCALE; using walk::valid_scale;
 constexpr int SLOTS = 64;                             // clusters of the LDS table of a workgroup
 constexpr int PROBES = 4;                             // slots a cluster tries, from k % SLOTS on, before it goes to memory directly
 constexpr int FLUSH_ABOVE = SLOTS / 2;                // the table is sent and emptied at the end of a trip that leaves more slots taken
 constexpr int MAX_CLASSES = 16;
 constexpr int TABLE_FIXED = 9;                        // weighted, clipped, odd, Q, Qr, Qc, Qrr, Qrc, Qcc
 constexpr int SLOT_WORDS = TABLE_FIXED + MAX_CLASSES; // uint64 words of one LDS slot
-constexpr int COUNT_BITS = 10;                        // weighted | clipped << 10 | odd << 20 within one wave round
 constexpr int64_t MAX_ROWS = 4096, MAX_COLS = 4096;
 constexpr int64_t MAX_PLANE_PIXELS = (int64_t)1 << 22;
-constexpr int64_t MAX_WEIGHT = 65535;
-constexpr int MAX_SCALE = 256;
 using scanplan::MAX_PIXELS;
 static_assert((SLOTS & (SLOTS - 1)) == 0 && SLOTS <= LANES && PROBES <= SLOTS, "k % SLOTS is a mask; one lane resets one slot key");
-static_assert(WAVE * LANE_PIXELS < (1 << COUNT_BITS), "a count field holds the pixels of a wave round");
-static_assert((uint64_t)WAVE * LANE_PIXELS * MAX_WEIGHT < ((uint64_t)1 << 32), "the charge of a wave round fits 32 bits");
-
-// adc_scale: a power of two in 1..MAX_SCALE
-inline bool valid_scale(float s) {
-  for (int p = 1; p <= MAX_SCALE; p *= 2)
-    if (s == (float)p) return true;
-  return false;
-}
 
 // what the image may be; the reason it is refused in *why (a format for rows, cols or the pixel count) if not
 inline bool valid_image(int64_t P, int64_t rows, int64_t cols, const char** why) {
@@ -65,11 +53,7 @@ inline uint64_t worst_column(int64_t rows, int64_t cols) {
   return (uint64_t)MAX_WEIGHT * (uint64_t)(rows * cols) * far * far;
 }
 
-struct Plan {
-  int64_t pixels;      // P * rows * cols
-  int64_t trips;       // ceil(pixels / TRIP_PIXELS)
-  int64_t span;        // consecutive trips of one workgroup: workgroup g takes trips g * span .. min((g + 1) * span, trips) - 1
-  int64_t grid;        // ceil(trips / span) <= MAX_GRID: no workgroup is without a trip
+struct Plan : walk::Walk {   // pixels = P * rows * cols, and its trips, span and grid
   int64_t clear_grid;  // workgroups of the clear: they stride over min(*count, capacity) * width words
 };
 
@@ -77,11 +61,7 @@ struct Plan {
 inline bool make_plan(int64_t P, int64_t rows, int64_t cols, int64_t capacity, int64_t C, Plan* p) {
   const char* why;
   if (!valid_image(P, rows, cols, &why) || capacity < 1 || C < 1 || C > MAX_CLASSES) return false;
-  p->pixels = P * rows * cols;
-  p->trips = (p->pixels + TRIP_PIXELS - 1) / TRIP_PIXELS;
-  const int64_t g = p->trips < MAX_GRID ? p->trips : MAX_GRID;
-  p->span = (p->trips + g - 1) / g;
-  p->grid = (p->trips + p->span - 1) / p->span;
+  static_cast<walk::Walk&>(*p) = walk::make_walk(P * rows * cols);
   // the rows that can be cleared are no more than the pixels: a cluster has a pixel
   const int64_t rows_max = capacity < p->pixels ? capacity : p->pixels;
   const int64_t units = (rows_max * (TABLE_FIXED + C) + LANES - 1) / LANES;

@@ -1,8 +1,9 @@
 // The launch plan, the pair key, the hash and the probe sequence of libubresnet_overlap.so (include/ubresnet_overlap.h) as plain
-// C++: no HIP, so tests/overlap_host.cpp compiles it into a stand-alone program with the host sanitizers on.  The trip, the grids,
-// the span of trips of a workgroup, the scratch layout, what is refused, the key of a pair, its home slot and how far it probes
-// are decided here and nowhere else; host_insert / host_lookup restate the device's insert and look-up one key at a time, for the
-// host program to hold against every insertion order.  The pixel-block compaction of launches 3 to 5 is ubr_scan_plan.h, unchanged.
+// C++: no HIP, so tests/overlap_host.cpp compiles it into a stand-alone program with the host sanitizers on.  The clear grid, the
+// scratch layout, what is refused, the key of a pair, its home slot and how far it probes are decided here and nowhere else;
+// host_insert / host_lookup restate the device's insert and look-up one key at a time, for the host program to hold against every
+// insertion order.  The trip, the grid and the span of trips of a workgroup of the insert are the pixel walk of ubr_walk_plan.h,
+// which libubresnet_moment.so shares; the pixel-block compaction of launches 3 to 5 is ubr_scan_plan.h, unchanged.
 //
 // The overflow bound.  An image has fewer than 2^31 pixels, so `first` and `pixels` are below 2^31 and so is `weighted`.  A weight
 // is at most MAX_WEIGHT = 2^16 - 1, so Q is below 2^31 * 2^16 = 2^47.  No column of a row, no word of a slot and no partial sum
@@ -15,15 +16,14 @@
 #define UBR_OVERLAP_PLAN_H
 
 #include "ubr_scan_plan.h"                            // the block plan of launches 3 to 5, and MAX_PIXELS
+#include "ubr_walk_plan.h"
 
 namespace ubh {
 
-constexpr int WAVE = 64;
-constexpr int LANES = 256;                            // lanes of a workgroup: four waves
-constexpr int LANE_PIXELS = 4;                        // pixels of one lane per load: one 16-byte load of each id map
-constexpr int TRIP_LOADS = 2;                         // loads of one lane per trip, all issued before any is used
-constexpr int TRIP_PIXELS = LANES * LANE_PIXELS * TRIP_LOADS;
-constexpr int MAX_GRID = 1024;                        // workgroups of the insert and of the clear
+using walk::WAVE; using walk::LANES; using walk::LANE_PIXELS; using walk::TRIP_LOADS; using walk::TRIP_PIXELS;
+using walk::MAX_GRID;                                 // workgroups of the insert and of the clear
+using walk::COUNT_BITS;                               // pixels | weighted << 10 within one wave round
+using walk::MAX_WEIGHT; using walk::MAX_SCALE; using walk::valid_scale;
 constexpr int LDS_SLOTS = 64;                         // pairs of the LDS table of a workgroup
 constexpr int LDS_PROBES = 4;                         // LDS slots a pair tries before it goes to memory directly
 constexpr int FLUSH_ABOVE = LDS_SLOTS / 2;            // the LDS table is sent and emptied at the end of a trip that leaves more taken
@@ -34,25 +34,13 @@ constexpr int64_t MIN_SLOTS = 64;
 constexpr int64_t MAX_SLOTS = (int64_t)1 << 30;
 constexpr int64_t DEFAULT_MIN_SLOTS = 1024;
 constexpr int64_t MAX_CAPACITY = (int64_t)1 << 31;    // pairs are no more than pixels; a larger table is never filled
-constexpr int COUNT_BITS = 10;                        // pixels | weighted << 10 within one wave round
-constexpr int64_t MAX_WEIGHT = 65535;
-constexpr int MAX_SCALE = 256;
 constexpr uint64_t GOLDEN = 0x9E3779B97F4A7C15ull;    // 2^64 / the golden ratio, odd: multiplying by it permutes the keys
 constexpr uint64_t EMPTY_KEY = 0;
 constexpr uint64_t NO_FIRST = ~(uint64_t)0;           // `first` of a slot nobody has added to: above every pixel index
 using scanplan::MAX_PIXELS;
 static_assert((LDS_SLOTS & (LDS_SLOTS - 1)) == 0 && LDS_SLOTS <= WAVE && LDS_PROBES <= LDS_SLOTS, "one lane of a wave flushes one LDS slot");
-static_assert(WAVE * LANE_PIXELS < (1 << COUNT_BITS), "a count field holds the pixels of a wave round");
-static_assert((uint64_t)WAVE * LANE_PIXELS * MAX_WEIGHT < ((uint64_t)1 << 32), "the charge of a wave round fits 32 bits");
 static_assert((uint64_t)MAX_PIXELS * MAX_WEIGHT < ((uint64_t)1 << 47), "Q < 2^47");
 static_assert(TRIP_PIXELS == 2 * scanplan::PIXEL_BLOCK && LANES == scanplan::LANES, "launches 3 to 5 use the workgroup of the scan plan");
-
-// adc_scale: a power of two in 1..MAX_SCALE
-inline bool valid_scale(float s) {
-  for (int p = 1; p <= MAX_SCALE; p *= 2)
-    if (s == (float)p) return true;
-  return false;
-}
 
 // ---- key, home slot, probe limit ----
 inline bool is_pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
@@ -89,11 +77,7 @@ inline int64_t default_slots(int64_t capacity) {
 }
 
 // ---- the plan ----
-struct Plan {
-  int64_t pixels;         // P * rows * cols
-  int64_t trips;          // ceil(pixels / TRIP_PIXELS)
-  int64_t span;           // consecutive trips of one workgroup of the insert
-  int64_t grid;           // ceil(trips / span) <= MAX_GRID: no workgroup is without a trip
+struct Plan : walk::Walk {   // pixels = P * rows * cols, and the trips, span and grid of the insert
   int64_t clear_grid;     // workgroups of the clear: they stride over `slots` slots, one per lane
   int log2_slots;
   int64_t probes;         // probes(slots)
@@ -117,11 +101,7 @@ inline bool make_plan(int64_t P, int64_t rows, int64_t cols, int64_t slots, Plan
   const char* why;
   if (!valid_image(P, rows, cols, &why) || !valid_slots(slots)) return false;
   if (!scanplan::make_block_plan(P, rows, cols, &p->blocks)) return false;
-  p->pixels = P * rows * cols;
-  p->trips = (p->pixels + TRIP_PIXELS - 1) / TRIP_PIXELS;
-  const int64_t g = p->trips < MAX_GRID ? p->trips : MAX_GRID;
-  p->span = (p->trips + g - 1) / g;
-  p->grid = (p->trips + p->span - 1) / p->span;
+  static_cast<walk::Walk&>(*p) = walk::make_walk(P * rows * cols);
   p->clear_grid = scanplan::stride_grid(slots, LANES, MAX_GRID);
   p->log2_slots = log2_of(slots);
   p->probes = probes(slots);
