@@ -2,7 +2,7 @@
 """Cluster the event products of synthetic labelled events on the device and print the cluster table, largest first.
 
     python tools/cluster_events.py [--events N] [--rows R] [--cols C] [--top K] [--min-pixels M] [--connectivity 4|8] [--by-class]
-                                   [--moments] [--adc-scale S] [--truth]
+                                   [--moments] [--adc-scale S] [--truth] [--match-planes] [--match-threshold T]
 
 Every event goes through WholeViewSegmenter(output="products") and an EventClusterer (ubresnet_amd/clusters.py); nothing leaves
 the device until Clusters.read(), which copies the count and that many table rows.  The model has seeded random weights, so the
@@ -12,7 +12,11 @@ of the shower class in that charge, its length (2 sqrt 3 times the major extent:
 With --truth the truth of the event is clustered the same way (overlap.truth_products into a second EventClusterer) and a
 ClusterOverlap (ubresnet_amd/overlap.py) matches the predicted clusters against the true ones: beside the table above, per
 predicted cluster, largest first, its purity, the efficiency of its best match and that match, pixel- and charge-weighted, and the
-event's adjusted Rand index.  (Without --by-class both sides cluster the same lit pixels whatever their class, and agree.)"""
+event's adjusted Rand index.  (Without --by-class both sides cluster the same lit pixels whatever their class, and agree.)
+With --match-planes the events are synthetic.make_matched_event -- the same objects seen by every plane -- and a PlaneMatcher
+(ubresnet_amd/planes.py) runs behind the clusterer: the clusters of at least --min-pixels pixels are matched across the planes by
+their time profiles, and the mutually best pairs at or above --match-threshold (containment) and the triples are printed with the
+object most pixels of each cluster belong to.  (--planes is the number of planes, as before.)"""
 import argparse
 import os
 import sys
@@ -37,6 +41,9 @@ def main():
     ap.add_argument("--moments", action="store_true")
     ap.add_argument("--adc-scale", type=int, default=16)
     ap.add_argument("--truth", action="store_true")
+    ap.add_argument("--match-planes", action="store_true")
+    ap.add_argument("--match-threshold", type=float, default=0.5)
+    ap.add_argument("--slots", type=int, default=512)
     a = ap.parse_args()
     import torch
     from ubresnet_amd import clusters, deploy, synthetic
@@ -55,10 +62,18 @@ def main():
         from ubresnet_amd import overlap
         cl_true = clusters.EventClusterer(a.planes, a.rows, a.cols, a.classes, a.connectivity, a.by_class, 255, a.capacity, "cuda:0")
         co = overlap.ClusterOverlap(a.planes, a.rows, a.cols, 4 * a.capacity, None, a.adc_scale, "cuda:0")
+    pm = None
+    if a.match_planes:
+        from ubresnet_amd import planes
+        pm = planes.PlaneMatcher(cl, a.slots, max(a.min_pixels, 1), 1, None, a.adc_scale)
     for e in range(a.events):
-        image, truth = synthetic.make_labelled_event(a.planes, a.rows, a.cols, 1000 + 10 * e)
+        if pm:
+            image, truth, instance = synthetic.make_matched_event(a.planes, a.rows, a.cols, 1000 + 10 * e)
+        else:
+            image, truth = synthetic.make_labelled_event(a.planes, a.rows, a.cols, 1000 + 10 * e)
         view = torch.from_numpy(image[:, None].copy()).cuda()
         found = cl(seg(view))
+        matches = pm(found, view) if pm else None                 # launched before anything is read back
         if a.truth:                                               # launched before anything is read back
             ov = co(found, cl_true(*overlap.truth_products(torch.from_numpy(truth).cuda(), view)), view)
         shape = cm(found, view).read(min_pixels=a.min_pixels) if cm else None
@@ -79,6 +94,24 @@ def main():
                                                                            float(width[i]), float(lin[i]))
             print("  %5d  %6d  %4d..%-4d  %4d..%-4d  %6.3f  %.4f" % (int(tab.plane[i]), int(tab.pixels[i]), r0, r1, c0, c1,
                                                                   float(frac[i, a.shower_class]), float(mean[i])) + more)
+        if pm:
+            mt = matches.read()
+            ids, inst = found.ids.cpu(), torch.from_numpy(instance)
+            obj = []
+            for k in mt.cluster.tolist():                             # the object most pixels of the cluster belong to
+                of = inst[ids == k]
+                obj.append(int(torch.bincount(of[of >= 0]).argmax()) if bool((of >= 0).any()) else -1)
+            pairs = mt.matched(a.match_threshold)
+            print("  %d candidates of at least %d pixels, %d pairs share a time bin, %d matched at containment >= %.2f; %d pixels dropped"
+                  % (len(mt), pm.min_pixels, len(mt.pairs()), len(pairs), a.match_threshold, mt.dropped))
+            iou, tio = mt.charge_iou(), mt.time_iou()
+            print("  cluster (plane, object)  cluster (plane, object)  containment  charge iou  time iou")
+            for i, j, v in pairs[:a.top]:
+                print("  %7d (%d, %3d)         %7d (%d, %3d)         %11.3f  %10.3f  %8.3f"
+                      % (int(mt.cluster[i]), int(mt.plane[i]), obj[i], int(mt.cluster[j]), int(mt.plane[j]), obj[j], v, iou[(i, j)], tio[(i, j)]))
+            triples = mt.triples(a.match_threshold)
+            print("  %d triples: %s" % (len(triples), ", ".join("(%s) of objects (%s)" % (", ".join(str(int(mt.cluster[c])) for c in t),
+                                                                                       ", ".join(str(obj[c]) for c in t)) for t in triples[:a.top])))
         if a.truth:
             match = ov.read()
             sizes, eff_of = match.sizes_a(), {}

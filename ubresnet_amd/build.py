@@ -5,8 +5,8 @@
 LIBS is the table of them, in build order: name -> (out, sources, headers, binding).  `hip` is libubresnet_hip.so, all HIP kernels
 of the network and its C ABI; every other entry is a library of one .hip file that links against none of the
 others (csrc/ubr_sat.h is the support header they all include; the event-product libraries of csrc/extra/ also share
-csrc/ubr_wave.h, their wave and workgroup primitives, and csrc/ubr_scan_plan.h, the plan of their pixel-block compaction; moment
-and overlap also csrc/ubr_walk_plan.h, ubr_adc_rule.h and ubr_walk.h, their pixel walk and weight rule), and whose purpose the docstring of its binding module states.  `sources` and `headers` are relative to csrc/, `headers`
+csrc/ubr_wave.h, their wave and workgroup primitives, and csrc/ubr_scan_plan.h, the plan of their pixel-block compaction; moment,
+overlap and match also csrc/ubr_walk_plan.h, ubr_adc_rule.h and ubr_walk.h, their pixel walk and weight rule), and whose purpose the docstring of its binding module states.  `sources` and `headers` are relative to csrc/, `headers`
 being every file the sources reach through quoted #includes; `binding` names the ctypes module of ubresnet_amd that loads `out`.
 
 The shared libraries have NO PyTorch dependency: they are plain HIP behind the public headers in include/.  Objects are compiled
@@ -77,6 +77,9 @@ ADDONS = {
     "overlap": Lib(os.path.join(HERE, "libubresnet_overlap.so"), [os.path.join("extra", "ubr_overlap.hip")],
                    ["ubr_sat.h", "ubr_overlap_plan.h", "ubr_scan_plan.h", "ubr_walk_plan.h", "ubr_adc_rule.h", "ubr_walk.h", "ubr_wave.h",
                     os.path.join("..", "..", "include", "ubresnet_overlap.h")], "_overlap"),
+    "match": Lib(os.path.join(HERE, "libubresnet_match.so"), [os.path.join("extra", "ubr_match.hip")],
+                 ["ubr_sat.h", "ubr_match_plan.h", "ubr_scan_plan.h", "ubr_walk_plan.h", "ubr_adc_rule.h", "ubr_walk.h", "ubr_wave.h",
+                  os.path.join("..", "..", "include", "ubresnet_match.h")], "_match"),
 }
 
 

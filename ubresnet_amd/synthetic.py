@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import numpy as np
 
-__all__ = ["make_crop", "make_batch", "make_labelled_event", "SyntheticLArCVDataset"]
+__all__ = ["make_crop", "make_batch", "make_labelled_event", "make_matched_event", "SyntheticLArCVDataset"]
 
 
 def make_crop(height: int, width: int, seed: int, labelled_weight: float = 10.0):
@@ -96,6 +96,71 @@ def make_labelled_event(planes: int, rows: int, cols: int, seed: int):
         a, l, _ = make_crop(rows, cols, seed + p)
         image[p], label[p] = a, l.astype(np.uint8)
     return image, label
+
+
+WIRE_ANGLES = (np.pi / 3.0, -np.pi / 3.0, 0.0, np.pi / 2.0)      # of planes 0..3 against the z axis: U, V, Y as in MicroBooNE, and one across
+OBJECT_GAP = 3                                                    # pixels between the projections of two objects, in every plane
+
+
+def _wire(p, y, z, cols):
+    """the column of the point (y, z) in plane p: y in -0.2 cols..0.2 cols and z in 0.25 cols..0.75 cols stay inside 0..cols"""
+    a = WIRE_ANGLES[p]
+    offset = (0.25, 0.25, 0.0, 0.5)[p] * cols
+    return z * np.cos(a) + y * np.sin(a) + offset
+
+
+def make_matched_event(planes: int, rows: int, cols: int, seed: int, objects: int = 8):
+    """One event whose planes show the SAME objects -> (image float32 [planes,rows,cols], label uint8 [planes,rows,cols],
+    instance int32 [planes,rows,cols], -1 where a pixel is dark).  ``make_labelled_event`` draws every plane on its own; here
+    track-like (label 1) and shower-like (label 2, a filled cone) objects are drawn in (t, y, z) and projected onto the planes with
+    the fixed WIRE_ANGLES, the row being t in every plane: an object covers the same rows and deposits the same charge per row in
+    every plane.  Charge that falls on one pixel adds up.  A candidate object is rejected until its projections keep OBJECT_GAP
+    pixels from every earlier object in every plane, so that a connected cluster is one object; at most 50 candidates per object
+    are drawn, so a crowded view may hold fewer than ``objects``.  Pure numpy, seeded."""
+    if not 1 <= planes <= len(WIRE_ANGLES):
+        raise ValueError("make_matched_event: planes must be 1..%d (got %r)" % (len(WIRE_ANGLES), planes))
+    rs = np.random.RandomState(seed)
+    image = np.zeros((planes, rows, cols), dtype=np.float32)
+    label = np.zeros((planes, rows, cols), dtype=np.uint8)
+    instance = np.full((planes, rows, cols), -1, dtype=np.int32)
+    taken = np.zeros((planes, rows, cols), dtype=bool)            # within OBJECT_GAP pixels of an accepted object
+    placed = 0
+    for _ in range(50 * objects):
+        if placed == objects:
+            break
+        shower = rs.uniform() < 0.4
+        t0, y0, z0 = rs.uniform(0.05 * rows, 0.95 * rows), rs.uniform(-0.2 * cols, 0.2 * cols), rs.uniform(0.25 * cols, 0.75 * cols)
+        length = rs.uniform(0.15, 0.5) * min(rows, cols) * (0.6 if shower else 1.0)
+        d = rs.normal(0.0, 1.0, 3)
+        d /= np.linalg.norm(d)
+        t1 = float(np.clip(t0 + length * d[0], 0, rows - 1))
+        y1 = float(np.clip(y0 + length * d[1], -0.2 * cols, 0.2 * cols))
+        z1 = float(np.clip(z0 + length * d[2], 0.25 * cols, 0.75 * cols))
+        reach = max([abs(t1 - t0)] + [abs(_wire(p, y1, z1, cols) - _wire(p, y0, z0, cols)) for p in range(planes)])
+        n = 2 * int(reach) + 2                                     # steps of at most half a pixel: the projection is 8-connected
+        s = np.linspace(0.0, 1.0, n)
+        adc = (rs.exponential(25.0, n) + 5.0 if shower else rs.uniform(20.0, 60.0) + rs.normal(0.0, 3.0, n).clip(-9.0, 9.0)).astype(np.float32)
+        half = np.floor(s * rs.uniform(2.0, 5.0)).astype(np.int64) if shower else np.full(n, rs.randint(0, 2), np.int64)
+        yy = np.clip(np.round(t0 + (t1 - t0) * s).astype(np.int64), 0, rows - 1)
+        drawn = []
+        for p in range(planes):
+            xc = np.round(_wire(p, y0 + (y1 - y0) * s, z0 + (z1 - z0) * s, cols)).astype(np.int64)
+            ys, xs, vs = [], [], []
+            for dw in range(-int(half.max()), int(half.max()) + 1):
+                on = np.abs(dw) <= half
+                ys.append(yy[on]), xs.append(np.clip(xc[on] + dw, 0, cols - 1)), vs.append(adc[on] / (2 * half[on] + 1))
+            drawn.append((np.concatenate(ys), np.concatenate(xs), np.concatenate(vs)))
+        if any(taken[p, ys, xs].any() for p, (ys, xs, _) in enumerate(drawn)):
+            continue
+        for p, (ys, xs, vs) in enumerate(drawn):
+            np.add.at(image[p], (ys, xs), vs)
+            label[p, ys, xs] = 2 if shower else 1
+            instance[p, ys, xs] = placed
+            for dy in range(-OBJECT_GAP, OBJECT_GAP + 1):
+                for dx in range(-OBJECT_GAP, OBJECT_GAP + 1):
+                    taken[p, np.clip(ys + dy, 0, rows - 1), np.clip(xs + dx, 0, cols - 1)] = True
+        placed += 1
+    return image, label, instance
 
 
 class SyntheticLArCVDataset(object):
