@@ -995,3 +995,115 @@ def assert_bits(got, expected, zero_sign=True, what=""):
         m = (1 << (8 * got.element_size())) - 1
         raise AssertionError("%s: %d of %d elements differ in bits; first at %s: got %r (0x%x), expected %r (0x%x)"
                              % (what, int(bad.sum()), bad.numel(), idx, float(got[idx]), gb & m, float(e[idx]), eb & m))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# launches replayed on operands that are NOT exact (tests/stage_shadow.py: the stages of a pass at realistic magnitudes, every
+# launch against fp64 of its own recorded inputs).  No new constant: every bound below is gamma(k) -- k fp32 roundings on the
+# path of a term, applied to the sum of the ABSOLUTE values of the terms -- plus one rounding to the stored type, i.e.
+# bound(ref, absref, dtype, k) above, plus half the smallest subnormal of the stored type (TINY: a store can miss by that much
+# however small the value is; for f16 that is 2^-25, which gradients do reach).
+# ------------------------------------------------------------------------------------------------------------------
+# ET<T>::pack / ET<T>::st (csrc/ubr_common.h) convert with plain casts, (__bf16)v and (_Float16)v: v_cvt_pk_bf16_f32 / v_cvt_f16_f32,
+# round to nearest even with gradual underflow (the f16 denormal mode of a HIP kernel is on by default; nothing in the build turns
+# it off), so a store misses by at most half the subnormal spacing.  A store that flushed subnormals would miss by up to 2^-14 in
+# f16 and fall outside these bounds.  TINY is added only where an output has a nonzero term: an output all of whose terms are
+# zero is exactly zero, and its bound is zero.
+TINY = {torch.float32: 2.0 ** -150, torch.bfloat16: 2.0 ** -134, torch.float16: 2.0 ** -25}
+
+
+def affine_terms(v, mean, scale, shift):
+    """(bn, sum of |terms|, d) of bn = fma(fl(v - mean), scale, shift) in fp64.  The kernels form it with TWO fp32 roundings (the
+    difference, the fused multiply-add), so |bn^ - bn| <= gamma(2) * (|d*scale| + |shift|)."""
+    d = v.double() - _vec(mean, v)
+    p = d * _vec(scale, v)
+    return p + _vec(shift, v), p.abs() + _vec(shift, v).abs(), d
+
+
+def gate_open(bn, terms):
+    """elements whose ReLU gate [bn > 0] the fp32 evaluation may decide either way: |bn| within its own error gamma(2) * terms"""
+    return bn.abs() <= gamma(2) * terms
+
+
+def xf_operand_err(x, xf, dtype):
+    """An MFMA operand formed on load: t = max(fma(fl(x - sub), scale, shift), lo) in fp32 (ubr_bnrelu: two roundings, the max is
+    1-Lipschitz), then packed to the compute type T (ET<T>::pack: one rounding, relative u_T, or TINY).  Per element
+        |x^ - t| <= u_T |t| + (1 + u_T) gamma(2) (|(x - sub) scale| + |shift|) + TINY.
+    A conv / weight gradient then carries sum |w| * that on top of its accumulation bound (conv_ref of this tensor with |W|).
+    -> fp64 tensor of x's shape; zero without a transform (operands are read as stored)."""
+    if xf is None:
+        return torch.zeros(x.shape, dtype=torch.float64)
+    sub, scale, shift, lo = xf
+    C = x.shape[-1]
+    bn, terms, _ = affine_terms(x, sub[:C], scale[:C], shift[:C])
+    t = torch.maximum(bn, _vec(lo, x)[:C])
+    u = UNIT_ROUNDOFF[dtype]
+    return u * t.abs() + (1.0 + u) * gamma(2) * terms + TINY[dtype] * (terms > 0)
+
+
+def tail_fwd_bound(c2, mean2, scale2, shift2, sc, dtype, mean_b=None, scale_b=None, shift_b=None):
+    """(ref, lim) of one block-tail forward launch (tail_fwd_kernel): relu(bn2) and the shortcut's BatchNorm carry two roundings
+    each, their sum a third, the ReLUs none: |o^ - o| <= gamma(3) * (terms of bn2 + terms of the shortcut), then the store."""
+    ref = tail_fwd_ref(c2, mean2, scale2, shift2, sc, mean_b, scale_b, shift_b)
+    _, t2, _ = affine_terms(c2, mean2, scale2, shift2)
+    tb = sc.double().abs() if mean_b is None else affine_terms(sc, mean_b, scale_b, shift_b)[1]
+    return ref, bound(ref, t2 + tb, dtype, 3) + TINY[dtype] * (t2 + tb > 0)
+
+
+def reduce_chain(npix, C, dtype):
+    """upper bound of the depth of an fp32 partial of a reduce pass (see the note on the reduce passes at the top): the per-thread
+    chain ceil(npix * CU / (256 * workgroups)) with the grid of pick_blocks(npix, CU, 512, 8), plus at most 6 butterfly levels"""
+    CU = C // CPU[dtype]
+    blocks = pick_blocks(npix, CU, 512, 8)
+    return (npix * CU + 256 * blocks - 1) // (256 * blocks) + 6
+
+
+def reduce_bound(gy, xhat, L, open_gate=None, extra=0):
+    """per-channel (s, sx, lim_s, lim_sx) of a reduce pass on inexact operands: fp32 partials L deep (reduce_chain), g_y*xhat with
+    the two roundings of xhat = fl(fl(c - mean) * invstd) and its own product (+3), `extra` roundings that g_y itself carries (a
+    second gradient operand added in fp32: 1), then fp64 (2^-50).  Where the gate of an element is open (gate_open) the kernel may
+    have taken the other branch: the whole term is added to the bound."""
+    C = gy.shape[-1]
+    g, x = gy.reshape(-1, C), xhat.reshape(-1, C)
+    t = g * x
+    l1 = (gamma(L + extra) + 2.0 ** -50) * g.abs().sum(0)
+    l2 = (gamma(L + 3 + extra) + 2.0 ** -50) * t.abs().sum(0)
+    if open_gate is not None:
+        o = open_gate.reshape(-1, C).double()
+        l1, l2 = l1 + (o * g.abs()).sum(0), l2 + (o * t.abs()).sum(0)
+    return g.sum(0), t.sum(0), l1, l2
+
+
+def apply_bound(gy, xhat, scale, k1, k2, dtype, extra=0):
+    """(ref, lim) of an apply pass g_c = scale * (g_y - k1 - xhat*k2): xhat two roundings, its product with k2, two differences,
+    the product with scale: at most 6 on any term (+ `extra` of g_y, + 1 where k1 / k2 are formed in the kernel from the stripes:
+    the caller passes it in `extra`), on the terms |scale| (|g_y| + |k1| + |xhat k2|); then the store."""
+    ref = apply_ref(gy, xhat, scale, k1, k2)
+    terms = _vec(scale, gy).abs() * (gy.abs() + _vec(k1, gy).abs() + (xhat * _vec(k2, gy)).abs())
+    return ref, bound(ref, terms, dtype, 6 + extra) + TINY[dtype] * (terms > 0)
+
+
+def stored_bound(ref, pre, dtype):
+    """bound after the store of an fp32 value v^ with |v^ - ref| <= pre: the store rounds once, |round(v^) - v^| <= u_out |v^| <=
+    u_out (|ref| + pre), or misses by TINY in the subnormal range: u_out (|ref| + pre) + pre + TINY (zero where ref and pre are)"""
+    return C_OUT * UNIT_ROUNDOFF[dtype] * (ref.abs() + pre) + pre + TINY[dtype] * ((ref.abs() + pre) > 0)
+
+
+def conv_stats_bound(ref, pre, N, OH, OW):
+    """forward statistics (sum v^, sum v^^2 over the output grid) of an fp32 conv value with |v^ - ref| <= pre, per channel:
+    -> (fp64 [2C] reference sums of ref, bound).  The chain bound stats_eps(stats_chain) applies to the sums of the values the
+    kernel actually has; those differ from ref's by at most sum pre, and sum |v^^2 - v^2| <= sum (2 |v| pre + pre^2):
+        |s1 - sum v|   <= e1 sum |v|  + (1 + e1) sum pre
+        |s2 - sum v^2| <= e2 sum v^2  + (1 + e2) sum (2 |v| pre + pre^2)"""
+    C = ref.shape[-1]
+    s1, s2, a1, a2 = conv_stats_ref(ref)
+    e1, e2 = stats_eps(stats_chain(N, OH, OW))
+    p, v = pre.reshape(-1, C), ref.reshape(-1, C).abs()
+    return torch.cat([s1, s2]), torch.cat([e1 * a1 + (1 + e1) * p.sum(0), e2 * a2 + (1 + e2) * (2 * v * p + p * p).sum(0)])
+
+
+def bn_eval_affine_bound(gamma_, rvar, eps):
+    """ubr_bn_eval_affine in fp32 against bn_eval_affine_ref (fp64): invstd = 1 / sqrtf(fl(rvar + eps)) is three roundings, scale =
+    gamma * invstd a fourth (the counts tests/test_gpu_param_exact.py uses): -> ((invstd, lim), (scale, lim)), lim = gamma(k) |ref|"""
+    inv, sc = bn_eval_affine_ref(gamma_, rvar, eps)
+    return (inv, gamma(3) * inv.abs()), (sc, gamma(4) * sc.abs())

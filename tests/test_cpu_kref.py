@@ -883,3 +883,91 @@ def test_assert_bits_tells_signed_zeros_and_nans():
     kref.assert_bits(torch.tensor([1, 2], dtype=torch.uint8), torch.tensor([1, 2], dtype=torch.uint8))
     with pytest.raises(AssertionError):
         kref.assert_bits(torch.tensor([1, 2], dtype=torch.uint8), torch.tensor([1, 3], dtype=torch.uint8))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# bounds for launches replayed on inexact operands (tests/stage_shadow.py)
+# ------------------------------------------------------------------------------------------------------------------
+def _inexact(shape, seed, scale=1.0):
+    return (torch.randn(shape, generator=torch.Generator().manual_seed(seed)) * scale)
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+def test_inexact_bounds_cover_a_float32_evaluation_and_miss_a_wrong_site(dt):
+    """the kernels' statements evaluated in fp32 (torch, no contraction) and stored in `dt` lie inside tail_fwd_bound /
+    apply_bound / xf_operand_err; the same evaluation with another site's mean lies outside"""
+    C, shape = 16, (2, 9, 7, 16)
+    c2, sc = _inexact(shape, 1).to(dt), _inexact(shape, 2).to(dt)
+    m2, s2, t2 = _inexact((C,), 3, 0.1), _inexact((C,), 4).abs() + 0.5, _inexact((C,), 5, 0.3)
+    mb, sb, tb = _inexact((C,), 6, 0.1), _inexact((C,), 7).abs() + 0.5, _inexact((C,), 8, 0.3)
+
+    def tail(mean2):
+        r2 = ((c2.float() - mean2) * s2 + t2).clamp_min(0)
+        return (r2 + ((sc.float() - mb) * sb + tb)).clamp_min(0).to(dt)
+    ref, lim = kref.tail_fwd_bound(c2, m2, s2, t2, sc, dt, mb, sb, tb)
+    kref.assert_within(tail(m2), ref, lim, "tail")
+    with pytest.raises(AssertionError):
+        kref.assert_within(tail(mb), ref, lim, "tail with bnpass's mean")
+    # apply pass
+    gy, k1, k2, inv = _inexact(shape, 9).to(dt), _inexact((C,), 10, 0.05), _inexact((C,), 11, 0.05), _inexact((C,), 12).abs() + 0.5
+    d = c2.float() - m2
+    got = (s2 * (gy.float() - k1 - (d * inv) * k2)).to(dt)
+    xh = (c2.double() - m2.double()) * inv.double()
+    ref, lim = kref.apply_bound(gy.double(), xh, s2, k1, k2, dt)
+    kref.assert_within(got, ref, lim, "apply")
+    with pytest.raises(AssertionError):
+        kref.assert_within((sb * (gy.float() - k1 - (d * inv) * k2)).to(dt), ref, lim, "apply with bnpass's scale")
+    # an operand transformed on load, then packed to the compute type
+    lo = torch.zeros(C)
+    got = torch.maximum((c2.float() - m2) * s2 + t2, lo).to(dt)
+    want = torch.maximum((c2.double() - m2.double()) * s2.double() + t2.double(), lo.double())
+    kref.assert_within(got, want, kref.xf_operand_err(c2, (m2, s2, t2, lo), dt), "operand")
+    assert float(kref.xf_operand_err(c2, None, dt).abs().max()) == 0.0
+
+
+def test_reduce_bound_covers_float32_partials_and_an_open_gate():
+    C, shape = 16, (2, 24, 40, 16)
+    g32, c32, m32, i32 = _inexact(shape, 1), _inexact(shape, 2), _inexact((C,), 3, 0.1), _inexact((C,), 4).abs() + 0.5
+    gy, xh = g32.double(), (c32.double() - m32.double()) * i32.double()
+    L = kref.reduce_chain(2 * 24 * 40, C, torch.bfloat16)
+    assert L == (1920 * 2 + 256 * kref.pick_blocks(1920, 2, 512, 8) - 1) // (256 * kref.pick_blocks(1920, 2, 512, 8)) + 6
+    s, sx, l1, l2 = kref.reduce_bound(gy, xh, L)
+    # the kernel's statements in fp32: xhat = fl(fl(c - mean) * invstd), the term fl(g_y * xhat): the three roundings reduce_bound
+    # counts on top of the chain.  Then fp32 partials of L terms each, added in fp64.  The limits stand on their own.
+    g32, t32 = g32.reshape(-1, C), (g32 * ((c32 - m32) * i32)).reshape(-1, C)
+    parts = lambda v: sum(v[i:i + L].sum(0, dtype=torch.float32).double() for i in range(0, v.shape[0], L))
+    assert bool(((parts(g32) - s).abs() <= l1).all()) and bool(((parts(t32) - sx).abs() <= l2).all())
+    # one term dropped is outside, unless its gate is open
+    drop = g32.clone()
+    drop[5] = 0
+    assert not bool(((parts(drop) - s).abs() <= l1).all())
+    opn = torch.zeros(shape, dtype=torch.bool).reshape(-1, C)
+    opn[5] = True
+    _, _, o1, _ = kref.reduce_bound(gy, xh, L, opn.reshape(shape))
+    assert bool(((parts(drop) - s).abs() <= o1).all())
+    assert kref.gate_open(torch.tensor([1e-9, 0.5]), torch.tensor([1.0, 1.0])).tolist() == [True, False]
+
+
+def test_stored_stats_and_eval_affine_bounds():
+    dt = torch.float16
+    ref = _inexact((2, 5, 7, 16), 1).double()
+    pre = ref.abs() * 1e-4
+    lim = kref.stored_bound(ref, pre, dt)
+    kref.assert_within((ref * (1 + 1e-4)).float().to(dt), ref, lim, "a value inside pre, then stored")
+    assert not bool((((ref * (1 + 2e-3)).float().to(dt).double() - ref).abs() <= lim).all())
+    z = torch.zeros(3, dtype=torch.float64)
+    assert float(kref.stored_bound(z, z, dt).max()) == 0.0                   # nothing in, nothing allowed out
+    assert float(kref.stored_bound(z + 1e-9, z, dt).min()) >= kref.TINY[dt]    # a subnormal result may miss by half a spacing
+    # statistics of values that are themselves off by up to pre
+    s, l = kref.conv_stats_bound(ref, pre, 2, 5, 7)
+    v = (ref * (1 + 1e-4)).float()
+    got = torch.cat([v.reshape(-1, 16).sum(0, dtype=torch.float32).double(), (v * v).reshape(-1, 16).sum(0, dtype=torch.float32).double()])
+    assert bool(((got - s).abs() <= l).all())
+    s0, l0 = kref.conv_stats_bound(ref, torch.zeros_like(ref), 2, 5, 7)
+    assert not bool(((got - s0).abs() <= l0).all())
+    # ubr_bn_eval_affine's statements in fp32
+    g, rv, eps = _inexact((64,), 2), _inexact((64,), 3).abs() + 0.1, 1e-5
+    inv32 = 1.0 / torch.sqrt(rv + torch.tensor(eps))
+    (inv, li), (sc, ls) = kref.bn_eval_affine_bound(g, rv, eps)
+    assert bool(((inv32.double() - inv).abs() <= li).all()) and bool((((g * inv32).double() - sc).abs() <= ls).all())
+    assert not bool(((1.0 / torch.sqrt(rv)).double() - inv).abs().le(li).all())
