@@ -82,6 +82,20 @@ def logsoftmax_ref(v):
     return ref, C_ACC * U32 * (ref.abs() + lse.abs() + 1.4 * n + 4 + 4 * math.log(n))
 
 
+# The same epilogue on logits that are not exact (tests/stage_shadow.py: the head's conv11 on realistic operands).  The kernel's fp32
+# logits v^ differ from the fp64 logits v of the recorded inputs by |v^_c - v_c| <= pre_c (accumulation + on-load affine, the term
+# ref_conv forms for every conv).  Log-softmax is out_c = v_c - lse(v); lse is a maximum-like function: its gradient is the softmax
+# p (p_r >= 0, sum p_r = 1), so |lse(v^) - lse(v)| <= max_r |v^_r - v_r| and
+#     |out_c(v^) - out_c(v)| <= |v^_c - v_c| + max_r |v^_r - v_r| <= 2 max_r pre_r.
+# The epilogue's own error, logsoftmax_ref()'s bound, applies to the logits the kernel has; evaluated on v instead of v^ its
+# |ref| + |lse| term moves by at most 3 max pre * u, second order, covered by C_ACC.  The output is stored as fp32: that rounding is
+# the u |out| of the bound above.  Hence logsoftmax_bound(): the epilogue bound + 2 max_r pre_r per pixel.
+def logsoftmax_bound(v, pre):
+    """v: fp64 logits, pre: bound of the fp32 logits' error, both channels last -> (log-softmax fp64, bound of the fused epilogue's output)"""
+    ref, lim = logsoftmax_ref(v)
+    return ref, lim + 2.0 * pre.amax(-1, keepdim=True)
+
+
 def stats_chain(N, OH, OW):
     return N * OH * ((OW + 15) // 16) + 4
 
@@ -1039,6 +1053,64 @@ def xf_operand_err(x, xf, dtype):
     t = torch.maximum(bn, _vec(lo, x)[:C])
     u = UNIT_ROUNDOFF[dtype]
     return u * t.abs() + (1.0 + u) * gamma(2) * terms + TINY[dtype] * (terms > 0)
+
+
+# The stem's pool (maxpool_fwd_kernel with XF, XCOPY, AMAX): every tap is t^ = max(fma(fl(x - sub), scale, shift), lo) in fp32, the
+# window maximum m^ and its tap index are taken on those fp32 values (strict >, first maximum), and both xcopy = pack(t^) and
+# pooled = pack(m^) are stored ONCE.
+#   * xcopy: |t^ - t| <= pre and one store: stored_bound(t, pre, T), with pre = xf_operand_err (which, being the bound of a PACKED
+#     operand, already holds one rounding to T: the bound is that much wider than the arithmetic needs, never narrower).
+#   * pooled: |max_i a_i - max_i b_i| <= max_i |a_i - b_i| over the taps inside the image: the window maximum of the taps' bounds.
+#     Rounding is monotone, so pack(max t^) = max pack(t^): pooled is bit for bit the xcopy element at the arg-max tap.
+#   * arg-max: the kernel chose tap i because t^_i >= t^_j for the fp64 maximum j, so t_i >= t^_i - e_i >= t^_j - e_i >= t_j - e_j - e_i:
+#     the chosen tap's fp64 value lies within e_i + e_j of the window maximum, e the fp32 errors before the store.  The element bound
+#     lim_i holds u_T |t_i| on top of e_i, which at these types is orders of magnitude above e_j of a neighbouring tap of the same
+#     channel (same scale, same shift, |x| of the same size): 2 lim_i is the window the check allows.
+def pool_xf_bound(x, xf, stride, dtype):
+    """-> (pooled, lim_pooled, argmax of the fp64 values, t, lim_t): t = transformed input (= xcopy's reference), fp64; bounds as above"""
+    pooled, am, t = maxpool_ref(x, xf, stride)
+    lim_t = stored_bound(t, xf_operand_err(x, xf, dtype), dtype)
+    lim_p, _, _ = maxpool_ref(lim_t, None, stride)
+    return pooled, lim_p, am, t, lim_t
+
+
+def window_take(v, am, stride):
+    """v [N,H,W,C] at tap am (ky*3+kx of MaxPool2d(3, stride, 1)) of every window -> ([N,OH,OW,C] values, inside: the tap names a
+    pixel of the image)"""
+    N, H, W, C = v.shape
+    OH, OW = pool_out(H, stride), pool_out(W, stride)
+    am = am.long()
+    oy = torch.arange(OH).view(1, OH, 1, 1) * stride - 1 + am // 3
+    ox = torch.arange(OW).view(1, 1, OW, 1) * stride - 1 + am % 3
+    inside = (am >= 0) & (am < 9) & (oy >= 0) & (oy < H) & (ox >= 0) & (ox < W)
+    n = torch.arange(N).view(N, 1, 1, 1).expand_as(am)
+    c = torch.arange(C).view(1, 1, 1, C).expand_as(am)
+    return v[n, oy.clamp(0, H - 1), ox.clamp(0, W - 1), c], inside
+
+
+# Matrix-core products of f16 SUBNORMAL operands.  The accumulation bounds above charge gamma(K) on the sum of |g x|, i.e. they take
+# every product to be exact and every fp32 addition to round relative to the values added.  That holds for bf16 (no operand of
+# the network's range is subnormal: bf16 shares fp32's exponent range) and for normal f16 operands (11 x 11 significand bits fit
+# fp32).  An f16 subnormal has no hidden bit: its significand is 0.m at the FIXED exponent 2^-14, and a multiplier that does not
+# normalise its inputs delivers the product positioned at the NOMINAL exponent 2^-14 * 2^e(x), whatever the value of 0.m; the
+# fp32 alignment of the dot product then keeps 24 bits below that nominal exponent, not below the product's own leading bit.
+# Measured on the MI355X (v_mfma_f32_16x16x32_f16, whole ASPP_ResNet pass at 2 x 32 x 64 in f16, enc_layer5 at 1 x 2 pixels):
+# g = 37 * 2^-24, x = 1177 * 2^-15 and g = 9 * 2^-24, x = 1514 * 2^-10 sum to 479581 * 2^-39, a 19-bit number; the hardware
+# returned 479580 * 2^-39 -- the bit at 2^-39 lies 25 places below the nominal 2^-14 of the second product.  Every deviation seen
+# is one such power of two (2^-41 .. 2^-37); products of subnormals whose bits all lie inside the window are exact
+# (k * 2^-24 times 11-bit x: 786432 outputs, none off).  So for the ERROR terms an f16 operand counts with its nominal magnitude
+# max(|v|, 2^-14); a zero operand still gives an exact zero product and adds nothing.  This is the hardware's arithmetic on the
+# bytes the kernel hands it (ubr_wgrad.hip stages g raw), not a defect of the kernel: the derivation was wrong, and it is the
+# derivation that changes.  Normal operands are unaffected (max(|v|, 2^-14) = |v|), so are bf16 and fp32.
+F16_MIN_NORMAL = 2.0 ** -14
+
+
+def nominal_abs(v, dtype):
+    """|v| as a matrix-core error term sees it: an f16 subnormal counts as the smallest normal; zero stays zero.  v: fp64 / stored"""
+    a = v.double().abs()
+    if dtype != torch.float16:
+        return a
+    return torch.where(a > 0, a.clamp_min(F16_MIN_NORMAL), a)
 
 
 def tail_fwd_bound(c2, mean2, scale2, shift2, sc, dtype, mean_b=None, scale_b=None, shift_b=None):

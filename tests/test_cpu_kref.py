@@ -1,6 +1,8 @@
 """CPU: the float64 kernel references of tests/kref.py restate the PyTorch ops they stand for, and their checks have
 teeth -- each injected fault of the kind a tiled kernel makes (a tap dropped at a border pixel, a channel slice of one
 tile scaled, a tile missing from a statistics sum, a tile counted twice in a weight gradient) fails the check."""
+import math
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -971,3 +973,91 @@ def test_stored_stats_and_eval_affine_bounds():
     (inv, li), (sc, ls) = kref.bn_eval_affine_bound(g, rv, eps)
     assert bool(((inv32.double() - inv).abs() <= li).all()) and bool((((g * inv32).double() - sc).abs() <= ls).all())
     assert not bool(((1.0 / torch.sqrt(rv)).double() - inv).abs().le(li).all())
+
+
+def test_logsoftmax_bound_covers_perturbed_logits_and_misses_a_shifted_class():
+    """kref.logsoftmax_bound: the epilogue in fp32 on logits that are off by up to `pre` stays inside; a bias of 3 pre on one class does not"""
+    g = torch.Generator().manual_seed(5)
+    v = torch.randn((2, 9, 7, 3), generator=g, dtype=torch.float64) * 4
+    pre = (torch.rand(v.shape, generator=g, dtype=torch.float64) + 0.1) * 1e-4
+    ref, lim = kref.logsoftmax_bound(v, pre)
+    for seed in range(8):
+        d = (torch.rand(v.shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64) * 2 - 1) * pre
+        v32 = (v + d).float()                                    # the kernel's fp32 logits, then its statements in fp32
+        m = v32.amax(-1, keepdim=True)
+        got = v32 - (m + torch.log(torch.exp(v32 - m).sum(-1, keepdim=True)))
+        kref.assert_within(got, ref, lim, "log-softmax of perturbed logits")
+    # worst case of the derivation: one class up by pre, the others down by pre
+    d = -pre.clone()
+    d[..., 0] = pre[..., 0]
+    kref.assert_within(torch.log_softmax(v + d, -1), ref, lim, "extreme perturbation")
+    # the propagated term is 2 max pre per pixel on top of the epilogue's own bound, no more
+    assert torch.equal(lim, kref.logsoftmax_ref(v)[1] + 2 * pre.amax(-1, keepdim=True))
+    d = torch.zeros_like(v)
+    d[..., 1] = 3 * pre.amax(-1) + 1e-5
+    with pytest.raises(AssertionError):
+        kref.assert_within(torch.log_softmax(v + d, -1), ref, lim, "a class shifted beyond the bound")
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+def test_pool_xf_bound_covers_a_float32_evaluation_stored_once(dt):
+    """the stem pool's statements in fp32 (affine + ReLU per tap, maximum, ONE store of pooled and of the copy): inside
+    kref.pool_xf_bound; pooled is the stored copy at the arg-max tap, which lies within twice its bound of the fp64 maximum;
+    the same with another channel's shift is outside"""
+    C, shape = 16, (2, 10, 14, 16)
+    x = _inexact(shape, 1).to(dt)
+    sub, sc, sh, lo = _inexact((C,), 2, 0.1), _inexact((C,), 3).abs() + 0.5, _inexact((C,), 4, 0.3), torch.zeros(C)
+    t32 = torch.maximum((x.float() - sub) * sc + sh, lo)
+    xcopy = t32.to(dt)
+    p32, am, _ = kref.maxpool_ref(t32, None, 2)            # (exact on fp32 inputs: the kernel's maximum and first arg-max)
+    pooled = p32.float().to(dt)
+    ref_p, lim_p, am64, t, lim_t = kref.pool_xf_bound(x, (sub, sc, sh, lo), 2, dt)
+    kref.assert_within(xcopy, t, lim_t, "xcopy")
+    kref.assert_within(pooled, ref_p, lim_p, "pooled")
+    got, inside = kref.window_take(xcopy, am, 2)
+    assert bool(inside.all()) and torch.equal(got, pooled)
+    tv, _ = kref.window_take(t, am, 2)
+    lv, _ = kref.window_take(lim_t, am, 2)
+    assert bool(((ref_p - tv) <= 2 * lv).all()) and bool((ref_p >= tv).all())
+    # a tap outside the image is reported; a window's wrong tap is (nearly always) further than twice its bound from the maximum
+    bad = am.clone()
+    bad[:, 0, :, :] = 0                                        # row -1
+    assert not bool(kref.window_take(xcopy, bad, 2)[1].all())
+    other = (am + 4) % 9
+    ov, oin = kref.window_take(t, other, 2)
+    olv, _ = kref.window_take(lim_t, other, 2)
+    assert int((((ref_p - ov) > 2 * olv) & oin).sum()) > 0.5 * int(oin.sum())
+    with pytest.raises(AssertionError):
+        kref.assert_within(torch.maximum((x.float() - sub) * sc + sh.roll(1), lo).to(dt), t, lim_t, "xcopy with a neighbour's shift")
+    # near-ties: two taps closer than the fp32 error resolve either way inside the window the check allows
+    z = torch.zeros((1, 2, 2, 8))
+    z[0, 0, 0], z[0, 1, 1] = 1.0, 1.0
+    rp, lp, amz, tz, lz = kref.pool_xf_bound(z.to(dt), (torch.zeros(8), torch.ones(8), torch.zeros(8), torch.zeros(8)), 2, dt)
+    for tap in (4, 8):
+        tv, inside = kref.window_take(tz, torch.full((1, 1, 1, 8), tap), 2)
+        assert bool(inside.all()) and bool(((rp - tv) <= 2 * kref.window_take(lz, torch.full((1, 1, 1, 8), tap), 2)[0]).all())
+    assert not bool(((rp - kref.window_take(tz, torch.full((1, 1, 1, 8), 5), 2)[0]) <= 2 * kref.window_take(lz, torch.full((1, 1, 1, 8), 5), 2)[0]).all())
+
+
+def test_nominal_abs_covers_products_aligned_at_the_subnormal_exponent():
+    """kref.nominal_abs: a dot product whose f16 subnormal operand is multiplied as 0.m * 2^-14 and whose sum keeps 24 bits below
+    the largest NOMINAL product exponent (bits below are dropped) stays inside gamma(K) of the nominal sum of |terms| and falls
+    outside gamma(K) of the plain one; the values are those measured on the device (tests/kref.py, the note above nominal_abs)"""
+    g = torch.tensor([37 * 2.0 ** -24, 9 * 2.0 ** -24], dtype=torch.float16)
+    x = torch.tensor([1177 * 2.0 ** -15, 1514 * 2.0 ** -10], dtype=torch.float16)
+    assert g.double().tolist() == [37 * 2.0 ** -24, 9 * 2.0 ** -24] and x.double().tolist() == [1177 * 2.0 ** -15, 1514 * 2.0 ** -10]
+    ref = float((g.double() * x.double()).sum())
+    assert ref == 479581 * 2.0 ** -39
+    # the model: nominal exponent of a product = 2^-14 (g has no hidden bit) times 2^floor(log2 x); 24 bits are kept below the largest
+    top = max(-14 + math.floor(math.log2(float(v))) for v in x)
+    q = 2.0 ** (top - 24)
+    got = sum(math.floor(float(a) * float(b) / q) * q for a, b in zip(g.double(), x.double()))
+    assert got == 479580 * 2.0 ** -39                                   # what the MI355X returned
+    K = 2
+    plain = kref.C_ACC * K * kref.U32 * float((g.double().abs() * x.double().abs()).sum()) + kref.U32 * abs(ref)
+    nominal = kref.C_ACC * K * kref.U32 * float((kref.nominal_abs(g, torch.float16) * kref.nominal_abs(x, torch.float16)).sum()) + kref.U32 * abs(ref)
+    assert plain < abs(got - ref) <= nominal
+    # zero stays zero, normal values and the other types are untouched
+    v = torch.tensor([0.0, 2.0 ** -24, -2.0 ** -15, 2.0 ** -14, -0.5], dtype=torch.float16)
+    assert kref.nominal_abs(v, torch.float16).tolist() == [0.0, 2.0 ** -14, 2.0 ** -14, 2.0 ** -14, 0.5]
+    assert torch.equal(kref.nominal_abs(v.to(torch.bfloat16), torch.bfloat16), v.double().abs())

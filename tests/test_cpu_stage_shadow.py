@@ -121,6 +121,12 @@ CASES = {
     "mixed_bnpass_frozen": lambda m, dt: S.block_case(m, dt, "cpu", 32, 64, 2, (24, 40), emu=True, freeze=("bnpass",)),
     "aspp_level": lambda m, dt: S.aspp_case(m, dt, "cpu", 128, (20, 36), emu=True),
     "deconv_layer": lambda m, dt: S.declayer_case(m, dt, "cpu", 64, 32, 32, 32, (12, 20), emu=True),
+    "stem_one_plane": lambda m, dt: S.stem_case(m, dt, "cpu", 2, 1, 24, 40, 16, emu=True),
+    "stem_three_planes": lambda m, dt: S.stem_case(m, dt, "cpu", 2, 3, 20, 36, 32, emu=True),
+    "stem_eval": lambda m, dt: S.stem_case(m, dt, "cpu", 2, 1, 24, 40, 16, training=False, emu=True),
+    "head_3_classes": lambda m, dt: S.head_case(m, dt, "cpu", 2, 24, 40, 16, 16, 3, emu=True),
+    "head_4_classes": lambda m, dt: S.head_case(m, dt, "cpu", 2, 20, 36, 16, 16, 4, emu=True),
+    "head_bn10_frozen": lambda m, dt: S.head_case(m, dt, "cpu", 2, 24, 40, 16, 16, 3, freeze=("bn10",), emu=True),
 }
 
 
@@ -192,3 +198,82 @@ def test_chain_sees_an_exact_element_changed_after_its_launch(projection_run):
             S.check_chain(r["tape"], r["flat"], r["outputs"])
     finally:
         gx.view(-1)[i] = old
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the whole networks on the stand-in (one storage type each, as on the device): wiring, and the harness at the networks' size
+# ------------------------------------------------------------------------------------------------------------------
+def _net(which, dt):
+    mp = pytest.MonkeyPatch()
+    try:
+        r = S.net_case(mp, dt, "cpu", which, emu=True)
+    finally:
+        mp.undo()          # (the tap comes off before any other test launches anything: the tape is this pass and nothing else)
+    yield r, S.check_all(r)
+
+
+@pytest.fixture(scope="module")
+def uresnet_run():
+    yield from _net("uresnet", BF)
+
+
+def _assert_net(r, stat):
+    assert all(v[1] <= 1.0 for v in stat.values())
+    assert sum(v[0] for v in stat.values()) == len(r["tape"]) and r["exact"] > 0
+    assert bool(torch.isfinite(r["outputs"][0]).all())
+    # the flat gradient buffer and the reduction arenas went the device-side way: no host copy of a whole storage per launch
+    big = [v for L in r["tape"] for v in L.args.values() if isinstance(v, S.TRec) and v.big]
+    assert big and all(v.base_before is None and v.base_after is None and v.outside == (0, -1) for v in big)
+    assert len({id(v.base_init) for v in big}) <= 4
+
+
+def test_whole_uresnet_on_the_cpu_stand_in(uresnet_run):
+    _assert_net(*uresnet_run)
+
+
+def test_whole_aspp_resnet_on_the_cpu_stand_in():
+    for r, stat in _net("aspp", torch.float16):
+        _assert_net(r, stat)
+        # dec_layer5 reads its virtual deconv input and dec_layer4 / 5 their virtual concat channels through arena slices
+        xf = [L for L in r["tape"] if L.op == "conv_phases" and L.args.get("xf.scale") is not None]
+        assert len(xf) == 1 and xf[0].args["xf.scale"].shape == (1024,)
+
+
+@pytest.mark.parametrize("kind", S.NET_MUTATIONS)
+def test_mutated_network_tape_is_rejected(uresnet_run, kind):
+    r, _ = uresnet_run
+    tape, what = S.mutate(r["tape"], kind)
+    with pytest.raises(AssertionError):
+        r["graph"].match(tape)
+    if kind in S.VALUE_MUTATIONS:
+        with pytest.raises(AssertionError):
+            S.replay([L for L in tape if L.op == "conv" and L.args["logsoftmax"]])
+    r["graph"].match(r["tape"])          # (the graph is none the worse for the failed match)
+
+
+@pytest.mark.parametrize("kind", S.STEM_MUTATIONS)
+def test_mutated_stem_tape_is_rejected(monkeypatch, kind):
+    r = CASES["stem_three_planes"](monkeypatch, BF)
+    r["graph"].match(r["tape"])
+    tape, what = S.mutate(r["tape"], kind)
+    with pytest.raises(AssertionError):
+        r["graph"].match(tape)
+
+
+def test_a_byte_beside_a_view_of_a_big_storage_is_seen(monkeypatch):
+    """a launch that writes into a storage above BIG_STORAGE keeps only the device-side verdict; one stray element turns it"""
+    monkeypatch.setattr(S, "BIG_STORAGE", 64)
+    from ubresnet_amd import ops
+    buf = torch.zeros(4096, dtype=torch.float64)
+    src = torch.arange(64, dtype=torch.float64)
+
+    def stray(g, red):
+        red[:16] += 1.0
+        buf[3000] = 5.0            # outside `red`
+    monkeypatch.setattr(ops, "channel_sum", stray)
+    tap = S.Tap(monkeypatch, sync=lambda: None)
+    ops.channel_sum(torch.zeros((1, 1, 1, 16), dtype=BF), buf[1024:1024 + 16 * kref.STAT_SLOTS])
+    rec = tap.tape[0].args["red"]
+    assert rec.big and rec.base_after is None and rec.outside == (1, 3000) and rec.base_init.numel() == 4096
+    with pytest.raises(AssertionError, match="outside its output"):
+        S._check_untouched(0, tap.tape[0])
