@@ -318,7 +318,7 @@ def test_bench_self_launches_two_ranks_dry_run():
 
 def test_no_16_byte_buffer_store_with_scalar_offset_in_the_built_library():
     """gfx950 + hipcc 7.2: a buffer_store_dwordx3/x4 with an SGPR soffset gets no wait state before a VALU write to its data
-    registers, and the store then sends corrupted data (ubresnet_amd/csrc/ubr_conv.hip, buf_store16).  The sources fold scalar
+    registers, and the store then sends corrupted data (ubresnet_amd/csrc/ubr_conv_epi.h, buf_store16).  The sources fold scalar
     offsets into the vector offset for such stores; scan the device code of the library build() produced to keep it that way."""
     import importlib.util
     lib = os.path.join(REPO, "ubresnet_amd", "libubresnet_hip.so")

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Scan the built library's gfx950 code for the 16-byte buffer-store hazard (ubresnet_amd/csrc/ubr_conv.hip, buf_store16).
+"""Scan the built library's gfx950 code for the 16-byte buffer-store hazard (ubresnet_amd/csrc/ubr_conv_epi.h, buf_store16).
 
 A `buffer_store_dwordx3/x4` whose soffset is an SGPR gets no wait state from hipcc (ROCm 7.2) before a VALU write to its data
 registers; on gfx950 that corrupts the stored data.  The sources avoid the form (scalar offsets are folded into the vector offset

@@ -26,7 +26,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libubresnet_hip.so")
 SOURCES = ["ubr_conv.hip", "ubr_aspp.hip", "ubr_wgrad.hip", "ubr_elem.hip", "ubr_head.hip", "ubr_tape.hip"]
-HEADERS = ["ubr_common.h", "ubr_host.h", os.path.join("..", "..", "include", "ubresnet_hip.h")]
+HEADERS = ["ubr_common.h", "ubr_conv_epi.h", "ubr_host.h", os.path.join("..", "..", "include", "ubresnet_hip.h")]
 Lib = namedtuple("Lib", "out sources headers binding")
 
 

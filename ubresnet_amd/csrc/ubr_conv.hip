@@ -13,9 +13,13 @@
 //
 // Workgroup = 256 threads = 4 waves.  Tile = TH x TW output pixels (TW = 16*TWF) x TN = 16*NT
 // output channels.  Wave w owns FW pixel fragments (16 px each) x NT channel fragments.
+//
+// What happens to an accumulator after the MFMA loop -- bias, activations, addend, statistics, the two store forms, the fused
+// log-softmax -- is one contract for the three kernels of this file and is written once, in ubr_conv_epi.h.
 #include <stdlib.h>
 #include <type_traits>
 #include "ubr_common.h"
+#include "ubr_conv_epi.h"
 #include "ubr_host.h"
 
 namespace {
@@ -48,8 +52,7 @@ struct ConvK {
   const char* bc; long bc_sn, bc_sy, bc_sx;      // saved activation c of the BatchNorm-backward sums (view of the output grid)
   const float *bmean, *bscale, *bshift, *binvstd;
   int nslots;                                    // stripes of `stats` in use
-  int pair_store;                                // conv_igemm_kernel: 16-byte stores of fragment pairs
-  int fast_epi;                                  // conv_igemm_kernel: per-image output / addend extents fit 31-bit offsets (buffer-addressed epilogue)
+  int fast_epi;                                  // conv_igemm_kernel / conv_pc_kernel: per-image output / addend extents fit 31-bit offsets (buffer-addressed epilogue)
   // several output phases in one launch (blockIdx.z; ubr_conv_desc.nphase): each has its own tap range, output and addend base
   int ptap0[4], pnunits[4], psteps[4];
   long pyoff[4], paoff[4];                       // bytes
@@ -57,62 +60,6 @@ struct ConvK {
   uint8_t wt[UBR_MAX_TAPS];
   unsigned long long* stamps;                    // diagnostic build (-DUBR_CONV_STAMPS): per-workgroup phase cycle sums
 };
-
-template <typename T> __device__ __forceinline__ void store4(char* p, const float* v);
-template <> __device__ __forceinline__ void store4<float>(char* p, const float* v) {
-  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-}
-template <> __device__ __forceinline__ void store4<bf16_t>(char* p, const float* v) {
-  *reinterpret_cast<uint2*>(p) = make_uint2(ET<bf16_t>::pk2(v[0], v[1]), ET<bf16_t>::pk2(v[2], v[3]));
-}
-template <> __device__ __forceinline__ void store4<f16_t>(char* p, const float* v) {
-  f16x4_t h; h[0] = (_Float16)v[0]; h[1] = (_Float16)v[1]; h[2] = (_Float16)v[2]; h[3] = (_Float16)v[3];
-  *reinterpret_cast<uint2*>(p) = __builtin_bit_cast(uint2, h);
-}
-template <typename T> __device__ __forceinline__ void load4(const char* p, float* v);
-template <> __device__ __forceinline__ void load4<float>(const char* p, float* v) {
-  float4 f = *reinterpret_cast<const float4*>(p); v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-}
-template <> __device__ __forceinline__ void load4<bf16_t>(const char* p, float* v) {
-  uint2 u = *reinterpret_cast<const uint2*>(p);
-  v[0] = __uint_as_float(u.x << 16); v[1] = __uint_as_float(u.x & 0xffff0000u);
-  v[2] = __uint_as_float(u.y << 16); v[3] = __uint_as_float(u.y & 0xffff0000u);
-}
-template <> __device__ __forceinline__ void load4<f16_t>(const char* p, float* v) {
-  f16x4_t h = __builtin_bit_cast(f16x4_t, *reinterpret_cast<const uint2*>(p));
-  v[0] = (float)h[0]; v[1] = (float)h[1]; v[2] = (float)h[2]; v[3] = (float)h[3];
-}
-
-// v rounded to the storage type (what a later pass would read back from the stored tensor)
-template <typename T> __device__ __forceinline__ void round4(const float* v, float* r);
-template <> __device__ __forceinline__ void round4<float>(const float* v, float* r) { r[0] = v[0]; r[1] = v[1]; r[2] = v[2]; r[3] = v[3]; }
-template <> __device__ __forceinline__ void round4<bf16_t>(const float* v, float* r) {
-  // round-to-nearest-even on the bit pattern (integer ops; NaN kept as NaN): the result v_cvt_pk_bf16_f32 gives
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const uint32_t u = __float_as_uint(v[i]);
-    const uint32_t rne = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
-    r[i] = __uint_as_float((u & 0x7fffffffu) > 0x7f800000u ? (u | 0x00400000u) & 0xffff0000u : rne);
-  }
-}
-template <> __device__ __forceinline__ void round4<f16_t>(const float* v, float* r) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) r[i] = (float)(_Float16)v[i];
-}
-// BatchNorm-backward sums of one 4-channel group: g_y = g*[bn(c) > 0], xhat = (c - mean)*invstd (same operations as bn_bwd_kernel)
-__device__ __forceinline__ void bnb_accumulate(const float* g, const float* c, const float4& mu, const float4& sc, const float4& sh, const float4& is,
-                                               float* s1, float* s2) {
-  const float m[4] = {mu.x, mu.y, mu.z, mu.w}, a[4] = {sc.x, sc.y, sc.z, sc.w}, b[4] = {sh.x, sh.y, sh.z, sh.w}, iv[4] = {is.x, is.y, is.z, is.w};
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float d = c[r] - m[r];
-    const float bn = __builtin_fmaf(d, a[r], b[r]);
-    const float xh = d * iv[r];
-    const float gy = bn > 0.f ? g[r] : 0.f;
-    s1[r] += gy;
-    s2[r] += gy * xh;
-  }
-}
 
 // LDS bytes per halo pixel.  A ds_read_b128 is served in four groups of 16 lanes that each pair 8 lanes of one quad with the
 // COMPLEMENTARY 8 lanes of the next quad ({0-3,12-15 | 20-27}, {4-11 | 16-19,28-31}, ... -- MI355X_MICROARCH.md, LDS table),
@@ -137,59 +84,7 @@ __host__ __device__ constexpr int thin_pixb(int upb) { return upb == 4 ? UBR_THI
 __host__ __device__ constexpr int conv_pipe_hslots(int fw, int twf) { return ((4 * fw / twf + 2) * (twf * 16 + 2) * 4 + 255) / 256; }
 __host__ __device__ constexpr int conv_pipe_wslots(int nt) { return (36 * nt * 16 + 255) / 256; }
 
-// Two pixel fragments' 4-channel groups (fp32) -> this lane's 16 output bytes after the quad exchange (see store_pair16).
-// bf16: converts and swaps in ONE asm statement with early-clobber outputs; wait states by hand (hipcc pads nothing inside asm).
-// (The wrong lanes 12-15 once seen after this block were the 16-byte store hazard described at buf_store16: a convert writing the
-// data registers of the store issued just before it.)
-template <typename T> __device__ __forceinline__ uint4 pack_swap_pair(const float* v0, const float* v1);
-template <> __device__ __forceinline__ uint4 pack_swap_pair<bf16_t>(const float* v0, const float* v1) {
-  uint2 X, Y;
-  asm volatile("v_cvt_pk_bf16_f32 %0, %4, %5\n\tv_cvt_pk_bf16_f32 %1, %6, %7\n\tv_cvt_pk_bf16_f32 %2, %8, %9\n\t"
-               "v_cvt_pk_bf16_f32 %3, %10, %11\n\ts_nop 1\n\tv_permlane16_swap_b32 %0, %2\n\tv_permlane16_swap_b32 %1, %3\n\ts_nop 3"
-               : "=&v"(X.x), "=&v"(X.y), "=&v"(Y.x), "=&v"(Y.y)
-               : "v"(v0[0]), "v"(v0[1]), "v"(v0[2]), "v"(v0[3]), "v"(v1[0]), "v"(v1[1]), "v"(v1[2]), "v"(v1[3]));
-  return make_uint4(X.x, X.y, Y.x, Y.y);
-}
-template <> __device__ __forceinline__ uint4 pack_swap_pair<f16_t>(const float* v0, const float* v1) {
-  f16x4_t a, b;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) { a[r] = (_Float16)v0[r]; b[r] = (_Float16)v1[r]; }
-  uint2 X = __builtin_bit_cast(uint2, a), Y = __builtin_bit_cast(uint2, b);
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3\n\ts_nop 3" : "+v"(X.x), "+v"(Y.x), "+v"(X.y), "+v"(Y.y));
-  return make_uint4(X.x, X.y, Y.x, Y.y);
-}
-template <> __device__ __forceinline__ uint4 pack_swap_pair<float>(const float* v0, const float* v1) { return make_uint4(0u, 0u, 0u, 0u); }
-
-// 16-bit types: lane (q, l16) holds channels 4q..4q+3 of pixel l16 of fragment 0 (X) and of fragment 1 (Y), 8 bytes each.
-// v_permlane16_swap exchanges the odd quads of X with the even quads of Y: afterwards an even quad holds channels
-// 4q..4q+7 of its fragment-0 pixel and an odd quad channels 4(q-1)..4q+3 of its fragment-1 pixel -- 16 contiguous bytes.
-// p0 / p1 address channel 4q of the lane's pixel in fragment 0 / 1.
-template <typename T> __device__ __forceinline__ void store_frag_pair(char* p0, char* p1, bool ok0, bool ok1, const float* v0, const float* v1, int q) {
-  if constexpr (std::is_same<T, float>::value) {
-    if (ok0) store4<float>(p0, v0);
-    if (ok1) store4<float>(p1, v1);
-  } else {
-    const uint4 v = pack_swap_pair<T>(v0, v1);
-    const bool odd = (q & 1) != 0;
-    char* p = odd ? (p1 - 8) : p0;          // an odd quad's 16 bytes start one quad (4 channels) lower
-    if (odd ? ok1 : ok0) *reinterpret_cast<uint4*>(p) = v;
-  }
-}
-
-typedef __attribute__((ext_vector_type(2))) unsigned ubr_u2;
 __device__ __forceinline__ unsigned udiv_magic(unsigned n, unsigned magic) { return magic == 0u ? n : __umulhi(n, magic); }
-
-// 16-byte buffer store with a scalar offset.  gfx950 reads a store's data registers over several cycles; a VALU write to them in the
-// next instruction slot corrupts what the store sends (observed: the second dword of lanes 12-15 of each 16-lane row).  hipcc (ROCm 7.2)
-// inserts the wait state for stores wider than 8 bytes only when soffset is NOT an SGPR (it assumes the scalar operand fetch hides the
-// hazard -- it does not on this part: ISA of the fp32 epilogues, `buffer_store_dwordx4 v[96:99], v135, s[24:27], s90 offen` directly
-// followed by `v_pk_add_f32 v[96:97], ...`).  So 16-byte stores fold the scalar offset into the vector one (one v_add) and leave
-// soffset zero, which puts them under the compiler's own hazard handling; 8-byte stores are not affected.  (This is what the "stale
-// lanes 12-15" failures of the training epilogues in round 3 were; they had first been put down to MFMA result latency and to a
-// v_cvt_pk_bf16_f32 next to v_permlane16_swap.)
-__device__ __forceinline__ void buf_store16(const ubr_u4& v, __amdgpu_buffer_rsrc_t r, int voff, int soff) {
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, voff + soff, 0, 0);
-}
 
 template <typename T, int FW, int NT, int TWF, bool PIPE>
 __global__ __launch_bounds__(256, ((NT == 4 && FW <= 2 && !PIPE) ? 4 : 2)) void conv_igemm_kernel(const ConvK k) {
@@ -410,24 +305,21 @@ __global__ __launch_bounds__(256, ((NT == 4 && FW <= 2 && !PIPE) ? 4 : 2)) void 
 #ifdef UBR_CONV_STAMPS
     unsigned long long tS = 0, tL = 0, tC = 0, tB = 0, tW = 0, t_ = __builtin_amdgcn_s_memtime();
     const unsigned long long t_begin = t_;
-#define UBR_STAMP(acc_) do { unsigned long long n_ = __builtin_amdgcn_s_memtime(); acc_ += n_ - t_; t_ = n_; } while (0)
-#else
-#define UBR_STAMP(acc_) do { } while (0)
 #endif
-    UBR_STAMP(tL);
+    UBR_CONV_STAMP(tL);
     for (int blk = 0; blk < k.nblk; ++blk) {
       __syncthreads();          // previous block's fragments fully read (block 0: the constants above are visible)
 #ifdef UBR_CONV_STAMPS
-      UBR_STAMP(tB);
+      UBR_CONV_STAMP(tB);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      UBR_STAMP(tW);
+      UBR_CONV_STAMP(tW);
 #endif
       store_blk(blk);
-      UBR_STAMP(tS);
+      UBR_CONV_STAMP(tS);
       __syncthreads();
-      UBR_STAMP(tB);
+      UBR_CONV_STAMP(tB);
       if (blk + 1 < k.nblk) load_blk(blk + 1);
-      UBR_STAMP(tL);
+      UBR_CONV_STAMP(tL);
       for (int s = 0; s < p_steps; ++s) {
         const int off = tbl[4 * s + q];
         uint4 wf[NT];
@@ -441,7 +333,7 @@ __global__ __launch_bounds__(256, ((NT == 4 && FW <= 2 && !PIPE) ? 4 : 2)) void 
           for (int j = 0; j < NT; ++j) acc[i][j] = mma_step<T>(acc[i][j], wf[j], a);
         }
       }
-      UBR_STAMP(tC);
+      UBR_CONV_STAMP(tC);
     }
 #ifdef UBR_CONV_STAMPS
     if (k.stamps != nullptr && tid == 0) {
@@ -543,112 +435,32 @@ __global__ __launch_bounds__(256, ((NT == 4 && FW <= 2 && !PIPE) ? 4 : 2)) void 
   const unsigned long long te0 = __builtin_amdgcn_s_memtime();
 #endif
   float bs[NT][4];
-#pragma unroll
-  for (int j = 0; j < NT; ++j)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int ch = n0 + j * 16 + 4 * q + r;
-      bs[j][r] = (k.bias != nullptr && ch < k.Cout) ? k.bias[ch] : 0.f;
-    }
+  load_bias<NT>(bs, k.bias, n0, q, k.Cout);
   float s1[NT][4], s2[NT][4];
 #pragma unroll
   for (int j = 0; j < NT; ++j)
 #pragma unroll
     for (int r = 0; r < 4; ++r) { s1[j][r] = 0.f; s2[j][r] = 0.f; }
 
-  // Buffer-addressed epilogue (plain output, no BatchNorm-backward sums): beside an MFMA-bound wave of the other resident workgroup
-  // every VALU instruction of this phase costs ~10 cycles, and the general form below spends ~25 of its ~40 instructions per store
-  // on 64-bit addresses and per-fragment tests (in-kernel stamps, 16x128x128x64 -> 64: 11 k of the workgroup's 47 k cycles were
-  // "values + stores").  Here a store's address is one per-lane offset computed once plus a SCALAR fragment offset; lanes outside the
-  // output (ragged tiles, padded channels) get an out-of-range offset, which drops the store / returns a zero addend; all addend and
-  // mask loads are issued before the first value is finished.  Same arithmetic per value, in the same order.
-  if (k.fast_epi && k.epilogue == 0 && k.bc == nullptr && !(FW % 2 == 0 && sizeof(T) == 2 && k.pair_store)) {
-    constexpr int kOut = (int)0x80000000;
-    const int wv = __builtin_amdgcn_readfirstlane(wave);
-    const bool full = (ox0 + TW <= k.OW) && (oy0 + TH <= k.OH) && (n0 + TN <= k.Cout);
-    const int ysx = (int)k.y_sx, ysy = (int)k.y_sy, asx = (int)k.a_sx, asy = (int)k.a_sy;
-    const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(yb + (long)n * k.y_sn + (long)oy0 * k.y_sy + (long)ox0 * k.y_sx + (long)n0 * ESZ), 0, 0x7fffffff, 0x00020000);
-    const bool has_ad = adb != nullptr, has_mask = has_ad && k.ad_mask != nullptr;
-    const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(has_ad ? adb + (long)n * k.a_sn + (long)oy0 * k.a_sy + (long)ox0 * k.a_sx + (long)n0 * ESZ : k.x), 0, has_ad ? 0x7fffffff : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t mr = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(has_mask ? (const char*)k.ad_mask + (((long)n * k.OH + oy0) * k.OW + ox0) * k.ad_mask_cu + n0 / CPU : k.x), 0, has_mask ? 0x7fffffff : 0, 0x00020000);
-    const int lane_y = l16 * ysx + 4 * q * ESZ, lane_a = l16 * asx + 4 * q * ESZ, lane_m = l16 * k.ad_mask_cu + (4 * q) / CPU;
-    // per fragment: scalar offsets and (ragged tiles only) the lane's validity
-    int so_y[FW], so_a[FW], so_m[FW];
-    bool okp[FW];        // pixel inside the output
-#pragma unroll
-    for (int i = 0; i < FW; ++i) {
-      const int f = wv * FW + i, fr = f / TWF, fc = f % TWF;
-      so_y[i] = fr * ysy + fc * 16 * ysx; so_a[i] = fr * asy + fc * 16 * asx; so_m[i] = (fr * k.OW + fc * 16) * k.ad_mask_cu;
-      okp[i] = full || ((oy0 + fr < k.OH) && (ox0 + fc * 16 + l16 < k.OW));
-    }
-    bool okc[NT];        // channel group inside Cout
-#pragma unroll
-    for (int j = 0; j < NT; ++j) okc[j] = full || (n0 + j * 16 + 4 * q < k.Cout);
-    ubr_u4 adv[FW][NT];  // raw addend: 8 bytes (16-bit types) or 16
-    unsigned admk[FW][NT];
-    if (has_ad) {
-#pragma unroll
-      for (int i = 0; i < FW; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          const int vo = (okp[i] && okc[j]) ? lane_a : kOut;
-          if constexpr (sizeof(T) == 2) {
-            const auto t2 = __builtin_amdgcn_raw_buffer_load_b64(ar, vo, so_a[i] + j * 16 * ESZ, 0);
-            adv[i][j] = ubr_u4{t2[0], t2[1], 0u, 0u};
-          } else {
-            adv[i][j] = __builtin_amdgcn_raw_buffer_load_b128(ar, vo, so_a[i] + j * 16 * ESZ, 0);
-          }
-          if (has_mask) admk[i][j] = __builtin_amdgcn_raw_buffer_load_b8(mr, (okp[i] && okc[j]) ? lane_m : kOut, so_m[i] + j * (16 / CPU), 0);
-        }
-    }
+  // Buffer-addressed epilogue (FastEpi; plain output, no BatchNorm-backward sums): beside an MFMA-bound wave of the other resident
+  // workgroup every VALU instruction of this phase costs ~10 cycles, and the general form below spends ~25 of its ~40 instructions
+  // per store on 64-bit addresses and per-fragment tests (in-kernel stamps, 16x128x128x64 -> 64: 11 k of the workgroup's 47 k cycles
+  // were "values + stores").  Same arithmetic per value, in the same order.
+  if (k.fast_epi && k.epilogue == 0 && k.bc == nullptr) {
+    FastEpi<T, FW, NT, TWF> fe;
+    fe.init(k, yb, adb, k.ad_mask, n, oy0, ox0, n0, wave, l16, q);
+    fe.prefetch_addend();
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
 #pragma unroll
       for (int i = 0; i < FW; ++i) {
         float v[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = acc[i][j][r] + bs[j][r];
-        if (k.act & 1) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-        }
-        if (has_ad) {
-          float a4[4];
-          if constexpr (sizeof(T) == 2) {
-            const uint2 raw = make_uint2(adv[i][j][0], adv[i][j][1]);
-            load4<T>(reinterpret_cast<const char*>(&raw), a4);
-          } else {
-            a4[0] = __uint_as_float(adv[i][j][0]); a4[1] = __uint_as_float(adv[i][j][1]); a4[2] = __uint_as_float(adv[i][j][2]); a4[3] = __uint_as_float(adv[i][j][3]);
-          }
-          if (has_mask) {
-            const unsigned mb = (admk[i][j] & 0xffu) >> ((4 * q) % CPU);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) a4[r] = ((mb >> r) & 1u) ? a4[r] : 0.f;
-          }
-          if (okp[i] && okc[j]) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] += a4[r];
-          }
-        }
-        if (k.act & 2) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-        }
-        if (k.stats != nullptr && okp[i]) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) { s1[j][r] += v[r]; s2[j][r] += v[r] * v[r]; }
-        }
-        const int vo = (okp[i] && okc[j]) ? lane_y : kOut;
-        if constexpr (sizeof(T) == 2) {
-          uint2 pk;
-          store4<T>(reinterpret_cast<char*>(&pk), v);
-          __builtin_amdgcn_raw_buffer_store_b64(ubr_u2{pk.x, pk.y}, yr, vo, so_y[i] + j * 16 * ESZ, 0);
-        } else {
-          buf_store16(ubr_u4{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])}, yr, vo, so_y[i] + j * 16 * ESZ);
-        }
+        finish4(v, acc[i][j], bs[j], k.act, fe.has_ad && fe.inside(i, j), fe.has_mask, [&](float* a4, unsigned& mb) {
+          fe.addend(i, j, a4);
+          if (fe.has_mask) mb = fe.mask_bits(i, j);
+        });
+        if (k.stats != nullptr && fe.okp[i]) stat_add4(s1[j], s2[j], v);
+        fe.store(i, j, v);
       }
     }
   } else
@@ -662,122 +474,37 @@ __global__ __launch_bounds__(256, ((NT == 4 && FW <= 2 && !PIPE) ? 4 : 2)) void 
       bmu = *reinterpret_cast<const float4*>(k.bmean + ch); bsc = *reinterpret_cast<const float4*>(k.bscale + ch);
       bsh = *reinterpret_cast<const float4*>(k.bshift + ch); bis = *reinterpret_cast<const float4*>(k.binvstd + ch);
     }
-    // one fragment's 4-channel group: bias, activations, (masked) addend, statistics
-    auto finish = [&](int i, float* v, int& oy, int& ox) -> bool {
+#pragma unroll
+    for (int i = 0; i < FW; ++i) {
       const int f = wave * FW + i;
-      oy = oy0 + f / TWF; ox = ox0 + (f % TWF) * 16 + l16;
+      const int oy = oy0 + f / TWF, ox = ox0 + (f % TWF) * 16 + l16;
       const bool valid = (oy < k.OH) && (ox < k.OW);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = acc[i][j][r] + bs[j][r];
-      if (k.act & 1) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-      }
-      if (adb != nullptr && valid && ch < k.Cout) {
-        float a4[4];
-        load4<T>(adb + (long)n * k.a_sn + (long)oy * k.a_sy + (long)ox * k.a_sx + (long)ch * ESZ, a4);
-        if (k.ad_mask != nullptr) {
-          const unsigned mb = (unsigned)k.ad_mask[(((long)n * k.OH + oy) * k.OW + ox) * k.ad_mask_cu + ch / CPU] >> (ch % CPU);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) a4[r] = ((mb >> r) & 1u) ? a4[r] : 0.f;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] += a4[r];
-      }
-      if (k.act & 2) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-      }
+      float v[4];
+      generic_finish4<T>(v, acc[i][j], bs[j], k, adb, k.ad_mask, n, oy, ox, ch, valid && ch < k.Cout);
       if (k.stats != nullptr && valid) {
         if (k.bc != nullptr) {
           if (bnb) {
             float g4[4], c4[4];
             round4<T>(v, g4);
-            load4<T>(k.bc + (long)n * k.bc_sn + (long)oy * k.bc_sy + (long)ox * k.bc_sx + (long)ch * ESZ, c4);
+            load4<T>(k.bc + nhwc_off<T>(k.bc_sn, k.bc_sy, k.bc_sx, n, oy, ox, ch), c4);
             bnb_accumulate(g4, c4, bmu, bsc, bsh, bis, s1[j], s2[j]);
           }
         } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) { s1[j][r] += v[r]; s2[j][r] += v[r] * v[r]; }
+          stat_add4(s1[j], s2[j], v);
         }
       }
-      return valid;
-    };
-    // 16-bit outputs with whole, 16-byte aligned channel octets: two pixel fragments exchange half their channels
-    // (v_permlane16_swap) and every lane stores 16 bytes -- half the store instructions of the 8-byte form, which split every
-    // 128-byte line of the output into sixteen pieces
-    constexpr bool PAIRS = (FW % 2 == 0) && sizeof(T) == 2;
-    if (PAIRS && k.pair_store && k.epilogue == 0) {
-#pragma unroll
-      for (int i = 0; i < FW; i += 2) {
-        float v0[4], v1[4];
-        int oy_a, ox_a, oy_b, ox_b;
-        const bool ok0 = finish(i, v0, oy_a, ox_a) && ch < k.Cout;
-        const bool ok1 = finish(i + (FW > 1 ? 1 : 0), v1, oy_b, ox_b) && ch < k.Cout;
-        store_frag_pair<T>(yb + (long)n * k.y_sn + (long)oy_a * k.y_sy + (long)ox_a * k.y_sx + (long)ch * ESZ,
-                           yb + (long)n * k.y_sn + (long)oy_b * k.y_sy + (long)ox_b * k.y_sx + (long)ch * ESZ, ok0, ok1, v0, v1, q);
-      }
-    } else {
-#pragma unroll
-    for (int i = 0; i < FW; ++i) {
-      float v[4];
-      int oy, ox;
-      const bool valid = finish(i, v, oy, ox);
       if (k.epilogue == 0) {
-        if (valid && ch < k.Cout)
-          store4<T>(yb + (long)n * k.y_sn + (long)oy * k.y_sy + (long)ox * k.y_sx + (long)ch * ESZ, v);
+        if (valid && ch < k.Cout) store4<T>(yb + nhwc_off<T>(k.y_sn, k.y_sy, k.y_sx, n, oy, ox, ch), v);
       } else if (j == 0) {
-        // fused LogSoftmax over the first Cout (<=16) channels, fp32 NCHW output
-        float m = -3.0e38f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) if (ch + r < k.Cout) m = fmaxf(m, v[r]);
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-        float e = 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) if (ch + r < k.Cout) e += expf(v[r] - m);
-        e += __shfl_xor(e, 16, 64);
-        e += __shfl_xor(e, 32, 64);
-        const float lse = m + logf(e);
-        if (valid) {
-          float* o = reinterpret_cast<float*>(k.y);
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (ch + r < k.Cout) o[(((long)n * k.Cout + ch + r) * k.OH + oy) * k.OW + ox] = v[r] - lse;
-        }
+        logsoftmax16_store(v, ch, k.Cout, valid, reinterpret_cast<float*>(k.y), n, oy, ox, k.OH, k.OW);
       }
-    }
     }
   }
 
 #ifdef UBR_CONV_STAMPS
   const unsigned long long te1 = __builtin_amdgcn_s_memtime();
 #endif
-  if (k.stats != nullptr) {
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float a = wave_quadrow_sum16(s1[j][r]);
-        const float b = wave_quadrow_sum16(s2[j][r]);
-        if (l16 == 0) {
-          red[(wave * TN + j * 16 + 4 * q + r) * 2 + 0] = a;
-          red[(wave * TN + j * 16 + 4 * q + r) * 2 + 1] = b;
-        }
-      }
-    __syncthreads();
-    if (tid < TN) {
-      const int ch = n0 + tid;
-      if (ch < k.Cout) {
-        double a = 0.0, b = 0.0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { a += (double)red[(w * TN + tid) * 2]; b += (double)red[(w * TN + tid) * 2 + 1]; }
-        double* st = k.stats + (size_t)(blockIdx.x % k.nslots) * 2 * k.Cout;
-        atomicAdd(&st[ch], a);
-        atomicAdd(&st[k.Cout + ch], b);
-      }
-    }
-  }
+  if (k.stats != nullptr) flush_tile_stats<NT>(s1, s2, red, wave, l16, q, tid, n0, k.Cout, k.stats, k.nslots);
 #ifdef UBR_CONV_STAMPS
   if (PIPE && k.stamps != nullptr) {
     const unsigned long long te2 = __builtin_amdgcn_s_memtime();
@@ -928,13 +655,7 @@ __global__ __launch_bounds__(256, ((ROW7 || (EXT == 1 && NT == 2)) ? 2 : 3)) voi
     }
   }
   float bs[NT][4];
-#pragma unroll
-  for (int j = 0; j < NT; ++j)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int ch = n0 + j * 16 + 4 * q + r;
-      bs[j][r] = (k.bias != nullptr && ch < k.Cout) ? k.bias[ch] : 0.f;
-    }
+  load_bias<NT>(bs, k.bias, n0, q, k.Cout);
   // BatchNorm+ReLU-on-load constants live in LDS ([4][UPB*CPU] floats behind the statistics scratch), not in 32 registers held
   // across the MFMA loop: the XF variants of the 32-channel tiles spilled.  (Same (x - mean)*scale + beta form as every other
   // kernel of the library: an activation re-formed on load by the forward conv, the weight gradient and the BatchNorm
@@ -1038,14 +759,11 @@ __global__ __launch_bounds__(256, ((ROW7 || (EXT == 1 && NT == 2)) ? 2 : 3)) voi
 #ifdef UBR_CONV_STAMPS
   unsigned long long tS = 0, tL = 0, tC = 0, tE = 0, tB = 0, tW = 0, t_ = __builtin_amdgcn_s_memtime();
   const unsigned long long t_begin = t_;
-#define UBR_TSTAMP(acc_) do { unsigned long long n_ = __builtin_amdgcn_s_memtime(); acc_ += n_ - t_; t_ = n_; } while (0)
-#else
-#define UBR_TSTAMP(acc_) do { } while (0)
 #endif
   while (tile < ntiles) {
 #ifdef UBR_CONV_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    UBR_TSTAMP(tW);
+    UBR_CONV_STAMP(tW);
 #endif
     // ---- halo of this tile: transform, write to LDS (slots beyond the halo hold zeros and land in the slack of the region) ----
     float xsub[XF ? CPU : 1], xsc[XF ? CPU : 1], xsh[XF ? CPU : 1], xlo[XF ? CPU : 1];
@@ -1069,9 +787,9 @@ __global__ __launch_bounds__(256, ((ROW7 || (EXT == 1 && NT == 2)) ? 2 : 3)) voi
       }
       if (tid + u * 256 < k.nitems) *reinterpret_cast<uint4*>(halo_w + u * (PPS * PIXB)) = v;     // (the region holds the halo exactly)
     }
-    UBR_TSTAMP(tS);
+    UBR_CONV_STAMP(tS);
     __syncthreads();
-    UBR_TSTAMP(tB);
+    UBR_CONV_STAMP(tB);
     const unsigned t = (unsigned)__builtin_amdgcn_readfirstlane(tile);
     const unsigned rr = udiv_magic(t, k.tx_magic), tx = t - rr * (unsigned)k.tiles_x;
     const unsigned n = udiv_magic(rr, k.ty_magic), ty = rr - n * (unsigned)k.tiles_y;
@@ -1091,7 +809,7 @@ __global__ __launch_bounds__(256, ((ROW7 || (EXT == 1 && NT == 2)) ? 2 : 3)) voi
       mr = __builtin_amdgcn_make_buffer_rsrc((void*)(k.ad_mask + (long)n * k.mask_bytes), 0, (int)k.mask_bytes, 0x00020000);
       mbase = (oy0 * k.OW + ox0) * k.ad_mask_cu;
     }
-    UBR_TSTAMP(tL);
+    UBR_CONV_STAMP(tL);
 
 #pragma unroll 1
     for (int g0 = 0; g0 < FW; g0 += FH) {
@@ -1191,7 +909,7 @@ __global__ __launch_bounds__(256, ((ROW7 || (EXT == 1 && NT == 2)) ? 2 : 3)) voi
           for (int j = 0; j < NT; ++j) acc[i][j] = mma_step<T>(acc[i][j], wf[j], a[i]);
       }
       }   // !ROW7
-      UBR_TSTAMP(tC);
+      UBR_CONV_STAMP(tC);
 
       // ---- epilogue of this fragment group ----
 #pragma unroll
@@ -1244,8 +962,7 @@ __global__ __launch_bounds__(256, ((ROW7 || (EXT == 1 && NT == 2)) ? 2 : 3)) voi
               bnb_accumulate(g4, c4, *reinterpret_cast<const float4*>(cc), *reinterpret_cast<const float4*>(cc + TN),
                              *reinterpret_cast<const float4*>(cc + 2 * TN), *reinterpret_cast<const float4*>(cc + 3 * TN), s1[j], s2[j]);
             } else if (k.stats != nullptr) {
-#pragma unroll
-              for (int r = 0; r < 4; ++r) { s1[j][r] += v[h][r]; s2[j][r] += v[h][r] * v[h][r]; }
+              stat_add4(s1[j], s2[j], v[h]);
             }
           }
           const int so = ybase + ((g0 + i) / TWF) * k.y_sy + y_ph;
@@ -1267,35 +984,18 @@ __global__ __launch_bounds__(256, ((ROW7 || (EXT == 1 && NT == 2)) ? 2 : 3)) voi
             (void)so;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-              // fused LogSoftmax over the first Cout (<=16) channels, fp32 NCHW output
-              const int ch = 4 * q;
-              const int f = wave * FW + g0 + i + h;
-              const int oy = oy0 + f / TWF, ox = ox0 + (f % TWF) * 16 + l16;
-              float m = -3.0e38f;
-#pragma unroll
-              for (int r = 0; r < 4; ++r) if (ch + r < k.Cout) m = fmaxf(m, v[h][r]);
-              m = fmaxf(m, __shfl_xor(m, 16, 64));
-              m = fmaxf(m, __shfl_xor(m, 32, 64));
-              float e = 0.f;
-#pragma unroll
-              for (int r = 0; r < 4; ++r) if (ch + r < k.Cout) e += expf(v[h][r] - m);
-              e += __shfl_xor(e, 16, 64);
-              e += __shfl_xor(e, 32, 64);
-              const float lse = m + logf(e);
-              float* o = reinterpret_cast<float*>(k.y);
-#pragma unroll
-              for (int r = 0; r < 4; ++r)
-                if (ch + r < k.Cout) o[(((long)n * k.Cout + ch + r) * k.OH + oy) * k.OW + ox] = v[h][r] - lse;
+              const int f = wave * FW + g0 + i + h;        // (tiles are exact: every pixel is inside the output)
+              logsoftmax16_store(v[h], 4 * q, k.Cout, true, reinterpret_cast<float*>(k.y), (int)n, oy0 + f / TWF, ox0 + (f % TWF) * 16 + l16, k.OH, k.OW);
             }
           }
         }
       }
       }   // phases
-      UBR_TSTAMP(tE);
+      UBR_CONV_STAMP(tE);
     }   // fragment groups
     tile = next;
     if (tile < ntiles) __syncthreads();        // every wave is done with this tile's halo image before it is overwritten
-    UBR_TSTAMP(tB);
+    UBR_CONV_STAMP(tB);
   }
 #ifdef UBR_CONV_STAMPS
   if (k.stamps != nullptr && tid == 0) {
@@ -1304,32 +1004,8 @@ __global__ __launch_bounds__(256, ((ROW7 || (EXT == 1 && NT == 2)) ? 2 : 3)) voi
   }
 #endif
 
-  if (k.stats != nullptr) {
-    // (fp32 partial sums span all tiles of the workgroup: <= 16 tiles x 128 pixels per lane here, then fp64)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float a = wave_quadrow_sum16(s1[j][r]);
-        const float b = wave_quadrow_sum16(s2[j][r]);
-        if (l16 == 0) {
-          red[(wave * TN + j * 16 + 4 * q + r) * 2 + 0] = a;
-          red[(wave * TN + j * 16 + 4 * q + r) * 2 + 1] = b;
-        }
-      }
-    __syncthreads();
-    if (tid < TN) {
-      const int ch = n0 + tid;
-      if (ch < k.Cout) {
-        double a = 0.0, b = 0.0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { a += (double)red[(w * TN + tid) * 2]; b += (double)red[(w * TN + tid) * 2 + 1]; }
-        double* st = k.stats + (size_t)(blockIdx.x % k.nslots) * 2 * k.Cout;
-        atomicAdd(&st[ch], a);
-        atomicAdd(&st[k.Cout + ch], b);
-      }
-    }
-  }
+  // (fp32 partial sums span all tiles of the workgroup: <= 16 tiles x 128 pixels per lane here, then fp64)
+  if (k.stats != nullptr) flush_tile_stats<NT>(s1, s2, red, wave, l16, q, tid, n0, k.Cout, k.stats, k.nslots);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1514,41 +1190,39 @@ __global__ __launch_bounds__(512) void conv_pc_kernel(const ConvK k) {
 #ifdef UBR_CONV_STAMPS
     unsigned long long tS = 0, tL = 0, tB = 0, tW = 0, t_ = __builtin_amdgcn_s_memtime();
     const unsigned long long t_begin = t_;
-#define UBR_PSTAMP(acc_) do { unsigned long long n_ = __builtin_amdgcn_s_memtime(); acc_ += n_ - t_; t_ = n_; } while (0)
-#define UBR_PWAIT(n_) do { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(n_) : "memory"); UBR_PSTAMP(tW); } while (0)
+#define UBR_PWAIT(n_) do { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(n_) : "memory"); UBR_CONV_STAMP(tW); } while (0)
 #else
-#define UBR_PSTAMP(acc_) do { } while (0)
 #define UBR_PWAIT(n_) do { } while (0)
 #endif
     if (niter > 0) issue(hvA, wvA, hokA);
     if (niter > 1) issue(hvB, wvB, hokB);
-    UBR_PSTAMP(tL);
+    UBR_CONV_STAMP(tL);
     if (niter > 0) stage(hvA, wvA, hokA, 0);
-    UBR_PSTAMP(tS);
+    UBR_CONV_STAMP(tS);
     if (niter > 2) issue(hvA, wvA, hokA);
-    UBR_PSTAMP(tL);
+    UBR_CONV_STAMP(tL);
     __syncthreads();                                   // buffer 0 holds block 0
-    UBR_PSTAMP(tB);
+    UBR_CONV_STAMP(tB);
     for (int i = 0; i < niter; i += 2) {
       if (i + 1 < niter) {                             // consumers are in block i (buffer 0): block i+1 goes to buffer 1
         UBR_PWAIT(HS + WS);
         stage(hvB, wvB, hokB, 1);
-        UBR_PSTAMP(tS);
+        UBR_CONV_STAMP(tS);
         if (i + 3 < niter) issue(hvB, wvB, hokB);
-        UBR_PSTAMP(tL);
+        UBR_CONV_STAMP(tL);
       }
       __syncthreads();
-      UBR_PSTAMP(tB);
+      UBR_CONV_STAMP(tB);
       if (i + 1 >= niter) break;
       if (i + 2 < niter) {                             // consumers are in block i+1 (buffer 1): block i+2 goes to buffer 0
         UBR_PWAIT(HS + WS);
         stage(hvA, wvA, hokA, 0);
-        UBR_PSTAMP(tS);
+        UBR_CONV_STAMP(tS);
         if (i + 4 < niter) issue(hvA, wvA, hokA);
-        UBR_PSTAMP(tL);
+        UBR_CONV_STAMP(tL);
       }
       __syncthreads();
-      UBR_PSTAMP(tB);
+      UBR_CONV_STAMP(tB);
     }
 #ifdef UBR_CONV_STAMPS
     if (k.stamps != nullptr && ptid == 0) {
@@ -1604,7 +1278,7 @@ __global__ __launch_bounds__(512) void conv_pc_kernel(const ConvK k) {
     const unsigned long long t_begin = t_;
 #endif
     __syncthreads();                                   // buffer 0 holds block 0
-    UBR_PSTAMP(tB);
+    UBR_CONV_STAMP(tB);
     for (int i = 0; i < niter; ++i) {
       const char* wl = smem + k.wl_off + (i & 1) * k.buf_stride;
       const char* halo = smem + k.halo_off + (i & 1) * k.buf_stride;
@@ -1666,7 +1340,7 @@ __global__ __launch_bounds__(512) void conv_pc_kernel(const ConvK k) {
           for (int j = 0; j < NT; ++j) acc[i2][j] = mma_step<T>(acc[i2][j], wf[j], a[i2]);
       }
       }
-      UBR_PSTAMP(tC);
+      UBR_CONV_STAMP(tC);
       if (++cblk == k.nblk) {
         // ---------------------------------- epilogue of this unit ----------------------------------
         cblk = 0;
@@ -1683,15 +1357,10 @@ __global__ __launch_bounds__(512) void conv_pc_kernel(const ConvK k) {
           stat_n0 = n0;
         }
         float bs[NT][4];
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int ch = n0 + j * 16 + 4 * q + r;
-            bs[j][r] = (k.bias != nullptr && ch < k.Cout) ? k.bias[ch] : 0.f;
-          }
+        load_bias<NT>(bs, k.bias, n0, q, k.Cout);
         if (k.fast_epi) {
-          // buffer-addressed form (see conv_igemm_kernel's epilogue): one per-lane offset, scalar fragment offsets, addend loads up front
+          // buffer-addressed form: the set-up of FastEpi (ubr_conv_epi.h) without the mask, spelled out -- built on the struct this kernel
+          // gained scratch.  One per-lane offset, scalar fragment offsets, addend loads up front.
           constexpr int kOut = (int)0x80000000;
           const int wv = __builtin_amdgcn_readfirstlane(wave);
           const bool full = (ox0 + TW <= k.OW) && (oy0 + TH <= k.OH) && (n0 + TN <= k.Cout);
@@ -1802,13 +1471,13 @@ __global__ __launch_bounds__(512) void conv_pc_kernel(const ConvK k) {
           }
         }
       }
-      UBR_PSTAMP(tE);
+      UBR_CONV_STAMP(tE);
       __syncthreads();
-      UBR_PSTAMP(tB);
+      UBR_CONV_STAMP(tB);
     }
     if (k.stats != nullptr && stat_n0 >= 0) flush_stats(stat_n0);
 #ifdef UBR_CONV_STAMPS
-    UBR_PSTAMP(tE);
+    UBR_CONV_STAMP(tE);
     if (k.stamps != nullptr && tid == 0) {
       unsigned long long* o = k.stamps + (size_t)blockIdx.x * 16;
       o[0] = tC; o[1] = tE; o[2] = tB; o[3] = t_ - t_begin; o[4] = (unsigned long long)niter;
@@ -1835,36 +1504,32 @@ static const TileCfg kCfgs[] = {
 };
 constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
 
-template <typename T, int FW, int NT, int TWF, bool PIPE>
-int launch_one(const ConvK& k, dim3 grid, size_t lds, hipStream_t st) {
-  auto fn = conv_igemm_kernel<T, FW, NT, TWF, PIPE>;
+// One kernel instantiation FN: raise its dynamic-LDS limit when a launch needs more than it has had so far, launch, check.
+// `block` must be the kernel's own workgroup size: 256 threads for conv_igemm_kernel and conv_thin_kernel, 512 for conv_pc_kernel
+// (its __launch_bounds__); each family's wrapper below is the one place that pairs the two.
+template <auto FN, typename K>
+int launch_kernel(dim3 block, dim3 grid, size_t lds, hipStream_t st, const K& k) {
   if (lds > 64 * 1024) {
     static thread_local size_t maxset = 0;  // per instantiation
     if (lds > maxset) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(FN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (e != hipSuccess) { ubr_set_error("ubr_conv: cannot raise LDS limit to %zu: %s", lds, hipGetErrorString(e)); return UBR_ELAUNCH; }
       maxset = lds;
     }
   }
-  ubr_launch(fn, grid, dim3(256), lds, st, k);
+  ubr_launch(FN, grid, block, lds, st, k);
   UBR_LAUNCH_CHECK("ubr_conv");
   return UBR_OK;
 }
 
+template <typename T, int FW, int NT, int TWF, bool PIPE>
+int launch_one(const ConvK& k, dim3 grid, size_t lds, hipStream_t st) {
+  return launch_kernel<conv_igemm_kernel<T, FW, NT, TWF, PIPE>>(dim3(256), grid, lds, st, k);
+}
+
 template <typename T, int FW, int NT, int TWF, int UPB, bool XF, bool LSM = false, bool ROW7 = false, int EXT = 0>
 int launch_thin(const ThinK& k, dim3 grid, size_t lds, hipStream_t st) {
-  auto fn = conv_thin_kernel<T, FW, NT, TWF, UPB, XF, LSM, ROW7, EXT>;
-  if (lds > 64 * 1024) {
-    static thread_local size_t maxset = 0;
-    if (lds > maxset) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) { ubr_set_error("ubr_conv: cannot raise LDS limit to %zu: %s", lds, hipGetErrorString(e)); return UBR_ELAUNCH; }
-      maxset = lds;
-    }
-  }
-  ubr_launch(fn, grid, dim3(256), lds, st, k);
-  UBR_LAUNCH_CHECK("ubr_conv");
-  return UBR_OK;
+  return launch_kernel<conv_thin_kernel<T, FW, NT, TWF, UPB, XF, LSM, ROW7, EXT>>(dim3(256), grid, lds, st, k);
 }
 
 static unsigned magic_u32(unsigned d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + d - 1) / d); }
@@ -2039,18 +1704,7 @@ int launch_cfg(const ConvK& k, dim3 grid, size_t lds, hipStream_t st) {
 
 template <typename T, int FW, int TWF, int STEPS>
 int launch_pc_steps(const ConvK& k, dim3 grid, size_t lds, hipStream_t st) {
-  auto fn = conv_pc_kernel<T, FW, TWF, STEPS>;
-  if (lds > 64 * 1024) {
-    static thread_local size_t maxset = 0;
-    if (lds > maxset) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) { ubr_set_error("ubr_conv: cannot raise LDS limit to %zu: %s", lds, hipGetErrorString(e)); return UBR_ELAUNCH; }
-      maxset = lds;
-    }
-  }
-  ubr_launch(fn, grid, dim3(512), lds, st, k);
-  UBR_LAUNCH_CHECK("ubr_conv");
-  return UBR_OK;
+  return launch_kernel<conv_pc_kernel<T, FW, TWF, STEPS>>(dim3(512), grid, lds, st, k);
 }
 
 template <typename T, int FW, int TWF>
@@ -2399,7 +2053,6 @@ extern "C" int ubr_conv(const ubr_conv_desc* d, void* stream) {
   k.dbg = 0; k.stamps = nullptr;
 #endif
   k.wide_store = wide_ok ? 1 : 0;
-  { static const bool pairs = [] { const char* e = getenv("UBR_CONV_PAIRS"); return e && atoi(e) != 0; }(); k.pair_store = (wide_ok && pairs) ? 1 : 0; }
   {
     static const bool fe = [] { const char* e = getenv("UBR_CONV_FAST_EPI"); return !e || atoi(e) != 0; }();
     // (offsets are relative to the tile origin: at most a tile's rows times the row pitch)
